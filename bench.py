@@ -15,7 +15,12 @@ serial frames on one, where the per-launch roofline is measured).
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line with `roofline` (trace kernel, per launch: the counted
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON line with the headline
+(`value`, `ms_per_step`) and the run's configuration; `--dump-outputs DIR` also writes the frame of
+the last timed step to DIR/frame.npy.  Everything else is measured only with `--full`: the counting
+pass, the one-frame-per-launch leg, the CPU legs and the comparison with them.
+
+With `--full` the line also holds `roofline` (trace kernel, per launch: the counted
 traversal work ÷ the kernel's average duration measured with HIP events on its stream,
 against the resource that serves it — SURVEY.md §8(d)'s FLOP accounting against the FP32
 vector peak for LDS-resident scenes, whose scene bytes never reach HBM, and §8(d)'s
@@ -82,6 +87,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the counting pass behind `roofline` and "
+                         "`work_per_sample`, the `single_frame` leg, the CPU legs (`cpu_baseline`, `cpu_numpy`) "
+                         "and `l2_vs_cpu`; without it these fields are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the frame of the last timed step, as rank 0 holds it, "
+                         "to DIR/frame.npy: (W, H, 3) float32 radiance sums (above 64 MB a fixed seeded sample "
+                         "of its pixels, (n, 3), with their flat indices x * H + y in DIR/frame_pixels.npy)")
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
     ap.add_argument("--scene", default=None, help="cornell | specular | cubes (overrides --config)")
     ap.add_argument("--res", type=int, default=None)
@@ -121,6 +134,8 @@ def parse():
                     help="PMC summaries per workload (tools/pmc_summary.py): HBM bytes per trace launch, "
                          "VALU issue / lane utilisation; traffic is null for a workload without an entry")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     for k, v in CONFIGS[a.config].items():
         if getattr(a, k) is None:
             setattr(a, k, v)
@@ -237,6 +252,25 @@ def l2_vs_cpu(gpu_sums, ids, cpu_sums, args):
             "max_pixel_l2": float(pix_l2.max()), "identical_pixels": round(float(same.mean()), 6),
             "tolerance": 1e-3, "pass": bool(pix_l2.max() < 1e-3),
             "reference": "oracle/prt_oracle.c (C port of PathTracer.trace), same seed, random 8x8 tiles"}
+
+
+# the line's fields that only a --full run measures (null in a plain run)
+FULL_FIELDS = ("roofline", "work_per_sample", "work_totals", "cpu_baseline", "cpu_numpy", "l2_vs_cpu")
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """Write the (W, H, 3) float32 frame of the last timed step to out_dir/frame.npy.  A frame above
+    DUMP_MAX_BYTES is cut to a fixed sample of its pixels (seed 0: the same pixels in every run), whose
+    flat indices x * H + y go to out_dir/frame_pixels.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.nbytes > DUMP_MAX_BYTES:
+        n_px = frame.shape[0] * frame.shape[1]
+        idx = np.sort(np.random.default_rng(0).choice(n_px, DUMP_MAX_BYTES // 2 // 12, replace=False))
+        frame = frame.reshape(n_px, 3)[idx]
+        np.save(os.path.join(out_dir, "frame_pixels.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame.npy"), frame)
 
 
 def free_port():
@@ -426,22 +460,26 @@ def main():
                 # (SURVEY.md §8(e)), one launch, inside the step
                 shard.scatter_frames(ds, stream, nf)
 
+    last_nf = [1]
+
     def run(n):
         # equal groups of <= F frames (equal launches: the per-launch roofline averages like sizes)
         groups = -(-n // F)
         for g in range(groups):
             nf = n // groups + (1 if g < n % groups else 0)
             steps(nf, N.PRT_FLAG_TIME if timing[0] else 0)
+            last_nf[0] = nf
 
     timing = [False]
-    # counted traversal work of one frame (deterministic: same RNG as the timed steps)
-    steps(1, N.PRT_FLAG_STATS)
-    torch.cuda.synchronize(dev)
-    st = np.append(ds.last_stats().astype(np.float64), float(ds.diag_stats()[14]))
-    cnt = torch.tensor(st, dtype=torch.float64, device=coll_dev)
-    if coll:
-        dist.all_reduce(cnt)
-    nodes, tris, ext, shadow, nonfinite = cnt.tolist()
+    if args.full:
+        # counted traversal work of one frame (deterministic: same RNG as the timed steps)
+        steps(1, N.PRT_FLAG_STATS)
+        torch.cuda.synchronize(dev)
+        st = np.append(ds.last_stats().astype(np.float64), float(ds.diag_stats()[14]))
+        cnt = torch.tensor(st, dtype=torch.float64, device=coll_dev)
+        if coll:
+            dist.all_reduce(cnt)
+        nodes, tris, ext, shadow, nonfinite = cnt.tolist()
 
     # warmup: the W steps, and at least one full group of F frames (its buffers are then allocated)
     run(max(args.warmup, F))
@@ -474,14 +512,18 @@ def main():
     # the last timed group (samples 0 .. spp - 1, rendered inside a multi-frame launch, gathered and, at
     # N > 1 or with --force-collective, scattered from the gather buffer) before any other leg renders
     timed_frame = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0:
         last = shards[(n_step[0] - 1) % n_streams]
-        timed_frame = last.assemble(ds, streams[(n_step[0] - 1) % n_streams])
+        if args.full and not args.no_cpu_baseline:
+            timed_frame = last.assemble(ds, streams[(n_step[0] - 1) % n_streams])
+        if args.dump_outputs:
+            # the last timed step: the last frame of the last timed group
+            dump_outputs(args.dump_outputs, last.assemble(ds, streams[(n_step[0] - 1) % n_streams], last_nf[0] - 1))
 
     # what batching buys: the same step with ONE frame per persistent launch, timed the
     # same way (barrier + synchronize on both sides, max over ranks), after the main leg
     single = None
-    if F > 1 and args.single_frame_steps > 0:
+    if args.full and F > 1 and args.single_frame_steps > 0:
         steps(1, 0)                                  # warm the single-frame buffers and launch shape
         if coll:
             dist.barrier()
@@ -507,10 +549,11 @@ def main():
                           "batches frames_per_launch frames per launch, each still rendered, reduced, gathered "
                           "and scattered whole"}
 
-    if rank == 0:
-        samples_per_step = W * H * args.spp
-        ms_per_step = elapsed * 1e3 / args.steps
-        value = samples_per_step / (elapsed / args.steps) / 1e6
+    samples_per_step = W * H * args.spp
+
+    def full_report():
+        """Rank 0 with --full: the roofline of the counted work, the CPU legs and the comparison of the
+        timed frame with them (the fields a plain run leaves null)."""
         # roofline of the dominant kernel (trace_kernel) on rank 0 (per launch)
         share = 1.0 / world
         n_px_rank = len(my_tiles) * T * T
@@ -608,6 +651,23 @@ def main():
                                 "256 MB MALL (traffic / hbm_measured_frac: PMC FETCH_SIZE x 2 + WRITE_SIZE per "
                                 "launch, profiles/pmc.json, only for this kernel_sha and variant). Latency-bound "
                                 "on the dependent node-fetch chain: neither HBM nor VALU issue saturates.")
+        return {
+            "roofline": roofline,
+            "work_per_sample": {"nodes": round(nodes / samples_per_step, 2), "tris": round(tris / samples_per_step, 2),
+                                "ext_queries": round(ext / samples_per_step, 3),
+                                "shadow_queries": round(shadow / samples_per_step, 3),
+                                "nonfinite_samples": int(nonfinite)},
+            # the same counts summed over the ranks (independent of the tile split for the queries)
+            "work_totals": {"nodes": int(nodes), "tris": int(tris), "ext_queries": int(ext),
+                            "shadow_queries": int(shadow)},
+            "cpu_baseline": cpu,
+            "cpu_numpy": cpu_np,
+            "l2_vs_cpu": l2,
+        }
+
+    if rank == 0:
+        ms_per_step = elapsed * 1e3 / args.steps
+        value = samples_per_step / (elapsed / args.steps) / 1e6
         line = {
             "metric": "Msamples/sec Cornell box 512²×64spp at 1/2/4/8 GPU; per-pixel L2 vs CPU",
             "value": round(value, 3), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
@@ -623,19 +683,10 @@ def main():
             # each rank's own wall time per step over the timed steps (value uses the max)
             "rank_ms_per_step": {"min": round(min(rank_ms), 4), "max": round(max(rank_ms), 4),
                                  "per_rank": [round(x, 4) for x in rank_ms]},
+            "full": bool(args.full),
             "single_frame": single,
-            "roofline": roofline,
-            "work_per_sample": {"nodes": round(nodes / samples_per_step, 2), "tris": round(tris / samples_per_step, 2),
-                                "ext_queries": round(ext / samples_per_step, 3),
-                                "shadow_queries": round(shadow / samples_per_step, 3),
-                                "nonfinite_samples": int(nonfinite)},
-            # the same counts summed over the ranks (independent of the tile split for the queries)
-            "work_totals": {"nodes": int(nodes), "tris": int(tris), "ext_queries": int(ext),
-                            "shadow_queries": int(shadow)},
-            "cpu_baseline": cpu,
-            "cpu_numpy": cpu_np,
-            "l2_vs_cpu": l2,
         }
+        line.update(full_report() if args.full else dict.fromkeys(FULL_FIELDS))
         print(json.dumps(line), flush=True)
     if coll:
         dist.destroy_process_group()

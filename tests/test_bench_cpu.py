@@ -21,6 +21,31 @@ def test_defaults_are_the_baseline_workload(monkeypatch):
     assert bench.CONFIGS[5]["res"] == 4096 and bench.CONFIGS[5]["spp"] == 256
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    a = _args(monkeypatch, ["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = _args(monkeypatch, ["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    rng = np.random.default_rng(3)
+    frame = rng.random((40, 24, 3)).astype(np.float32)
+    bench.dump_outputs(str(tmp_path / "a" / "b"), frame)          # the directory is created
+    got = np.load(tmp_path / "a" / "b" / "frame.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    assert sorted(p.name for p in (tmp_path / "a" / "b").iterdir()) == ["frame.npy"]
+    # above the size limit: the same sample of pixels in every run, within the limit
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2400)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), frame)
+    s1, p1 = np.load(tmp_path / "s1" / "frame.npy"), np.load(tmp_path / "s1" / "frame_pixels.npy")
+    assert np.array_equal(p1, np.load(tmp_path / "s2" / "frame_pixels.npy"))
+    assert s1.dtype == np.float32 and p1.dtype == np.float64 and s1.shape == (100, 3) and p1.shape == (100,)
+    assert s1.nbytes + p1.nbytes <= 2400 and len(np.unique(p1)) == 100
+    assert np.array_equal(s1, frame.reshape(-1, 3)[p1.astype(np.int64)])
+
+
 def test_l2_vs_cpu_arithmetic():
     args = types.SimpleNamespace(res=16, spp=4)
     ids = np.array([0, 3], np.int32)

@@ -17,7 +17,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-ARGS = ["--res", "128", "--spp", "8", "--depth", "8", "--tile", "16", "--steps", "2", "--warmup", "1",
+ARGS = ["--full", "--res", "128", "--spp", "8", "--depth", "8", "--tile", "16", "--steps", "2", "--warmup", "1",
         "--numpy-seconds", "0", "--cpu-seconds", "2"]
 
 
@@ -72,7 +72,7 @@ def test_bench_three_ranks_ragged_multi_frame_over_gloo():
     CPU oracle and the counters sum to the one-process counts."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
-    args = ["--res", "128", "--spp", "4", "--depth", "6", "--tile", "16", "--steps", "4", "--warmup", "1",
+    args = ["--full", "--res", "128", "--spp", "4", "--depth", "6", "--tile", "16", "--steps", "4", "--warmup", "1",
             "--numpy-seconds", "0", "--cpu-seconds", "1", "--frames-per-launch", "4", "--single-frame-steps", "0"]
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "3", "--backend", "gloo"] + args, cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
@@ -94,7 +94,7 @@ def test_bench_force_collective_nccl_world_one():
     equal the CPU oracle bit for bit."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
-    args = ["--res", "128", "--spp", "8", "--depth", "8", "--tile", "16", "--steps", "8", "--warmup", "1",
+    args = ["--full", "--res", "128", "--spp", "8", "--depth", "8", "--tile", "16", "--steps", "8", "--warmup", "1",
             "--numpy-seconds", "0", "--cpu-seconds", "2", "--frames-per-launch", "4", "--single-frame-steps", "2"]
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--backend", "nccl", "--force-collective"] + args,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)

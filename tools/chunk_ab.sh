@@ -10,7 +10,7 @@ for c in $CONFIGS; do
   STEPS="--steps 10"; [ $c = 5 ] && STEPS="--steps 4 --warmup 1"
   for r in $(seq 1 $ROUNDS); do
     for g in $GIBS; do
-      PRT_CHUNK_BYTES=$((g << 30)) timeout -k 10 300 python3 bench.py --config $c $STEPS --no-cpu-baseline \
+      PRT_CHUNK_BYTES=$((g << 30)) timeout -k 10 300 python3 bench.py --full --config $c $STEPS --no-cpu-baseline \
         --numpy-seconds 0 > $O/c${c}_g${g}_r${r}.json 2> $O/c${c}_g${g}_r${r}.err
       python3 -c "import json; d=json.load(open('$O/c${c}_g${g}_r${r}.json')); rf=d['roofline']; print('c$c ${g}GiB r$r', round(d['value'],1), round(d['ms_per_step'],3), rf['kernel_avg_ms'], rf['launches_per_step'])"
     done

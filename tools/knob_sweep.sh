@@ -8,7 +8,7 @@ mkdir -p $O
 for r in $(seq $R); do
   for kv in DEFAULT $SETS; do
     E=""; [ $kv != DEFAULT ] && E=${kv//,/ }
-    env $E timeout -k 10 200 python3 bench.py --config $C --no-cpu-baseline --numpy-seconds 0 > $O/c${C}_${kv}_r$r.json 2> $O/err.log
+    env $E timeout -k 10 200 python3 bench.py --full --config $C --no-cpu-baseline --numpy-seconds 0 > $O/c${C}_${kv}_r$r.json 2> $O/err.log
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('$kv r$r', d['value'], d['roofline']['kernel_avg_ms'], d.get('work_per_sample'))" $O/c${C}_${kv}_r$r.json
   done
 done

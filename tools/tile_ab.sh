@@ -9,7 +9,7 @@ mkdir -p $O
 for c in $CONFIGS; do
   for r in $(seq 1 $ROUNDS); do
     for t in $TILES; do
-      timeout -k 10 300 python3 bench.py --config $c --tile $t --no-cpu-baseline --numpy-seconds 0 \
+      timeout -k 10 300 python3 bench.py --full --config $c --tile $t --no-cpu-baseline --numpy-seconds 0 \
         > $O/c${c}_t${t}_r${r}.json 2> $O/c${c}_t${t}_r${r}.err
       python3 -c "import json,sys; d=json.load(open('$O/c${c}_t${t}_r${r}.json')); print('c$c t$t r$r', round(d['value'],1), round(d['ms_per_step'],3), (d.get('l2_vs_cpu') or {}).get('pass'))"
     done

@@ -42,7 +42,9 @@ extern "C" {
  * ABI 4 (this build, round 6): variant ids 9..14 removed again (none became the default; DESIGN.md
  * §9), ids above 8 are rejected with PRT_ERR_ARG as in ABI 2; prt_scatter_frames rejects a
  * group_pitch too short for n_frames frames at src_frame_pitch; prt_camera_rays zero-fills the rows
- * of slots outside the frame; prt_selftest_guards added. */
+ * of slots outside the frame; prt_selftest_guards added.  Added later under the same number (purely
+ * additive, no existing entry point changed): the denoiser's four entry points at the end of this
+ * header. */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -311,6 +313,43 @@ int prt_diag_stats(void* scene, uint64_t* stats16);
  * [16] most BVH node visits of one query, [23] queries with > 1000 node visits, [24 + 8k ..]
  * the first 16 of them: o.xyz, d.xyz, t_max (f32 bits), query kind << 32 | node visits */
 int prt_diag_words(void* scene, uint64_t* out, int n);
+
+/* ------------------------------------------------------------ denoise ----
+ * Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on albedo-demodulated radiance,
+ * guided by first-hit features (the reference has no denoiser).  The entry points
+ * below live in units of their own: they take no scene handle and report failures through
+ * prt_denoise_last_error, not prt_last_error.
+ *   color   W x H x 3 f32   mean radiance, [x][y]
+ *   feat    W x H x 8 f32   per pixel: albedo.rgb, shading normal.xyz, depth, hit fraction
+ *                           (pyrenderer_amd.denoise.features composes them from prt_camera_rays
+ *                           and prt_hit_all)
+ *   iterations 0..8         pass i uses the 5 x 5 B3-spline stencil at step 2^i
+ *   params4 4 f32           sigma_c (colour), sigma_z (depth), eps_a (albedo floor of the
+ *                           demodulation), eps_z (depth floor); all > 0 and finite
+ *   out     W x H x 3 f32   filtered radiance
+ * A pixel with hit fraction 0, and a pixel whose colour, demodulated colour or any of its eight
+ * features is not finite, is returned bit for bit and is never a tap of another pixel; a depth
+ * gradient that reaches such a neighbour's depth counts as 0.  Every other output pixel is finite
+ * for finite features of magnitude below 2^60.  Every operation is an IEEE f32 add,
+ * mul, div, sqrt, min, max or abs in a fixed order: the result is reproducible bit for bit
+ * (tests/atrous_ref.py restates it in NumPy).
+ * prt_denoise takes host pointers and is synchronous.  Bad arguments (NULL, W or H < 1 or > 32768,
+ * iterations outside 0..8, a parameter that is not positive and finite) return PRT_ERR_ARG before
+ * any device is touched. */
+int prt_denoise(int device, const float* color, const float* feat, int W, int H, int iterations,
+                const float* params4, float* out);
+/* The same filter on device pointers, enqueued on `stream` (a hipStream_t of `device`; NULL = the
+ * null stream) with no host synchronisation: for a progressive preview loop or the root of the
+ * torch.distributed path, whose frames stay on the device.  d_work: scratch of at least
+ * prt_denoise_work_bytes(W, H) bytes, 16-byte aligned, work_bytes its size; it may be reused by the
+ * next call on the same stream.  d_out must not alias d_color. */
+int prt_denoise_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                       const float* params4, float* d_out, void* d_work, int64_t work_bytes, void* stream);
+/* scratch bytes prt_denoise_device needs for a W x H frame (56 per pixel, rounded up to 256); 0 for
+ * a shape the filter rejects */
+int64_t prt_denoise_work_bytes(int W, int H);
+/* message of the last failed prt_denoise / prt_denoise_device call on the calling thread */
+const char* prt_denoise_last_error(void);
 
 #ifdef __cplusplus
 }

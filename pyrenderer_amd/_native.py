@@ -83,6 +83,10 @@ EXPORTS = {
     "prt_last_stats": (_i, [_vp, _vp]),
     "prt_diag_stats": (_i, [_vp, _vp]),
     "prt_diag_words": (_i, [_vp, _vp, _i]),
+    "prt_denoise": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "prt_denoise_device": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    "prt_denoise_work_bytes": (_i64, [_i, _i]),
+    "prt_denoise_last_error": (ctypes.c_char_p, []),
 }
 
 
@@ -114,6 +118,13 @@ def lib():
 def check(rc):
     if rc != PRT_OK:
         raise PrtError(rc, lib().prt_last_error().decode(errors="replace"))
+    return rc
+
+
+def check_denoise(rc):
+    """check() for the denoiser's entry points, which keep their own error text."""
+    if rc != PRT_OK:
+        raise PrtError(rc, lib().prt_denoise_last_error().decode(errors="replace"))
     return rc
 
 

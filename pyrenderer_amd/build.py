@@ -24,6 +24,12 @@ TRACE_INST = "prt_trace_inst.hip"
 # part), 32 (deeper LDS-resident BVHs, PRT_SPILL_LDS=32)
 TRACE_SETS = [(s, t) for s in (4, 10, 16, 32) for t in (0, 1)]
 HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_device.h"]
+# the denoiser: units of their own, compiled with the same FLAGS and linked into
+# libprt.so.  They include none of HEADERS and nothing above includes theirs, so they cannot change
+# the trace kernels' code: they are dependencies of the build (_stale) but NOT part of kernel_sha(),
+# which keys the counter profiles to the trace-kernel build.
+AUX_SOURCES = ["prt_denoise.hip", "prt_denoise_capi.cpp"]
+AUX_HEADERS = ["prt_denoise.h"]
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 ARCH = os.environ.get("PRT_OFFLOAD_ARCH", "gfx950")
 
@@ -40,7 +46,7 @@ def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS + [TRACE_INST]] + [os.path.join(ROOT, "include", "prt.h"), __file__]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS + [TRACE_INST] + AUX_SOURCES + AUX_HEADERS] + [os.path.join(ROOT, "include", "prt.h"), __file__]
     return any(os.path.getmtime(p) > t for p in deps if os.path.exists(p))
 
 
@@ -78,7 +84,7 @@ def build(force=False, verbose=False, out=None, defs=()):
         # A/B builds only: extra compiler flags (e.g. "-mllvm --amdgpu-use-amdgpu-trackers")
         extra += os.environ.get("PRT_AB_FLAGS", "").split()
     units = [(os.path.join(CSRC, f), os.path.join(obj_dir, os.path.splitext(f)[0] + ".o"), UNIT_FLAGS.get(f, []))
-             for f in SOURCES]
+             for f in SOURCES + AUX_SOURCES]
     units += [(os.path.join(CSRC, TRACE_INST), os.path.join(obj_dir, f"prt_trace_{st}_{tt}.o"),
                [f"-DPRT_STACK={st}", f"-DPRT_STATS={tt}"]) for st, tt in TRACE_SETS]
     cmds = [[hipcc] + FLAGS + extra + d + ["-c", src, "-o", obj] for src, obj, d in units]

@@ -90,8 +90,12 @@ def build_world(scene, devices=(0,)):
 
 
 def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None,
-           nee="reference"):
+           nee="reference", denoise=False):
     """Mean linear radiance (W, H, 3) float32, [x][y], y up.
+
+    denoise: False (default) returns the Monte-Carlo mean as it is.  True filters it with the
+    a-trous denoiser (pyrenderer_amd.denoise, default parameters) guided by one-sample first-hit
+    features of the same camera, seed and resolution, on the first of `devices`.
 
     nee: 'reference' (sample_direct_lighting, what the reference's trace runs) or 'mis'
     (the reference's unused MIS estimator sample_direct_lighting2, as an optional variant).
@@ -102,7 +106,14 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     W, H = resolution if resolution is not None else camera.resolution
     world = world or build_world(scene, devices)
     tracer = PathTracer(world, depth, int(W), int(H))
-    return tracer.render(camera.convert_to_taichi_camera().packed(), spp, seed, devices, tile, nee)
+    cam = camera.convert_to_taichi_camera().packed()
+    mean = tracer.render(cam, spp, seed, devices, tile, nee)
+    if not denoise:
+        return mean
+    from .. import denoise as D
+    dev = tuple(devices)[0]
+    feat = D.features_packed(world.device_scene(dev), cam, int(W), int(H), samples=1, seed=seed, tile=tile)
+    return D.denoise(mean, feat, device=dev)
 
 
 def render_sums(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None,
@@ -160,6 +171,15 @@ class Accumulator:
         if self.samples == 0:
             return np.zeros((self.W, self.H, 3), np.float32)
         return self.sums() / np.float32(self.samples)
+
+    def denoised(self, **params):
+        """The running mean filtered by the a-trous denoiser (pyrenderer_amd.denoise.denoise; `params`
+        are its keyword parameters), guided by one-sample first-hit features of the accumulator's own
+        camera, seed and resolution: what render(..., denoise=True) returns for the same samples."""
+        from .. import denoise as D
+        feat = D.features_packed(self.world.device_scene(self.device), self.cam, self.W, self.H, samples=1,
+                                 seed=self.seed, tile=self.tile)
+        return D.denoise(self.mean(), feat, device=self.device, **params)
 
     def state(self):
         return dict(slots=self.slots, samples=np.int64(self.samples), seed=np.int64(self.seed),

@@ -1,0 +1,145 @@
+// prt_denoise_capi.cpp — the extern "C" surface of the a-trous denoiser (include/prt.h, "denoise").
+//
+// A unit of its own next to prt_capi.cpp: it keeps its own thread-local error text
+// (prt_denoise_last_error) and shares no state with the scene code.  Arguments are checked
+// before any HIP call, so a rejected call never touches a device.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../include/prt.h"
+#include "prt_denoise.h"
+
+namespace {
+
+thread_local std::string g_dn_err;
+
+int fail(int code, const std::string& msg) {
+    g_dn_err = msg;
+    return code;
+}
+
+#define DN_HIP_TRY(expr)                                                                                       \
+    do {                                                                                                       \
+        hipError_t e_ = (expr);                                                                                \
+        if (e_ != hipSuccess) return fail(PRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
+    } while (0)
+
+// Makes `dev` current for its lifetime; `err` is hipSetDevice's result, which the caller checks
+// before it enqueues anything (an invalid ordinal must not run on whatever device was current).
+struct DeviceGuard {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        err = hipSetDevice(dev);
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+// device ordinal against the visible devices: PRT_ERR_HIP without a device, PRT_ERR_ARG out of range
+int check_device(const char* fn, int device) {
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
+        (void)hipGetLastError();
+        return fail(PRT_ERR_HIP, std::string(fn) + ": no HIP device");
+    }
+    if (device >= n_dev) return fail(PRT_ERR_ARG, std::string(fn) + ": no such device");
+    return PRT_OK;
+}
+
+struct DevMem {
+    void* p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { if (p) (void)hipFree(p); }
+};
+
+bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
+
+// shape and parameter checks shared by both entry points; fills `p`
+int check_args(const char* fn, int device, int W, int H, int iterations, const float* params4, prt_dn::Params* p) {
+    const std::string who(fn);
+    if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
+    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
+    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
+        return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
+    if (iterations < 0 || iterations > prt_dn::kMaxIterations)
+        return fail(PRT_ERR_ARG, who + ": iterations must be in 0.." + std::to_string(prt_dn::kMaxIterations));
+    if (!params4) return fail(PRT_ERR_ARG, who + ": params4 is NULL");
+    p->sigma_c = params4[0];
+    p->sigma_z = params4[1];
+    p->eps_a = params4[2];
+    p->eps_z = params4[3];
+    if (!positive_finite(p->sigma_c) || !positive_finite(p->sigma_z))
+        return fail(PRT_ERR_ARG, who + ": sigma_c and sigma_z must be positive and finite");
+    if (!positive_finite(p->eps_a) || !positive_finite(p->eps_z))
+        return fail(PRT_ERR_ARG, who + ": eps_a and eps_z must be positive and finite");
+    // the last pass divides by (sigma_c * 2^-i)^2: it must not underflow to 0 or overflow
+    const float sc_last = p->sigma_c * (1.0f / (float)(1 << (iterations > 0 ? iterations - 1 : 0)));
+    if (!positive_finite(sc_last * sc_last) || !positive_finite(p->sigma_c * p->sigma_c))
+        return fail(PRT_ERR_ARG, who + ": sigma_c squared leaves the f32 range");
+    return PRT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* prt_denoise_last_error(void) { return g_dn_err.c_str(); }
+
+int64_t prt_denoise_work_bytes(int W, int H) {
+    if (W < 1 || H < 1 || W > prt_dn::kMaxSide || H > prt_dn::kMaxSide) return 0;
+    return (int64_t)prt_dn::work_bytes(W, H);
+}
+
+int prt_denoise_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                       const float* params4, float* d_out, void* d_work, int64_t work_bytes, void* stream) {
+    prt_dn::Params p;
+    if (!d_color || !d_feat || !d_out || !d_work)
+        return fail(PRT_ERR_ARG, "prt_denoise_device: NULL pointer");
+    int rc = check_args("prt_denoise_device", device, W, H, iterations, params4, &p);
+    if (rc != PRT_OK) return rc;
+    if (work_bytes < (int64_t)prt_dn::work_bytes(W, H))
+        return fail(PRT_ERR_ARG, "prt_denoise_device: d_work is smaller than prt_denoise_work_bytes(W, H)");
+    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0)
+        return fail(PRT_ERR_ARG, "prt_denoise_device: d_work must be 16-byte aligned");
+    if (d_out == d_color) return fail(PRT_ERR_ARG, "prt_denoise_device: d_out must not alias d_color");
+    rc = check_device("prt_denoise_device", device);
+    if (rc != PRT_OK) return rc;
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    DN_HIP_TRY(prt_dn::enqueue(d_color, d_feat, W, H, iterations, p, d_out, d_work, static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+int prt_denoise(int device, const float* color, const float* feat, int W, int H, int iterations,
+                const float* params4, float* out) {
+    prt_dn::Params p;
+    if (!color || !feat || !out) return fail(PRT_ERR_ARG, "prt_denoise: NULL pointer");
+    int rc = check_args("prt_denoise", device, W, H, iterations, params4, &p);
+    if (rc != PRT_OK) return rc;
+    rc = check_device("prt_denoise", device);
+    if (rc != PRT_OK) return rc;
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    const size_t n = (size_t)W * (size_t)H;
+    DevMem d_color, d_feat, d_out, d_work;
+    if (hipMalloc(&d_color.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&d_out.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_work.p, prt_dn::work_bytes(W, H)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PRT_ERR_OOM, "prt_denoise: device allocation failed");
+    }
+    DN_HIP_TRY(hipMemcpy(d_color.p, color, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
+    DN_HIP_TRY(prt_dn::enqueue(static_cast<const float*>(d_color.p), static_cast<const float*>(d_feat.p), W, H, iterations,
+                               p, static_cast<float*>(d_out.p), d_work.p, nullptr));
+    // the copy on the null stream follows the kernels and blocks until it is done
+    DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+}  // extern "C"

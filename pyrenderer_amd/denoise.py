@@ -1,0 +1,146 @@
+"""First-hit feature buffers and the edge-avoiding a-trous denoiser.
+
+`features()` composes per-pixel albedo / shading normal / depth / hit fraction on the host from
+the render's own primary rays (prt_camera_rays) traced with prt_hit_all; `denoise()` runs the
+HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise).  There is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _native as N
+from .device_scene import interleaved_tiles
+
+# defaults chosen by tools/denoise_sweep.py (profiles/denoise_sweep.txt): the lowest
+# geometric-mean RMSE ratio among the parameter sets that improve every frame of the sweep
+ITERATIONS = 5
+SIGMA_C = 0.25
+SIGMA_Z = 1.0
+EPS_A = 1e-2
+EPS_Z = 1e-2
+
+FEATURE_CHANNELS = 8
+# rays per prt_camera_rays / prt_hit_all call of features(): 2^20 rays are 32 MiB of rays and
+# 64 MiB of hit records on the host, whatever the frame size
+CHUNK_RAYS = 1 << 20
+T_MIN, T_MAX = 1e-5, 99999.9   # the primary ray's range in PathTracer.trace (core/tracing.py:126-127)
+
+
+def _slots_in_frame(W, H, tile, ids):
+    """(n_tiles * tile * tile,) bool: slots (tile-major, then row ly, then column lx) whose pixel
+    lies inside the W x H frame."""
+    tx = (W + tile - 1) // tile
+    ids = np.asarray(ids, np.int64)
+    x = (ids % tx)[:, None, None] * tile + np.arange(tile)[None, None, :]
+    y = (ids // tx)[:, None, None] * tile + np.arange(tile)[None, :, None]
+    return ((x < W) & (y < H)).reshape(-1)
+
+
+def _unpack_into(slots, frame, tile, tile_ids):
+    """device_scene.unpack_tiles for any channel count, into an existing [x][y] frame: (n_tiles * tile *
+    tile, C) slot rows (tile-major, then row ly, then column lx) -> frame (W, H, C)."""
+    W, H, C = frame.shape
+    tx = (W + tile - 1) // tile
+    s = slots.reshape(len(tile_ids), tile, tile, C)
+    for k, tid in enumerate(tile_ids):
+        x0 = (int(tid) % tx) * tile
+        y0 = (int(tid) // tx) * tile
+        w = min(tile, W - x0)
+        h = min(tile, H - y0)
+        frame[x0:x0 + w, y0:y0 + h] = s[k, :h, :w].transpose(1, 0, 2)
+
+
+def features_packed(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_rays=CHUNK_RAYS):
+    """features() for a DeviceScene and a packed camera record."""
+    W, H, tile, samples = int(W), int(H), int(tile), int(samples)
+    if samples < 1:
+        raise ValueError("samples must be >= 1")
+    ids = interleaved_tiles(W, H, tile)
+    per_tile = tile * tile
+    group = max(1, chunk_rays // per_tile)
+    n_f32 = np.float32(samples)
+    feat = np.zeros((W, H, FEATURE_CHANNELS), np.float32)   # the only frame-sized array held
+    for g0 in range(0, ids.shape[0], group):
+        gid = ids[g0:g0 + group]
+        n_slots = gid.shape[0] * per_tile
+        inside = _slots_in_frame(W, H, tile, gid)
+        n_in = int(inside.sum())
+        acc = np.zeros((n_slots, 8), np.float32)   # albedo sum, normal sum, t sum, hits
+        step = max(1, chunk_rays // n_slots)
+        for s0 in range(0, samples, step):
+            k = min(step, samples - s0)
+            o, d, _ = ds.camera_rays(cam_packed, W, H, tile, tile, gid, s0, k, seed)
+            # slots of partial edge tiles outside the frame carry all-zero rays: they never reach the traversal
+            keep = np.tile(inside, k)
+            hits = ds.hit_all(o[keep], d[keep], T_MIN, T_MAX).reshape(k, n_in, 16)
+            for j in range(k):   # float32 sums in sample order
+                r = hits[j]
+                hit = r[:, 0] > 0
+                acc[inside, 0:3] += r[:, 9:12]
+                acc[inside, 3:6] += r[:, 5:8]
+                acc[inside, 6] += np.where(hit, r[:, 1], np.float32(0.0))
+                acc[inside, 7] += hit.astype(np.float32)
+        hits_sum = acc[:, 7].copy()
+        acc[:, 0:6] /= n_f32
+        acc[:, 6] /= np.maximum(hits_sum, np.float32(1.0))
+        acc[:, 7] /= n_f32
+        _unpack_into(acc, feat, tile, gid)
+    return feat
+
+
+def features(scene, camera, *, resolution=None, samples=1, seed=0, device=0, tile=64, world=None):
+    """First-hit feature buffers, (W, H, 8) float32 indexed [x][y]: the per-pixel mean over samples
+    0 .. samples-1 of the render's own primary rays (same seed, resolution and tile as the render).
+
+    [0:3] albedo (bsdf.evaluate() at the first hit; misses add 0), [3:6] shading normal (flipped
+    toward the ray; misses add 0), [6] depth (sum of t over the hitting samples / max(hits, 1)),
+    [7] hit fraction (hits / samples).
+    """
+    from .core.tracing import build_world
+    W, H = resolution if resolution is not None else camera.resolution
+    world = world or build_world(scene, (device,))
+    return features_packed(world.device_scene(device), camera.convert_to_taichi_camera().packed(), W, H,
+                           samples=samples, seed=seed, tile=tile)
+
+
+def _params(sigma_c, sigma_z, eps_a, eps_z):
+    return np.array([sigma_c, sigma_z, eps_a, eps_z], np.float32)
+
+
+def denoise(mean, feat, *, iterations=ITERATIONS, sigma_c=SIGMA_C, sigma_z=SIGMA_Z, eps_a=EPS_A, eps_z=EPS_Z,
+            device=0):
+    """Filter the mean radiance `mean` (W, H, 3) guided by `feat` (W, H, 8) from features():
+    `iterations` a-trous passes (0..8) on the GPU `device`; returns (W, H, 3) float32.
+
+    sigma_c: colour edge-stopping width (in demodulated radiance, halved every pass); sigma_z: depth
+    edge-stopping width relative to the local depth gradient; eps_a: albedo floor of the
+    demodulation; eps_z: depth floor.  Pixels without a first hit, and pixels whose colour or
+    features are not finite, are returned unchanged."""
+    mean = np.ascontiguousarray(mean, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if mean.ndim != 3 or mean.shape[2] != 3:
+        raise ValueError(f"mean must be (W, H, 3), not {mean.shape}")
+    if feat.shape != mean.shape[:2] + (FEATURE_CHANNELS,):
+        raise ValueError(f"feat must be {mean.shape[:2] + (FEATURE_CHANNELS,)}, not {feat.shape}")
+    W, H = mean.shape[:2]
+    out = np.zeros_like(mean)
+    par = _params(sigma_c, sigma_z, eps_a, eps_z)
+    N.check_denoise(N.lib().prt_denoise(int(device), N.ptr(mean), N.ptr(feat), W, H, int(iterations), N.ptr(par),
+                                        N.ptr(out)))
+    return out
+
+
+def work_bytes(W, H):
+    """Scratch bytes denoise_device needs for a W x H frame."""
+    return int(N.lib().prt_denoise_work_bytes(int(W), int(H)))
+
+
+def denoise_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_bytes, *, iterations=ITERATIONS,
+                   sigma_c=SIGMA_C, sigma_z=SIGMA_Z, eps_a=EPS_A, eps_z=EPS_Z, device=0, stream_ptr=None):
+    """prt_denoise_device: the same filter on device pointers (e.g. torch tensors' data_ptr()),
+    enqueued on `stream_ptr` (a hipStream_t; None = the null stream) without a host synchronisation."""
+    par = _params(sigma_c, sigma_z, eps_a, eps_z)
+    vp = ctypes.c_void_p
+    N.check_denoise(N.lib().prt_denoise_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
+                                               int(iterations), N.ptr(par), vp(d_out_ptr), vp(d_work_ptr),
+                                               int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))

@@ -6,6 +6,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd [scene.json] --samples 64 --depth 16 --out out.png
     python -m pyrenderer_amd --samples 256 --interval 32 --state acc.npz      # resumable
     python -m pyrenderer_amd --samples 64 --devices 0 1 2 3                   # tiles over 4 GPUs
+    python -m pyrenderer_amd --samples 8 --denoise --aov aov/                 # filtered image + feature buffers
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
 no CPU fallback.
@@ -16,7 +17,7 @@ import time
 
 import numpy as np
 
-from .core.tracing import Accumulator, as_image, render_sums
+from .core.tracing import Accumulator, as_image, build_world, render_sums
 from .io_utils.read_tungsten import read_file
 from .tone_map import finish, reinhard_extended, save_hdr, to_uint8, write_png
 
@@ -44,11 +45,33 @@ def parse(argv=None):
                     help="also save the reference's HDR pair (main_taichi.py:120-123) into DIR: hdr.npy = the "
                          "radiance sums (W, H, 3) [x][y], spp.npy = the per-pixel sample counts (W, H); "
                          "the reference's tone_map.py reads exactly these")
+    ap.add_argument("--denoise", action="store_true",
+                    help="filter the image with the edge-avoiding a-trous denoiser (pyrenderer_amd.denoise), guided "
+                         "by one-sample first-hit albedo / normal / depth; --hdr still saves the raw sums")
+    ap.add_argument("--denoise-iterations", type=int, default=None, metavar="N",
+                    help="a-trous passes, 0..8 (default 5; pass i uses step 2^i); implies --denoise")
+    ap.add_argument("--aov", metavar="DIR",
+                    help="save the first-hit feature buffers into DIR: albedo.png, normal.png (0.5 n + 0.5) and "
+                         "depth.npy ((W, H) float32 [x][y], 0 where no ray hits)")
     args = ap.parse_args(argv)
+    if args.denoise_iterations is not None:
+        if not 0 <= args.denoise_iterations <= 8:
+            ap.error(f"--denoise-iterations must be in 0..8, not {args.denoise_iterations}")
+        args.denoise = True
     if args.hdr and args.hdr.lower().endswith(".npy"):
         # rounds <= 4 took a .npy FILE here; a directory named out.npy would silently replace it
         ap.error(f"--hdr takes a directory (hdr.npy and spp.npy are written into it), not a .npy file: {args.hdr}")
     return args
+
+
+def write_aov(directory, feat):
+    """--aov: albedo.png, normal.png (0.5 n + 0.5) and depth.npy of a features() array."""
+    os.makedirs(directory, exist_ok=True)
+    paths = [os.path.join(directory, n) for n in ("albedo.png", "normal.png", "depth.npy")]
+    write_png(paths[0], to_uint8(as_image(feat[..., 0:3])))
+    write_png(paths[1], to_uint8(as_image(np.float32(0.5) * feat[..., 3:6] + np.float32(0.5))))
+    np.save(paths[2], np.ascontiguousarray(feat[..., 6]))
+    return paths
 
 
 def _write(args, sums, samples, mean):
@@ -93,12 +116,24 @@ def main(argv=None):
                 acc.save(state)
         sums, samples, mean = acc.sums(), acc.samples, acc.mean()
         W, H = acc.W, acc.H
+        world, seed, tile = acc.world, acc.seed, acc.tile
     else:
+        world, seed, tile = build_world(scene, tuple(args.devices)), args.seed, 64
         sums = render_sums(scene, camera, spp=args.samples, depth=args.depth, seed=args.seed, resolution=(W, H),
-                           devices=tuple(args.devices), nee=args.nee)
+                           devices=tuple(args.devices), nee=args.nee, world=world)
         samples = max(args.samples, 0)
         # render()'s mean, bit for bit: pixels / samples (main_taichi.py:61-64)
         mean = sums / np.float32(samples) if samples else np.zeros_like(sums)
+    if args.denoise or args.aov:
+        from . import denoise as D
+        dev = args.devices[0]
+        feat = D.features_packed(world.device_scene(dev), camera.convert_to_taichi_camera().packed(), W, H,
+                                 samples=1, seed=seed, tile=tile)
+        if args.aov:
+            write_aov(args.aov, feat)
+        if args.denoise:
+            it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
+            mean = D.denoise(mean, feat, iterations=it, device=dev)
     dt = time.perf_counter() - t0
     _write(args, sums, samples, mean)
     print(f"{W}x{H} x {args.samples} spp, depth {args.depth}: {dt:.2f} s "

@@ -1,0 +1,93 @@
+"""Parameter sweep of the a-trous denoiser: sigma_c, sigma_z, eps_a, eps_z.
+
+For the Cornell box and scene_specular.json at 128^2 and 512^2 with 4, 8 and 64 spp, the score of
+a parameter set is the RMSE of the denoised frame against a 4096-spp render of the same frame
+(other seed), divided by the noisy frame's RMSE; sets are ranked by the geometric mean of that
+ratio over the twelve frames.  The yardstick is the 4096-spp render, never the filter's output.
+
+    python tools/denoise_sweep.py --out profiles/denoise_sweep.txt
+"""
+import argparse
+import itertools
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+MEDIA = os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box")
+SIGMA_C = (0.125, 0.25, 0.5, 1.0, 2.0, 4.0, 8.0, 16.0)
+SIGMA_Z = (0.5, 1.0, 2.0, 4.0)
+EPS_A = (1e-3, 1e-2, 5e-2)
+EPS_Z = (1e-4, 1e-3, 1e-2)
+
+
+def rmse(a, b):
+    return float(np.sqrt(np.mean((a.astype(np.float64) - b) ** 2)))
+
+
+def load(which):
+    from pyrenderer_amd.io_utils.read_tungsten import process_primitives, read_file
+    if which == "cornell":
+        return read_file(os.path.join(MEDIA, "scene.json"))
+    return process_primitives(json.load(open(os.path.join(MEDIA, "scene_specular.json"))))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", default="-", help="table file ('-' = stdout)")
+    ap.add_argument("--sizes", type=int, nargs="+", default=[128, 512])
+    ap.add_argument("--spp", type=int, nargs="+", default=[4, 8, 64])
+    ap.add_argument("--ref-spp", type=int, default=4096)
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--iterations", type=int, default=5)
+    a = ap.parse_args()
+    from pyrenderer_amd.core.tracing import build_world, render
+    from pyrenderer_amd.denoise import denoise, features
+
+    frames = []
+    for which in ("cornell", "specular"):
+        scene, cam = load(which)
+        world = build_world(scene, (0,))
+        for size in a.sizes:
+            res = (size, size)
+            ref = render(scene, cam, spp=a.ref_spp, depth=a.depth, seed=1, resolution=res, world=world)
+            feat = features(scene, cam, resolution=res, samples=1, seed=2, world=world)
+            for spp in a.spp:
+                noisy = render(scene, cam, spp=spp, depth=a.depth, seed=2, resolution=res, world=world)
+                frames.append((f"{which}-{size}-{spp}spp", noisy, feat, ref, rmse(noisy, ref)))
+            print(f"rendered {which} {size}", file=sys.stderr, flush=True)
+
+    rows = []
+    for sc, sz, ea, ez in itertools.product(SIGMA_C, SIGMA_Z, EPS_A, EPS_Z):
+        ratios = [rmse(denoise(n, f, iterations=a.iterations, sigma_c=sc, sigma_z=sz, eps_a=ea, eps_z=ez), r) / e
+                  for _, n, f, r, e in frames]
+        rows.append((float(np.exp(np.mean(np.log(ratios)))), sc, sz, ea, ez, ratios))
+    rows.sort(key=lambda t: t[0])
+
+    out = sys.stdout if a.out == "-" else open(a.out, "w")
+    names = [f[0] for f in frames]
+    print(f"# a-trous parameter sweep: iterations {a.iterations}, depth {a.depth}, reference {a.ref_spp} spp (seed 1), "
+          f"noisy frames seed 2", file=out)
+    print("# noisy RMSE: " + "  ".join(f"{n} {e:.5f}" for n, _, _, _, e in frames), file=out)
+    print("# columns: geometric-mean ratio, sigma_c, sigma_z, eps_a, eps_z, then RMSE(denoised) / RMSE(noisy) of "
+          + " ".join(names), file=out)
+    for g, sc, sz, ea, ez, ratios in rows:
+        print(f"{g:.4f} {sc:g} {sz:g} {ea:g} {ez:g}  " + " ".join(f"{r:.4f}" for r in ratios), file=out)
+    if out is not sys.stdout:
+        out.close()
+    g, sc, sz, ea, ez, _ = rows[0]
+    print(f"best: sigma_c {sc:g} sigma_z {sz:g} eps_a {ea:g} eps_z {ez:g} (geometric-mean ratio {g:.4f})")
+    # a default must not make any frame of the sweep worse than its input
+    safe = [r for r in rows if max(r[5]) < 1.0]
+    if safe:
+        g, sc, sz, ea, ez, ratios = safe[0]
+        print(f"best with every frame improved: sigma_c {sc:g} sigma_z {sz:g} eps_a {ea:g} eps_z {ez:g} "
+              f"(geometric-mean ratio {g:.4f}, worst frame {max(ratios):.4f})")
+
+
+if __name__ == "__main__":
+    main()

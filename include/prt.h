@@ -44,7 +44,7 @@ extern "C" {
  * group_pitch too short for n_frames frames at src_frame_pitch; prt_camera_rays zero-fills the rows
  * of slots outside the frame; prt_selftest_guards added.  Added later under the same number (purely
  * additive, no existing entry point changed): the denoiser's four entry points at the end of this
- * header. */
+ * header, then the three of its variance-guided mode (prt_denoise_var*). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -350,6 +350,35 @@ int prt_denoise_device(int device, const float* d_color, const float* d_feat, in
 int64_t prt_denoise_work_bytes(int W, int H);
 /* message of the last failed prt_denoise / prt_denoise_device call on the calling thread */
 const char* prt_denoise_last_error(void);
+
+/* Variance-guided mode of the same filter (the spatial half of SVGF, Schied et al. 2017; DESIGN.md
+ * §11).  Added under ABI 4 like the four entry points above: purely additive.  The colour
+ * edge-stopping width is not a parameter: a 7 x 7 estimate of the per-pixel variance of the
+ * demodulated luminance scales it, and the variance is carried through the passes, so the filter
+ * widens where the image is noisy and narrows where it has converged.  color, feat, iterations, out,
+ * the set-aside rule and the fixed operation order are those of prt_denoise
+ * (tests/atrous_var_ref.py restates this mode in NumPy).
+ *   params5 5 f32           sigma_l (luminance width in local standard deviations), sigma_z, eps_a,
+ *                           eps_z (as above), eps_l (luminance floor, in demodulated radiance); all
+ *                           > 0 and finite
+ *   out_var W x H f32       optional (may be NULL): the variance estimate of the demodulated
+ *                           luminance before any pass, 0 at pixels that are set aside — a noise map
+ * The variance is always finite (one that overflows becomes 0).  Every other output pixel is finite
+ * for features as above, demodulated radiance |color / max(albedo, eps_a)| <= 2^126 and albedo <= 1.
+ * prt_denoise_var takes host pointers and is synchronous; bad arguments return PRT_ERR_ARG before
+ * any device is touched, with the text in prt_denoise_last_error. */
+int prt_denoise_var(int device, const float* color, const float* feat, int W, int H, int iterations,
+                    const float* params5, float* out, float* out_var);
+/* prt_denoise_var on device pointers, enqueued on `stream` with no host synchronisation (see
+ * prt_denoise_device).  d_out_var may be NULL.  d_work: scratch of at least
+ * prt_denoise_var_work_bytes(W, H) bytes, 16-byte aligned.  d_out must not alias d_color; d_out_var
+ * must not alias d_out, d_color or d_feat. */
+int prt_denoise_var_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                           const float* params5, float* d_out, float* d_out_var, void* d_work, int64_t work_bytes,
+                           void* stream);
+/* scratch bytes prt_denoise_var_device needs for a W x H frame (60 per pixel, rounded up to 256); 0
+ * for a shape the filter rejects */
+int64_t prt_denoise_var_work_bytes(int W, int H);
 
 #ifdef __cplusplus
 }

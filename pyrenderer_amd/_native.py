@@ -87,6 +87,9 @@ EXPORTS = {
     "prt_denoise_device": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i64, _vp]),
     "prt_denoise_work_bytes": (_i64, [_i, _i]),
     "prt_denoise_last_error": (ctypes.c_char_p, []),
+    "prt_denoise_var": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "prt_denoise_var_device": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "prt_denoise_var_work_bytes": (_i64, [_i, _i]),
 }
 
 

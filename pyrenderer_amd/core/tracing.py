@@ -95,7 +95,9 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
 
     denoise: False (default) returns the Monte-Carlo mean as it is.  True filters it with the
     a-trous denoiser (pyrenderer_amd.denoise, default parameters) guided by one-sample first-hit
-    features of the same camera, seed and resolution, on the first of `devices`.
+    features of the same camera, seed and resolution, on the first of `devices`.  "variance" selects
+    its variance-guided mode (pyrenderer_amd.denoise.denoise_variance, default parameters), which
+    takes the colour edge-stopping width from the image's own noise.  Anything else is a ValueError.
 
     nee: 'reference' (sample_direct_lighting, what the reference's trace runs) or 'mis'
     (the reference's unused MIS estimator sample_direct_lighting2, as an optional variant).
@@ -103,6 +105,8 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     resolution: (W, H) override of camera.resolution (the aspect ratio still
     comes from camera.resolution, as convert_to_taichi_camera() does).
     """
+    if not (isinstance(denoise, (bool, np.bool_)) or (isinstance(denoise, str) and denoise == "variance")):
+        raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
     W, H = resolution if resolution is not None else camera.resolution
     world = world or build_world(scene, devices)
     tracer = PathTracer(world, depth, int(W), int(H))
@@ -113,6 +117,8 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     from .. import denoise as D
     dev = tuple(devices)[0]
     feat = D.features_packed(world.device_scene(dev), cam, int(W), int(H), samples=1, seed=seed, tile=tile)
+    if denoise == "variance":
+        return D.denoise_variance(mean, feat, device=dev)
     return D.denoise(mean, feat, device=dev)
 
 
@@ -172,13 +178,18 @@ class Accumulator:
             return np.zeros((self.W, self.H, 3), np.float32)
         return self.sums() / np.float32(self.samples)
 
-    def denoised(self, **params):
+    def denoised(self, mode="fixed", **params):
         """The running mean filtered by the a-trous denoiser (pyrenderer_amd.denoise.denoise; `params`
         are its keyword parameters), guided by one-sample first-hit features of the accumulator's own
-        camera, seed and resolution: what render(..., denoise=True) returns for the same samples."""
+        camera, seed and resolution: what render(..., denoise=True) returns for the same samples.
+        mode="variance" routes to denoise_variance instead: render(..., denoise="variance")."""
         from .. import denoise as D
+        if mode not in D.MODES:
+            raise ValueError(f"mode must be one of {D.MODES}, not {mode!r}")
         feat = D.features_packed(self.world.device_scene(self.device), self.cam, self.W, self.H, samples=1,
                                  seed=self.seed, tile=self.tile)
+        if mode == "variance":
+            return D.denoise_variance(self.mean(), feat, device=self.device, **params)
         return D.denoise(self.mean(), feat, device=self.device, **params)
 
     def state(self):

@@ -85,6 +85,29 @@ int check_args(const char* fn, int device, int W, int H, int iterations, const f
     return PRT_OK;
 }
 
+// check_args for the variance-guided entry points (params5 = sigma_l, sigma_z, eps_a, eps_z, eps_l)
+int check_var_args(const char* fn, int device, int W, int H, int iterations, const float* params5,
+                   prt_dn::VarParams* p) {
+    const std::string who(fn);
+    if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
+    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
+    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
+        return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
+    if (iterations < 0 || iterations > prt_dn::kMaxIterations)
+        return fail(PRT_ERR_ARG, who + ": iterations must be in 0.." + std::to_string(prt_dn::kMaxIterations));
+    if (!params5) return fail(PRT_ERR_ARG, who + ": params5 is NULL");
+    p->sigma_l = params5[0];
+    p->sigma_z = params5[1];
+    p->eps_a = params5[2];
+    p->eps_z = params5[3];
+    p->eps_l = params5[4];
+    if (!positive_finite(p->sigma_l) || !positive_finite(p->sigma_z))
+        return fail(PRT_ERR_ARG, who + ": sigma_l and sigma_z must be positive and finite");
+    if (!positive_finite(p->eps_a) || !positive_finite(p->eps_z) || !positive_finite(p->eps_l))
+        return fail(PRT_ERR_ARG, who + ": eps_a, eps_z and eps_l must be positive and finite");
+    return PRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -139,6 +162,64 @@ int prt_denoise(int device, const float* color, const float* feat, int W, int H,
                                p, static_cast<float*>(d_out.p), d_work.p, nullptr));
     // the copy on the null stream follows the kernels and blocks until it is done
     DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
+
+int64_t prt_denoise_var_work_bytes(int W, int H) {
+    if (W < 1 || H < 1 || W > prt_dn::kMaxSide || H > prt_dn::kMaxSide) return 0;
+    return (int64_t)prt_dn::var_work_bytes(W, H);
+}
+
+int prt_denoise_var_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                           const float* params5, float* d_out, float* d_out_var, void* d_work, int64_t work_bytes,
+                           void* stream) {
+    prt_dn::VarParams p;
+    if (!d_color || !d_feat || !d_out || !d_work)
+        return fail(PRT_ERR_ARG, "prt_denoise_var_device: NULL pointer");
+    int rc = check_var_args("prt_denoise_var_device", device, W, H, iterations, params5, &p);
+    if (rc != PRT_OK) return rc;
+    if (work_bytes < (int64_t)prt_dn::var_work_bytes(W, H))
+        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_work is smaller than prt_denoise_var_work_bytes(W, H)");
+    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0)
+        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_work must be 16-byte aligned");
+    if (d_out == d_color) return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_out must not alias d_color");
+    if (d_out_var && (d_out_var == d_out || d_out_var == d_color || d_out_var == d_feat))
+        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_out_var must not alias d_out, d_color or d_feat");
+    rc = check_device("prt_denoise_var_device", device);
+    if (rc != PRT_OK) return rc;
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, W, H, iterations, p, d_out, d_out_var, d_work,
+                                   static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+int prt_denoise_var(int device, const float* color, const float* feat, int W, int H, int iterations,
+                    const float* params5, float* out, float* out_var) {
+    prt_dn::VarParams p;
+    if (!color || !feat || !out) return fail(PRT_ERR_ARG, "prt_denoise_var: NULL pointer");
+    int rc = check_var_args("prt_denoise_var", device, W, H, iterations, params5, &p);
+    if (rc != PRT_OK) return rc;
+    rc = check_device("prt_denoise_var", device);
+    if (rc != PRT_OK) return rc;
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    const size_t n = (size_t)W * (size_t)H;
+    DevMem d_color, d_feat, d_out, d_var, d_work;
+    if (hipMalloc(&d_color.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
+        hipMalloc(&d_out.p, n * 3 * sizeof(float)) != hipSuccess || (out_var && hipMalloc(&d_var.p, n * sizeof(float)) != hipSuccess) ||
+        hipMalloc(&d_work.p, prt_dn::var_work_bytes(W, H)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(PRT_ERR_OOM, "prt_denoise_var: device allocation failed");
+    }
+    DN_HIP_TRY(hipMemcpy(d_color.p, color, n * 3 * sizeof(float), hipMemcpyHostToDevice));
+    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
+    DN_HIP_TRY(prt_dn::enqueue_var(static_cast<const float*>(d_color.p), static_cast<const float*>(d_feat.p), W, H,
+                                   iterations, p, static_cast<float*>(d_out.p), static_cast<float*>(d_var.p), d_work.p,
+                                   nullptr));
+    // the copies on the null stream follow the kernels and block until they are done
+    DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (out_var) DN_HIP_TRY(hipMemcpy(out_var, d_var.p, n * sizeof(float), hipMemcpyDeviceToHost));
     return PRT_OK;
 }
 

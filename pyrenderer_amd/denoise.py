@@ -144,3 +144,58 @@ def denoise_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_
     N.check_denoise(N.lib().prt_denoise_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
                                                int(iterations), N.ptr(par), vp(d_out_ptr), vp(d_work_ptr),
                                                int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))
+
+
+# ---- variance-guided mode (prt_denoise_var) ----
+# defaults chosen by tools/denoise_sweep.py --mode variance (profiles/denoise_var_sweep.txt) by the
+# fixed filter's rule; eps_a and eps_z are the fixed filter's
+VAR_SIGMA_L = 1.0
+VAR_SIGMA_Z = 2.0
+VAR_EPS_L = 1e-2
+MODES = ("fixed", "variance")
+
+
+def _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l):
+    return np.array([sigma_l, sigma_z, eps_a, eps_z, eps_l], np.float32)
+
+
+def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A,
+                     eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False):
+    """denoise() with the colour edge-stopping width taken from the image's own noise: a 7 x 7
+    estimate of the variance of the demodulated luminance scales it per pixel, and the variance is
+    carried through the passes.  Returns (W, H, 3) float32, or with return_variance=True the pair
+    (image, (W, H) float32 variance estimate before any pass).
+
+    sigma_l: luminance edge-stopping width in local standard deviations; eps_l: its floor, in
+    demodulated radiance; sigma_z, eps_a, eps_z: as in denoise()."""
+    mean = np.ascontiguousarray(mean, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if mean.ndim != 3 or mean.shape[2] != 3:
+        raise ValueError(f"mean must be (W, H, 3), not {mean.shape}")
+    if feat.shape != mean.shape[:2] + (FEATURE_CHANNELS,):
+        raise ValueError(f"feat must be {mean.shape[:2] + (FEATURE_CHANNELS,)}, not {feat.shape}")
+    W, H = mean.shape[:2]
+    out = np.zeros_like(mean)
+    var = np.zeros((W, H), np.float32) if return_variance else None
+    par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
+    N.check_denoise(N.lib().prt_denoise_var(int(device), N.ptr(mean), N.ptr(feat), W, H, int(iterations), N.ptr(par),
+                                            N.ptr(out), N.ptr(var)))
+    return (out, var) if return_variance else out
+
+
+def work_bytes_variance(W, H):
+    """Scratch bytes denoise_variance_device needs for a W x H frame."""
+    return int(N.lib().prt_denoise_var_work_bytes(int(W), int(H)))
+
+
+def denoise_variance_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_bytes, *, d_out_var_ptr=None,
+                            iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A, eps_z=EPS_Z,
+                            eps_l=VAR_EPS_L, device=0, stream_ptr=None):
+    """prt_denoise_var_device: denoise_variance on device pointers, enqueued on `stream_ptr` without a
+    host synchronisation; `d_out_var_ptr` (W x H floats, optional) receives the variance estimate."""
+    par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
+    vp = ctypes.c_void_p
+    N.check_denoise(N.lib().prt_denoise_var_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
+                                                   int(iterations), N.ptr(par), vp(d_out_ptr),
+                                                   vp(d_out_var_ptr) if d_out_var_ptr else None, vp(d_work_ptr),
+                                                   int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))

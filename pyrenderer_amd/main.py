@@ -7,6 +7,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd --samples 256 --interval 32 --state acc.npz      # resumable
     python -m pyrenderer_amd --samples 64 --devices 0 1 2 3                   # tiles over 4 GPUs
     python -m pyrenderer_amd --samples 8 --denoise --aov aov/                 # filtered image + feature buffers
+    python -m pyrenderer_amd --samples 8 --denoise --denoise-mode variance    # width from the image's own noise
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
 no CPU fallback.
@@ -50,9 +51,13 @@ def parse(argv=None):
                          "by one-sample first-hit albedo / normal / depth; --hdr still saves the raw sums")
     ap.add_argument("--denoise-iterations", type=int, default=None, metavar="N",
                     help="a-trous passes, 0..8 (default 5; pass i uses step 2^i); implies --denoise")
+    ap.add_argument("--denoise-mode", choices=("fixed", "variance"), default="fixed",
+                    help="with --denoise: 'fixed' (default) stops at colour edges with one fixed width; 'variance' "
+                         "takes the width from a per-pixel estimate of the image's own noise")
     ap.add_argument("--aov", metavar="DIR",
                     help="save the first-hit feature buffers into DIR: albedo.png, normal.png (0.5 n + 0.5) and "
-                         "depth.npy ((W, H) float32 [x][y], 0 where no ray hits)")
+                         "depth.npy ((W, H) float32 [x][y], 0 where no ray hits); with --denoise --denoise-mode "
+                         "variance also variance.npy, the (W, H) float32 variance estimate of the demodulated luminance")
     args = ap.parse_args(argv)
     if args.denoise_iterations is not None:
         if not 0 <= args.denoise_iterations <= 8:
@@ -133,7 +138,12 @@ def main(argv=None):
             write_aov(args.aov, feat)
         if args.denoise:
             it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
-            mean = D.denoise(mean, feat, iterations=it, device=dev)
+            if args.denoise_mode == "variance":
+                mean, var = D.denoise_variance(mean, feat, iterations=it, device=dev, return_variance=True)
+                if args.aov:
+                    np.save(os.path.join(args.aov, "variance.npy"), var)
+            else:
+                mean = D.denoise(mean, feat, iterations=it, device=dev)
     dt = time.perf_counter() - t0
     _write(args, sums, samples, mean)
     print(f"{W}x{H} x {args.samples} spp, depth {args.depth}: {dt:.2f} s "

@@ -6,6 +6,11 @@ a parameter set is the RMSE of the denoised frame against a 4096-spp render of t
 ratio over the twelve frames.  The yardstick is the 4096-spp render, never the filter's output.
 
     python tools/denoise_sweep.py --out profiles/denoise_sweep.txt
+
+--mode variance sweeps the variance-guided mode instead (sigma_l, eps_l, sigma_z; eps_a and eps_z stay
+at the fixed filter's defaults) on the same frames with the same score:
+
+    python tools/denoise_sweep.py --mode variance --out profiles/denoise_var_sweep.txt
 """
 import argparse
 import itertools
@@ -23,6 +28,9 @@ SIGMA_C = (0.125, 0.25, 0.5, 1.0, 2.0, 4.0, 8.0, 16.0)
 SIGMA_Z = (0.5, 1.0, 2.0, 4.0)
 EPS_A = (1e-3, 1e-2, 5e-2)
 EPS_Z = (1e-4, 1e-3, 1e-2)
+VAR_SIGMA_L = (1.0, 2.0, 4.0, 8.0)
+VAR_EPS_L = (1e-4, 1e-3, 1e-2)
+VAR_SIGMA_Z = (0.5, 1.0, 2.0)
 
 
 def rmse(a, b):
@@ -36,6 +44,38 @@ def load(which):
     return process_primitives(json.load(open(os.path.join(MEDIA, "scene_specular.json"))))
 
 
+def sweep_variance(a, frames):
+    """The --mode variance leg: table and choice for sigma_l, eps_l, sigma_z."""
+    from pyrenderer_amd.denoise import EPS_A, EPS_Z, denoise_variance
+    rows = []
+    for sl, el, sz in itertools.product(VAR_SIGMA_L, VAR_EPS_L, VAR_SIGMA_Z):
+        ratios = [rmse(denoise_variance(n, f, iterations=a.iterations, sigma_l=sl, sigma_z=sz, eps_l=el), r) / e
+                  for _, n, f, r, e in frames]
+        rows.append((float(np.exp(np.mean(np.log(ratios)))), sl, el, sz, ratios))
+    rows.sort(key=lambda t: t[0])
+    out = sys.stdout if a.out == "-" else open(a.out, "w")
+    print(f"# variance-guided a-trous parameter sweep: iterations {a.iterations}, depth {a.depth}, reference {a.ref_spp} spp "
+          f"(seed 1), noisy frames seed 2, eps_a {EPS_A:g}, eps_z {EPS_Z:g}", file=out)
+    print("# noisy RMSE: " + "  ".join(f"{n} {e:.5f}" for n, _, _, _, e in frames), file=out)
+    print("# columns: geometric-mean ratio, sigma_l, eps_l, sigma_z, then RMSE(denoised) / RMSE(noisy) of "
+          + " ".join(f[0] for f in frames), file=out)
+    for g, sl, el, sz, ratios in rows:
+        print(f"{g:.4f} {sl:g} {el:g} {sz:g}  " + " ".join(f"{r:.4f}" for r in ratios), file=out)
+    if out is not sys.stdout:
+        out.close()
+    g, sl, el, sz, _ = rows[0]
+    print(f"best: sigma_l {sl:g} eps_l {el:g} sigma_z {sz:g} (geometric-mean ratio {g:.4f})")
+    safe = [r for r in rows if max(r[4]) < 1.0]
+    if safe:
+        g, sl, el, sz, ratios = safe[0]
+        print(f"best with every frame improved: sigma_l {sl:g} eps_l {el:g} sigma_z {sz:g} "
+              f"(geometric-mean ratio {g:.4f}, worst frame {max(ratios):.4f})")
+    else:
+        g, sl, el, sz, ratios = min(rows, key=lambda t: max(t[4]))
+        print(f"no set improves every frame; best worst frame: sigma_l {sl:g} eps_l {el:g} sigma_z {sz:g} "
+              f"(geometric-mean ratio {g:.4f}, worst frame {max(ratios):.4f})")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default="-", help="table file ('-' = stdout)")
@@ -44,6 +84,9 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=4096)
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--iterations", type=int, default=5)
+    ap.add_argument("--mode", choices=("fixed", "variance"), default="fixed",
+                    help="fixed: sigma_c, sigma_z, eps_a, eps_z of denoise(); variance: sigma_l, eps_l, sigma_z of "
+                         "denoise_variance()")
     a = ap.parse_args()
     from pyrenderer_amd.core.tracing import build_world, render
     from pyrenderer_amd.denoise import denoise, features
@@ -60,6 +103,9 @@ def main():
                 noisy = render(scene, cam, spp=spp, depth=a.depth, seed=2, resolution=res, world=world)
                 frames.append((f"{which}-{size}-{spp}spp", noisy, feat, ref, rmse(noisy, ref)))
             print(f"rendered {which} {size}", file=sys.stderr, flush=True)
+
+    if a.mode == "variance":
+        return sweep_variance(a, frames)
 
     rows = []
     for sc, sz, ea, ez in itertools.product(SIGMA_C, SIGMA_Z, EPS_A, EPS_Z):

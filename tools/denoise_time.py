@@ -3,6 +3,7 @@ repeated enqueues on one stream.  Inputs: an 8-spp Cornell rend
 features at 512^2, tiled to the larger sizes.  One JSON line per size.
 
     python tools/denoise_time.py --sizes 512 4096
+    python tools/denoise_time.py --mode variance --sizes 512 4096   # the variance-guided mode (prt_denoise_var_device)
 """
 import argparse
 import json
@@ -23,6 +24,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--mode", choices=("fixed", "variance"), default="fixed")
     a = ap.parse_args()
     import torch
     from pyrenderer_amd import denoise as D
@@ -42,11 +44,16 @@ def main():
         f = np.ascontiguousarray(np.tile(feat, (k, k, 1))[:size, :size])
         d_c, d_f = torch.from_numpy(c).to(dev), torch.from_numpy(f).to(dev)
         d_out = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
-        need = D.work_bytes(size, size)
+        variance = a.mode == "variance"
+        need = D.work_bytes_variance(size, size) if variance else D.work_bytes(size, size)
         d_work = torch.empty(need, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
 
         def run():
+            if variance:
+                D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), size, size, d_out.data_ptr(), d_work.data_ptr(),
+                                          need, iterations=a.iterations, stream_ptr=stream.cuda_stream)
+                return
             D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), size, size, d_out.data_ptr(), d_work.data_ptr(), need,
                              iterations=a.iterations, stream_ptr=stream.cuda_stream)
 
@@ -69,8 +76,15 @@ def main():
         # reads I, the class plane, colour and albedo and writes the colour
         per_pass = n * (16 + 16 + 8 + 16)
         fixed = n * ((12 + 32 + 16 + 16 + 8) + (16 + 16 + 12 + 32 + 12))
+        what = "denoise_time"
+        if variance:
+            # per pass one read of (I, var), (N, class), the gradient and the depth and one write of (I, var); the
+            # estimate reads (I, Z), (N, class) and the gradient and writes (I, var) and the depth
+            per_pass = n * (16 + 16 + 8 + 4 + 16)
+            fixed += n * ((16 + 16 + 8) + (16 + 4))
+            what = "denoise_var_time"
         total = per_pass * a.iterations + fixed
-        print(json.dumps(dict(what="denoise_time", size=size, iterations=a.iterations, median_ms=round(med, 4),
+        print(json.dumps(dict(what=what, size=size, iterations=a.iterations, median_ms=round(med, 4),
                               min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), reps=a.reps,
                               bytes_per_pass=per_pass, bytes_total=total,
                               implied_gbs=round(total / (med * 1e-3) / 1e9, 1),

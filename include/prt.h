@@ -44,7 +44,8 @@ extern "C" {
  * group_pitch too short for n_frames frames at src_frame_pitch; prt_camera_rays zero-fills the rows
  * of slots outside the frame; prt_selftest_guards added.  Added later under the same number (purely
  * additive, no existing entry point changed): the denoiser's four entry points at the end of this
- * header, then the three of its variance-guided mode (prt_denoise_var*). */
+ * header, then the three of its variance-guided mode (prt_denoise_var*), then the four of the
+ * sample-moments variance (prt_moments_add*, prt_denoise_var_given*). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -379,6 +380,52 @@ int prt_denoise_var_device(int device, const float* d_color, const float* d_feat
 /* scratch bytes prt_denoise_var_device needs for a W x H frame (60 per pixel, rounded up to 256); 0
  * for a shape the filter rejects */
 int64_t prt_denoise_var_work_bytes(int W, int H);
+
+/* Variance from per-pixel sample moments.  Added under ABI 4, purely additive.  Random
+ * streams are keyed by (seed, pixel, sample), so spp samples rendered as K batches from zero sums
+ * (prt_render_tiles_accumulate, prt_render_frames_device) give K independent batch means per pixel;
+ * the sample variance of those means over K is the variance of the final mean.  It knows nothing of
+ * neighbouring pixels, so unlike the 7 x 7 estimate it does not take an edge for noise; its square
+ * root is a per-pixel standard-error map.
+ *
+ * prt_moments_add: a running Welford update over n_frames frames of per-pixel radiance SUMS.
+ *   sums      n_frames frames of W x H x 3 f32 [x][y]; frame f starts at + f * frame_pitch floats
+ *             (0 = packed, W * H * 3)
+ *   n_samples samples per frame (every frame and every call on one state must use the same count)
+ *   feat      W x H x 8 f32, as for prt_denoise; eps_a > 0 and finite
+ *   io_state  W x H x 4 f32 [x][y], updated in place: k (frames seen, exact below 2^24), mean of the
+ *             frames' luminances, M2, var_mean (the variance of that mean).  All zeroes = empty.
+ * Per pixel and frame, in frame order, every operation one IEEE f32 operation in this association
+ * (tests/moments_ref.py restates it in NumPy):
+ *   c = S / n_samples;  I_c = feat[7] > 0 ? c_c / fmax(A_c, eps_a) : c_c;
+ *   l = (0.2126 I_r + 0.7152 I_g) + 0.0722 I_b;  a frame whose l is not finite is skipped;
+ *   k' = k + 1;  d = l - mean;  mean' = mean + d / k';  M2' = M2 + d * (l - mean')
+ * and after the last frame var_mean = k >= 2 ? (M2 / (k - 1)) / k : 0, stored as 0 when not finite.
+ * Adding frames in one call or split over several gives the same bits.  Finiteness: with |l| <= B both
+ * factors of d * (l - mean') are at most 2B, the product at most 4 B^2, and M2 at most k B^2; the whole
+ * state stays finite while k B^2 <= 2^127, i.e. |l| <= 2^62 for up to 8 frames and |l| <= 2^51 for 2^24.
+ * Host pointers, synchronous.  Bad arguments (NULL, W or H outside 1..32768, n_frames < 1, a non-zero
+ * frame_pitch below W * H * 3, n_samples not finite or < 1, eps_a not positive and finite) return
+ * PRT_ERR_ARG before any device is touched, with the text in prt_denoise_last_error. */
+int prt_moments_add(int device, const float* sums, int n_frames, int64_t frame_pitch, float n_samples,
+                    const float* feat, float eps_a, int W, int H, float* io_state);
+/* prt_moments_add on device pointers, enqueued on `stream` with no host synchronisation.  d_io_state
+ * must be 16-byte aligned and must not overlap d_sums or d_feat. */
+int prt_moments_add_device(int device, const float* d_sums, int n_frames, int64_t frame_pitch, float n_samples,
+                           const float* d_feat, float eps_a, int W, int H, float* d_io_state, void* stream);
+/* prt_denoise_var with the variance plane in_var (W x H f32 [x][y], e.g. channel 3 of a moments state
+ * copied out) in place of the 7 x 7 estimate: at a pixel that is not set aside a value that is finite
+ * and >= 0 is used as it is (-0 included), anything else — NaN, inf, a negative value — counts as 0;
+ * a pixel that is set aside gets 0.  out_var (may be NULL) receives the variance actually used.
+ * Everything else, the finiteness statement included, is prt_denoise_var's. */
+int prt_denoise_var_given(int device, const float* color, const float* feat, const float* in_var, int W, int H,
+                          int iterations, const float* params5, float* out, float* out_var);
+/* prt_denoise_var_given on device pointers, enqueued on `stream` with no host synchronisation.  d_work:
+ * prt_denoise_var_work_bytes(W, H) bytes, 16-byte aligned (no more than prt_denoise_var_device needs).
+ * The aliasing rules of prt_denoise_var_device hold, and d_in_var must not alias d_out or d_out_var. */
+int prt_denoise_var_given_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
+                                 int W, int H, int iterations, const float* params5, float* d_out,
+                                 float* d_out_var, void* d_work, int64_t work_bytes, void* stream);
 
 #ifdef __cplusplus
 }

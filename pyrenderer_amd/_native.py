@@ -90,6 +90,10 @@ EXPORTS = {
     "prt_denoise_var": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "prt_denoise_var_device": (_i, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "prt_denoise_var_work_bytes": (_i64, [_i, _i]),
+    "prt_moments_add": (_i, [_i, _vp, _i, _i64, ctypes.c_float, _vp, ctypes.c_float, _i, _i, _vp]),
+    "prt_moments_add_device": (_i, [_i, _vp, _i, _i64, ctypes.c_float, _vp, ctypes.c_float, _i, _i, _vp, _vp]),
+    "prt_denoise_var_given": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "prt_denoise_var_given_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 

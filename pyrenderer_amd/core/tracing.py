@@ -89,8 +89,60 @@ def build_world(scene, devices=(0,)):
     return world.commit(devices)
 
 
+def _check_variance_batches(variance_batches, spp, denoise, devices):
+    """render()'s rules for variance_batches; returns K (0 = off)."""
+    if isinstance(variance_batches, (bool, np.bool_)) or not isinstance(variance_batches, (int, np.integer)):
+        raise ValueError(f"variance_batches must be an integer, not {variance_batches!r}")
+    K = int(variance_batches)
+    if K == 0:
+        return 0
+    if K < 2:
+        raise ValueError(f"variance_batches must be 0 or >= 2, not {K}")
+    if not (isinstance(denoise, str) and denoise == "variance"):
+        raise ValueError("variance_batches is a variance source of denoise='variance'")
+    if spp < K or spp % K:
+        raise ValueError(f"spp ({spp}) must be a positive multiple of variance_batches ({K})")
+    if len(tuple(devices)) != 1:
+        raise ValueError("variance_batches renders on one device (prt_render_multi has no first-sample argument)")
+    return K
+
+
+def _render_batch(ds, cam, W, H, tile, ids, first_sample, spp, depth, seed, flags):
+    """Slot sums of samples first_sample .. first_sample + spp - 1, rendered from zero sums."""
+    slots = np.zeros((ids.shape[0] * tile * tile, 3), np.float32)
+    return ds.render_tiles_accumulate(cam, W, H, tile, tile, ids, first_sample, spp, depth, slots, seed, flags)
+
+
+def render_batches(scene, camera, *, spp, depth, variance_batches, seed=0, resolution=None, device=0, tile=64,
+                   world=None, nee="reference"):
+    """spp samples as K = variance_batches batches of spp / K, with the per-pixel moments of the batch
+    means: (sums (W, H, 3), feat (W, H, 8), state (W, H, 4)).  Batch j holds samples j * spp / K ..., each
+    rendered from zero sums; `sums` adds the batch sums in batch order on the host, an association that
+    differs in the last bits from render_sums()'s sample-order sum.  `feat` are the one-sample features
+    render(denoise=...) uses and `state` is pyrenderer_amd.denoise.moments_add's over the K batches."""
+    from .. import denoise as D
+    K = _check_variance_batches(variance_batches, spp, "variance", (device,))
+    if K == 0:
+        raise ValueError("variance_batches must be >= 2")
+    W, H = (int(v) for v in (resolution if resolution is not None else camera.resolution))
+    world = world or build_world(scene, (device,))
+    ds = world.device_scene(device)
+    cam = camera.convert_to_taichi_camera().packed()
+    ids = interleaved_tiles(W, H, tile)
+    n, flags = spp // K, nee_flags(nee)
+    feat = D.features_packed(ds, cam, W, H, samples=1, seed=seed, tile=tile)
+    frames = np.zeros((K, W, H, 3), np.float32)
+    total = np.zeros((ids.shape[0] * tile * tile, 3), np.float32)
+    for j in range(K):
+        batch = _render_batch(ds, cam, W, H, tile, ids, j * n, n, depth, seed, flags)
+        total += batch
+        unpack_tiles(batch, W, H, tile, tile, ids, frame=frames[j])
+    state = D.moments_add(D.moments_state(W, H), frames, n, feat, device=device)
+    return unpack_tiles(total, W, H, tile, tile, ids), feat, state
+
+
 def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None,
-           nee="reference", denoise=False):
+           nee="reference", denoise=False, variance_batches=0):
     """Mean linear radiance (W, H, 3) float32, [x][y], y up.
 
     denoise: False (default) returns the Monte-Carlo mean as it is.  True filters it with the
@@ -98,6 +150,13 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     features of the same camera, seed and resolution, on the first of `devices`.  "variance" selects
     its variance-guided mode (pyrenderer_amd.denoise.denoise_variance, default parameters), which
     takes the colour edge-stopping width from the image's own noise.  Anything else is a ValueError.
+
+    variance_batches: 0 (default) is the path above exactly.  K >= 2, with denoise="variance", one device
+    and spp a multiple of K, renders the spp samples as K batches of spp / K (render_batches) and gives
+    the filter the variance of the mean measured from the K batch means per pixel
+    (pyrenderer_amd.denoise.moments_add) in place of its 7 x 7 spatial estimate.  The unfiltered mean is
+    then (sum of the batch sums, in batch order) / spp, which differs in the last bits from the
+    sample-order sum of variance_batches=0.  Any other combination is a ValueError.
 
     nee: 'reference' (sample_direct_lighting, what the reference's trace runs) or 'mis'
     (the reference's unused MIS estimator sample_direct_lighting2, as an optional variant).
@@ -107,6 +166,13 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     """
     if not (isinstance(denoise, (bool, np.bool_)) or (isinstance(denoise, str) and denoise == "variance")):
         raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
+    K = _check_variance_batches(variance_batches, spp, denoise, devices)
+    if K:
+        from .. import denoise as D
+        dev = tuple(devices)[0]
+        sums, feat, state = render_batches(scene, camera, spp=spp, depth=depth, variance_batches=K, seed=seed,
+                                           resolution=resolution, device=dev, tile=tile, world=world, nee=nee)
+        return D.denoise_variance(sums / np.float32(spp), feat, device=dev, variance=state[..., 3])
     W, H = resolution if resolution is not None else camera.resolution
     world = world or build_world(scene, devices)
     tracer = PathTracer(world, depth, int(W), int(H))
@@ -145,10 +211,18 @@ class Accumulator:
     count, seed, depth, resolution, tile, estimator flags, the packed camera and a
     fingerprint of the flattened scene — load() refuses a different camera or scene,
     whose samples would otherwise be averaged into the same image).
+
+    moments=True also keeps the per-pixel moments of the batch means (pyrenderer_amd.denoise.moments_add):
+    every add(spp) is one batch, rendered from zero sums, added onto the running sums on the host (so the
+    sums are the batch sums in batch order, which differs in the last bits from the sample-order sum
+    above) and folded into the moments state.  Every batch must have the first batch's spp.
+    denoised(mode="variance") then takes its variance from the state once it holds
+    pyrenderer_amd.denoise.MIN_MOMENT_BATCHES batches, noise_map() is the per-pixel standard error, and
+    save / load carry the state.  moments=False (default) leaves every bit and every saved field as above.
     """
 
     def __init__(self, scene, camera, *, depth, seed=0, resolution=None, device=0, tile=64, world=None,
-                 nee="reference"):
+                 nee="reference", moments=False):
         W, H = resolution if resolution is not None else camera.resolution
         self.W, self.H, self.depth, self.seed, self.tile = int(W), int(H), int(depth), int(seed), int(tile)
         self.device = device
@@ -158,11 +232,60 @@ class Accumulator:
         self.slots = np.zeros((self.ids.shape[0] * self.tile * self.tile, 3), np.float32)
         self.samples = 0
         self.flags = nee_flags(nee)
+        self.moments = bool(moments)
+        self.batch_spp = 0        # moments: the spp of every batch, 0 before the first
+        self.moments_state = None
+        self._feat = None
+        if self.moments:
+            from .. import denoise as D
+            self.moments_state = D.moments_state(self.W, self.H)
+
+    @property
+    def batches(self):
+        """moments=True: the batches added so far."""
+        return self.samples // self.batch_spp if self.batch_spp else 0
+
+    def features(self):
+        """One-sample first-hit features of the accumulator's camera, seed and resolution; with
+        moments=True composed once and kept."""
+        from .. import denoise as D
+        if self._feat is not None:
+            return self._feat
+        feat = D.features_packed(self.world.device_scene(self.device), self.cam, self.W, self.H, samples=1,
+                                 seed=self.seed, tile=self.tile)
+        if self.moments:
+            self._feat = feat
+        return feat
+
+    def _add_batch(self, spp):
+        from .. import denoise as D
+        if spp == 0:
+            return self
+        if self.batch_spp and spp != self.batch_spp:
+            raise ValueError(f"moments=True needs equal batches: add({spp}) after batches of {self.batch_spp} spp")
+        ds = self.world.device_scene(self.device)
+        batch = _render_batch(ds, self.cam, self.W, self.H, self.tile, self.ids, self.samples, spp, self.depth,
+                              self.seed, self.flags)
+        self.slots += batch
+        frame = unpack_tiles(batch, self.W, self.H, self.tile, self.tile, self.ids)
+        D.moments_add(self.moments_state, frame, spp, self.features(), device=self.device)
+        self.batch_spp = spp
+        self.samples += spp
+        return self
+
+    def noise_map(self):
+        """moments=True: the standard error of the demodulated luminance per pixel, (W, H) float32:
+        the square root of the state's variance of the mean (0 below two batches)."""
+        if not self.moments:
+            raise ValueError("noise_map() needs Accumulator(..., moments=True)")
+        return np.sqrt(self.moments_state[..., 3])
 
     def add(self, spp=1):
         """Render samples [samples, samples + spp) of every pixel onto the sums."""
         if spp < 0:
             raise ValueError("spp must be >= 0")
+        if self.moments:
+            return self._add_batch(int(spp))
         ds = self.world.device_scene(self.device)
         ds.render_tiles_accumulate(self.cam, self.W, self.H, self.tile, self.tile, self.ids, self.samples, spp,
                                    self.depth, self.slots, self.seed, self.flags)
@@ -182,21 +305,28 @@ class Accumulator:
         """The running mean filtered by the a-trous denoiser (pyrenderer_amd.denoise.denoise; `params`
         are its keyword parameters), guided by one-sample first-hit features of the accumulator's own
         camera, seed and resolution: what render(..., denoise=True) returns for the same samples.
-        mode="variance" routes to denoise_variance instead: render(..., denoise="variance")."""
+        mode="variance" routes to denoise_variance instead: render(..., denoise="variance").  With
+        moments=True and at least pyrenderer_amd.denoise.MIN_MOMENT_BATCHES batches it passes the moments
+        state's variance of the mean as `variance` (what render(..., variance_batches=K) does); with
+        fewer batches it leaves the filter its spatial estimate."""
         from .. import denoise as D
         if mode not in D.MODES:
             raise ValueError(f"mode must be one of {D.MODES}, not {mode!r}")
-        feat = D.features_packed(self.world.device_scene(self.device), self.cam, self.W, self.H, samples=1,
-                                 seed=self.seed, tile=self.tile)
+        feat = self.features()
         if mode == "variance":
+            if self.moments and self.batches >= D.MIN_MOMENT_BATCHES and "variance" not in params:
+                params = dict(params, variance=self.moments_state[..., 3])
             return D.denoise_variance(self.mean(), feat, device=self.device, **params)
         return D.denoise(self.mean(), feat, device=self.device, **params)
 
     def state(self):
-        return dict(slots=self.slots, samples=np.int64(self.samples), seed=np.int64(self.seed),
-                    depth=np.int64(self.depth), resolution=np.array([self.W, self.H], np.int64),
-                    tile=np.int64(self.tile), flags=np.int64(self.flags), camera=self.cam,
-                    scene_sha=np.array(scene_fingerprint(self.world.flat)))
+        d = dict(slots=self.slots, samples=np.int64(self.samples), seed=np.int64(self.seed),
+                 depth=np.int64(self.depth), resolution=np.array([self.W, self.H], np.int64),
+                 tile=np.int64(self.tile), flags=np.int64(self.flags), camera=self.cam,
+                 scene_sha=np.array(scene_fingerprint(self.world.flat)))
+        if self.moments:
+            d.update(moments=self.moments_state, batch_spp=np.int64(self.batch_spp))
+        return d
 
     @staticmethod
     def state_path(path):
@@ -213,15 +343,21 @@ class Accumulator:
         W, H = (int(v) for v in z["resolution"])
         mis = "flags" in z.files and int(z["flags"]) & nee_flags("mis")
         acc = cls(scene, camera, depth=int(z["depth"]), seed=int(z["seed"]), resolution=(W, H), device=device,
-                  tile=int(z["tile"]), world=world, nee="mis" if mis else "reference")
+                  tile=int(z["tile"]), world=world, nee="mis" if mis else "reference",
+                  moments="moments" in z.files)
         if z["slots"].shape != acc.slots.shape:
             raise ValueError("saved accumulation does not match the frame layout")
         if "camera" in z.files and not np.array_equal(z["camera"], acc.cam):
             raise ValueError("saved accumulation was rendered with a different camera")
         if "scene_sha" in z.files and str(z["scene_sha"]) != scene_fingerprint(acc.world.flat):
             raise ValueError("saved accumulation was rendered from a different scene")
+        if acc.moments and z["moments"].shape != acc.moments_state.shape:
+            raise ValueError("saved moments do not match the frame")
         acc.slots[...] = z["slots"]
         acc.samples = int(z["samples"])
+        if acc.moments:
+            acc.moments_state[...] = z["moments"]
+            acc.batch_spp = int(z["batch_spp"])
         return acc
 
 

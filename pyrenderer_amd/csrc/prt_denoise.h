@@ -49,4 +49,26 @@ size_t var_work_bytes(int W, int H);
 hipError_t enqueue_var(const float* d_color, const float* d_feat, int W, int H, int iterations, const VarParams& p,
                        float* d_out, float* d_out_var, void* d_work, hipStream_t stream);
 
+// ---- variance from per-pixel sample moments ----
+
+// enqueue_var with the variance plane d_in_var (W x H floats) in place of the 7 x 7 estimate: at a
+// usable pixel a value that is finite and >= 0 is taken as it is, anything else counts as 0.
+// d_out_var (may be null) receives the variance actually used.  Scratch: var_work_bytes(W, H).
+// d_in_var must not alias d_out or d_out_var.
+hipError_t enqueue_var_given(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
+                             hipStream_t stream);
+
+// Running Welford update of the demodulated luminance over n_frames frames of per-pixel radiance sums
+// (frame f at d_sums + f * frame_pitch floats, W x H x 3, each the sum of n_samples samples).
+// d_io_state: W x H x 4 floats (k, mean, M2, var_mean), 16-byte aligned; zeroes are the empty state.
+//
+// Finiteness: a frame whose luminance l is not finite is skipped.  With |l| <= B, |mean| <= B, so both
+// factors of d * (l - mean') are at most 2B and the product at most 4B^2; M2, a sum of k such
+// non-negative terms, is at most k * B^2 in exact arithmetic.  The whole state is finite while
+// k * B^2 <= 2^127: |l| <= 2^62 for up to 8 batches, |l| <= 2^51 for the 2^24 that k counts exactly.
+// Beyond it M2 becomes inf and stays inf; var_mean is then stored as 0.
+hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
+                           float eps_a, int W, int H, float* d_io_state, hipStream_t stream);
+
 }  // namespace prt_dn

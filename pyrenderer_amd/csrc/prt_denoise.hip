@@ -7,7 +7,8 @@
 //
 // Frames are [x][y] with y contiguous (pixel index x * H + y).  One pixel per lane, 64 lanes along
 // y: the 16-byte loads of a tap are contiguous over a wave.  Taps come straight from global memory, except in the variance estimate
-// of the variance-guided mode, which stages its 7 x 7 windows in LDS.
+// of the variance-guided mode, which stages its 7 x 7 windows in LDS.  The sample-moments kernels at the
+// end (moments_kernel, var_given_kernel) read and write each pixel once and take no taps.
 #include "prt_denoise.h"
 
 namespace prt_dn {
@@ -330,6 +331,65 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_atrous_kernel(const floa
     dst[p] = make_float4(s0 / sum_w, s1 / sum_w, s2 / sum_w, var);
 }
 
+// ---- variance from per-pixel sample moments (tests/moments_ref.py restates both) ----
+
+// given variance: stands where var_estimate_kernel stands.  Repacks (I.rgb, Z) into (I.rgb, v) and the
+// depth plane, with v the caller's variance at a usable pixel when it is finite and >= 0 (a -0 passes
+// as it is), else 0.
+__global__ __launch_bounds__(kBlockX* kBlockY) void var_given_kernel(const float4* __restrict__ iz,
+                                                                     const float4* __restrict__ nc,
+                                                                     const float* __restrict__ in_var, int W, int H,
+                                                                     float4* __restrict__ iv, float* __restrict__ zp,
+                                                                     float* __restrict__ out_var) {
+    int x, y;
+    if (!pixel_of_lane(W, H, x, y)) return;
+    const size_t p = (size_t)x * (size_t)H + (size_t)y;
+    const float4 ip = iz[p];
+    float var = 0.0f;
+    if (__float_as_uint(nc[p].w) == kHit) {
+        const float t = in_var[p];
+        if (finite_f(t) && t >= 0.0f) var = t;
+    }
+    iv[p] = make_float4(ip.x, ip.y, ip.z, var);
+    zp[p] = ip.w;
+    if (out_var) out_var[p] = var;
+}
+
+// running Welford update of the demodulated luminance of the batch means over n_frames frames of
+// radiance sums; state (k, mean, M2, var_mean) per pixel, one 16-byte load and store
+__global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* __restrict__ sums, int n_frames,
+                                                                   size_t frame_pitch, float n,
+                                                                   const float* __restrict__ feat, int W, int H,
+                                                                   float eps_a, float4* __restrict__ state) {
+    int x, y;
+    if (!pixel_of_lane(W, H, x, y)) return;
+    const size_t p = (size_t)x * (size_t)H + (size_t)y;
+    const float* f = feat + p * 8;
+    const bool hit = f[7] > 0.0f;
+    const float a0 = fmaxf(f[0], eps_a), a1 = fmaxf(f[1], eps_a), a2 = fmaxf(f[2], eps_a);
+    const float4 s = state[p];
+    float k = s.x, mean = s.y, m2 = s.z;
+    for (int fr = 0; fr < n_frames; ++fr) {
+        const float* S = sums + (size_t)fr * frame_pitch + p * 3;
+        float i0 = S[0] / n, i1 = S[1] / n, i2 = S[2] / n;
+        if (hit) {
+            i0 = i0 / a0;
+            i1 = i1 / a1;
+            i2 = i2 / a2;
+        }
+        const float l = lum(i0, i1, i2);
+        if (!finite_f(l)) continue;
+        k = k + 1.0f;
+        const float d = l - mean;
+        mean = mean + d / k;
+        m2 = m2 + d * (l - mean);
+    }
+    float vm = 0.0f;
+    if (k >= 2.0f) vm = (m2 / (k - 1.0f)) / k;
+    if (!finite_f(vm)) vm = 0.0f;
+    state[p] = make_float4(k, mean, m2, vm);
+}
+
 }  // namespace
 
 size_t work_bytes(int W, int H) {
@@ -394,6 +454,46 @@ hipError_t enqueue_var(const float* d_color, const float* d_feat, int W, int H, 
         cur ^= 1;
     }
     post_kernel<<<grid, block, 0, stream>>>(a[cur], nc, d_color, d_feat, W, H, p.eps_a, d_out);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_var_given(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
+                             hipStream_t stream) {
+    const size_t n = (size_t)W * (size_t)H;
+    float4* a[2] = {static_cast<float4*>(d_work), static_cast<float4*>(d_work) + n};
+    float4* nc = a[1] + n;
+    float2* grad = reinterpret_cast<float2*>(nc + n);
+    float* zp = reinterpret_cast<float*>(grad + n);
+    const dim3 block(kBlockY, kBlockX);
+    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+    (void)hipGetLastError();
+    // enqueue_var's planes and launches, with the caller's variance in place of the 7 x 7 estimate
+    pre_kernel<<<grid, block, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, a[1], nc, grad);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    var_given_kernel<<<grid, block, 0, stream>>>(a[1], nc, d_in_var, W, H, a[0], zp, d_out_var);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    int cur = 0;
+    for (int i = 0; i < iterations; ++i) {
+        var_atrous_kernel<<<grid, block, 0, stream>>>(a[cur], a[cur ^ 1], nc, grad, zp, W, H, 1 << i, p.sigma_l,
+                                                      p.sigma_z, p.eps_z, p.eps_l);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        cur ^= 1;
+    }
+    post_kernel<<<grid, block, 0, stream>>>(a[cur], nc, d_color, d_feat, W, H, p.eps_a, d_out);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
+                           float eps_a, int W, int H, float* d_io_state, hipStream_t stream) {
+    const dim3 block(kBlockY, kBlockX);
+    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+    (void)hipGetLastError();
+    moments_kernel<<<grid, block, 0, stream>>>(d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
+                                               reinterpret_cast<float4*>(d_io_state));
     return hipGetLastError();
 }
 

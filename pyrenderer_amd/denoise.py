@@ -160,14 +160,19 @@ def _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l):
 
 
 def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A,
-                     eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False):
+                     eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False, variance=None):
     """denoise() with the colour edge-stopping width taken from the image's own noise: a 7 x 7
     estimate of the variance of the demodulated luminance scales it per pixel, and the variance is
     carried through the passes.  Returns (W, H, 3) float32, or with return_variance=True the pair
     (image, (W, H) float32 variance estimate before any pass).
 
     sigma_l: luminance edge-stopping width in local standard deviations; eps_l: its floor, in
-    demodulated radiance; sigma_z, eps_a, eps_z: as in denoise()."""
+    demodulated radiance; sigma_z, eps_a, eps_z: as in denoise().
+
+    variance: None (default) estimates the variance from the image as described.  A (W, H) plane, e.g.
+    channel 3 of a moments state (moments_add), is used in its place (prt_denoise_var_given): at a pixel
+    that is filtered a finite value >= 0 is taken as it is, anything else counts as 0.  The variance
+    returned with return_variance=True is then the one actually used."""
     mean = np.ascontiguousarray(mean, np.float32)
     feat = np.ascontiguousarray(feat, np.float32)
     if mean.ndim != 3 or mean.shape[2] != 3:
@@ -178,6 +183,13 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
     out = np.zeros_like(mean)
     var = np.zeros((W, H), np.float32) if return_variance else None
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
+    if variance is not None:
+        given = np.ascontiguousarray(variance, np.float32)
+        if given.shape != (W, H):
+            raise ValueError(f"variance must be {(W, H)}, not {given.shape}")
+        N.check_denoise(N.lib().prt_denoise_var_given(int(device), N.ptr(mean), N.ptr(feat), N.ptr(given), W, H,
+                                                      int(iterations), N.ptr(par), N.ptr(out), N.ptr(var)))
+        return (out, var) if return_variance else out
     N.check_denoise(N.lib().prt_denoise_var(int(device), N.ptr(mean), N.ptr(feat), W, H, int(iterations), N.ptr(par),
                                             N.ptr(out), N.ptr(var)))
     return (out, var) if return_variance else out
@@ -190,12 +202,67 @@ def work_bytes_variance(W, H):
 
 def denoise_variance_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_bytes, *, d_out_var_ptr=None,
                             iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A, eps_z=EPS_Z,
-                            eps_l=VAR_EPS_L, device=0, stream_ptr=None):
+                            eps_l=VAR_EPS_L, device=0, stream_ptr=None, d_in_var_ptr=None):
     """prt_denoise_var_device: denoise_variance on device pointers, enqueued on `stream_ptr` without a
-    host synchronisation; `d_out_var_ptr` (W x H floats, optional) receives the variance estimate."""
+    host synchronisation; `d_out_var_ptr` (W x H floats, optional) receives the variance estimate.
+    `d_in_var_ptr` (W x H floats, optional) is denoise_variance's `variance` (prt_denoise_var_given_device,
+    same scratch); it must not alias the output or `d_out_var_ptr`."""
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
     vp = ctypes.c_void_p
+    if d_in_var_ptr:
+        N.check_denoise(N.lib().prt_denoise_var_given_device(
+            int(device), vp(d_color_ptr), vp(d_feat_ptr), vp(d_in_var_ptr), int(W), int(H), int(iterations), N.ptr(par),
+            vp(d_out_ptr), vp(d_out_var_ptr) if d_out_var_ptr else None, vp(d_work_ptr), int(n_work_bytes),
+            vp(stream_ptr) if stream_ptr else None))
+        return
     N.check_denoise(N.lib().prt_denoise_var_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
                                                    int(iterations), N.ptr(par), vp(d_out_ptr),
                                                    vp(d_out_var_ptr) if d_out_var_ptr else None, vp(d_work_ptr),
                                                    int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))
+
+
+# ---- variance from per-pixel sample moments (prt_moments_add, prt_denoise_var_given; DESIGN.md §11) ----
+MOMENT_CHANNELS = 4          # k, mean, M2, var_mean
+# batches a moments state must hold before Accumulator.denoised(mode="variance") trusts its variance
+# (SVGF's history threshold); below it the spatial estimate is used
+MIN_MOMENT_BATCHES = 4
+
+
+def moments_state(W, H):
+    """The empty moments state of a W x H frame: (W, H, 4) float32 zeros, [x][y]; channels k (batches
+    seen), mean of the batches' demodulated luminance, M2, var_mean (the variance of that mean)."""
+    return np.zeros((int(W), int(H), MOMENT_CHANNELS), np.float32)
+
+
+def moments_add(state, sums_frames, n_samples, feat, *, eps_a=EPS_A, device=0):
+    """Welford update of `state` (moments_state, modified in place and returned) with the batch frames
+    `sums_frames`: (n_frames, W, H, 3) or (W, H, 3) per-pixel radiance SUMS, each over `n_samples`
+    samples (the same count for every frame ever added to one state).  `feat`: (W, H, 8) features.
+    state[..., 3] is the variance of the mean over all batches seen, 0 below two batches; its square
+    root is the standard error of the demodulated luminance."""
+    if not (isinstance(state, np.ndarray) and state.dtype == np.float32 and state.flags.c_contiguous
+            and state.ndim == 3 and state.shape[2] == MOMENT_CHANNELS):
+        raise ValueError("state must be a C-contiguous float32 (W, H, 4) array (moments_state)")
+    W, H = state.shape[:2]
+    frames = np.ascontiguousarray(sums_frames, np.float32)
+    if frames.ndim == 3:
+        frames = frames[None]
+    if frames.ndim != 4 or frames.shape[1:] != (W, H, 3) or frames.shape[0] < 1:
+        raise ValueError(f"sums_frames must be (n_frames, {W}, {H}, 3) or ({W}, {H}, 3), not {frames.shape}")
+    feat = np.ascontiguousarray(feat, np.float32)
+    if feat.shape != (W, H, FEATURE_CHANNELS):
+        raise ValueError(f"feat must be {(W, H, FEATURE_CHANNELS)}, not {feat.shape}")
+    N.check_denoise(N.lib().prt_moments_add(int(device), N.ptr(frames), frames.shape[0], 0, float(n_samples),
+                                            N.ptr(feat), float(eps_a), W, H, N.ptr(state)))
+    return state
+
+
+def moments_add_device(d_sums_ptr, n_frames, n_samples, d_feat_ptr, W, H, d_state_ptr, *, frame_pitch=0, eps_a=EPS_A,
+                       device=0, stream_ptr=None):
+    """prt_moments_add_device: moments_add on device pointers, enqueued on `stream_ptr` without a host
+    synchronisation.  Frame f starts at d_sums_ptr + f * frame_pitch floats (0 = packed); the state
+    (W x H x 4 floats, 16-byte aligned) is updated in place."""
+    vp = ctypes.c_void_p
+    N.check_denoise(N.lib().prt_moments_add_device(int(device), vp(d_sums_ptr), int(n_frames), int(frame_pitch),
+                                                   float(n_samples), vp(d_feat_ptr), float(eps_a), int(W), int(H),
+                                                   vp(d_state_ptr), vp(stream_ptr) if stream_ptr else None))

@@ -8,6 +8,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd --samples 64 --devices 0 1 2 3                   # tiles over 4 GPUs
     python -m pyrenderer_amd --samples 8 --denoise --aov aov/                 # filtered image + feature buffers
     python -m pyrenderer_amd --samples 8 --denoise --denoise-mode variance    # width from the image's own noise
+    python -m pyrenderer_amd --samples 64 --denoise --denoise-mode variance --variance-batches 8   # ... from sample moments
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
 no CPU fallback.
@@ -18,7 +19,7 @@ import time
 
 import numpy as np
 
-from .core.tracing import Accumulator, as_image, build_world, render_sums
+from .core.tracing import Accumulator, as_image, build_world, render_batches, render_sums
 from .io_utils.read_tungsten import read_file
 from .tone_map import finish, reinhard_extended, save_hdr, to_uint8, write_png
 
@@ -54,15 +55,37 @@ def parse(argv=None):
     ap.add_argument("--denoise-mode", choices=("fixed", "variance"), default="fixed",
                     help="with --denoise: 'fixed' (default) stops at colour edges with one fixed width; 'variance' "
                          "takes the width from a per-pixel estimate of the image's own noise")
+    ap.add_argument("--variance-batches", type=int, default=0, metavar="K",
+                    help="with --denoise --denoise-mode variance: take the variance from per-pixel moments of K "
+                         "batch means instead of the spatial estimate (0 = off, else >= 2; --samples must be a "
+                         "multiple of K).  With --interval every pass is a batch (K only switches the moments on) "
+                         "and --samples must be a multiple of the interval; the moments are used from 4 batches on")
     ap.add_argument("--aov", metavar="DIR",
                     help="save the first-hit feature buffers into DIR: albedo.png, normal.png (0.5 n + 0.5) and "
                          "depth.npy ((W, H) float32 [x][y], 0 where no ray hits); with --denoise --denoise-mode "
-                         "variance also variance.npy, the (W, H) float32 variance estimate of the demodulated luminance")
+                         "variance also variance.npy, the (W, H) float32 variance of the demodulated luminance "
+                         "that the filter used (the spatial estimate, or with --variance-batches the sample moments')")
     args = ap.parse_args(argv)
     if args.denoise_iterations is not None:
         if not 0 <= args.denoise_iterations <= 8:
             ap.error(f"--denoise-iterations must be in 0..8, not {args.denoise_iterations}")
         args.denoise = True
+    K = args.variance_batches
+    if K:
+        if K < 2:
+            ap.error(f"--variance-batches must be 0 or >= 2, not {K}")
+        if not (args.denoise and args.denoise_mode == "variance"):
+            ap.error("--variance-batches needs --denoise --denoise-mode variance")
+        if len(args.devices) != 1:
+            ap.error("--variance-batches renders on one device")
+        if args.interval > 0:
+            if args.samples % args.interval:
+                ap.error(f"--variance-batches with --interval {args.interval} needs --samples to be a multiple of it "
+                         f"(equal batches), not {args.samples}")
+        elif args.state:
+            ap.error("--variance-batches with --state needs --interval (every pass is a batch)")
+        elif args.samples < K or args.samples % K:
+            ap.error(f"--variance-batches {K} needs --samples to be a positive multiple of it, not {args.samples}")
     if args.hdr and args.hdr.lower().endswith(".npy"):
         # rounds <= 4 took a .npy FILE here; a directory named out.npy would silently replace it
         ap.error(f"--hdr takes a directory (hdr.npy and spp.npy are written into it), not a .npy file: {args.hdr}")
@@ -92,6 +115,7 @@ def main(argv=None):
     scene, camera = read_file(args.scene)
     W, H = args.resolution if args.resolution else camera.resolution
     t0 = time.perf_counter()
+    feat = given_var = None   # --variance-batches: the features it composed and the moments' variance plane
     if args.interval > 0 or args.state:
         if len(args.devices) != 1:
             raise SystemExit("progressive rendering (--interval/--state) runs on one device")
@@ -106,10 +130,15 @@ def main(argv=None):
             clash = [f"--{k} {given[k]} (saved: {saved[k]})" for k in given if given[k] != saved[k]]
             if clash:
                 raise SystemExit(f"{state} was rendered with other settings: " + ", ".join(clash))
+            if bool(args.variance_batches) != acc.moments:
+                raise SystemExit(f"{state} was saved {'with' if acc.moments else 'without'} sample moments: "
+                                 f"{'add' if acc.moments else 'drop'} --variance-batches")
+            if acc.moments and acc.batch_spp and acc.batch_spp != args.interval:
+                raise SystemExit(f"{state} holds batches of {acc.batch_spp} spp: --interval must be {acc.batch_spp}")
             print(f"resumed {state}: {acc.samples} spp")
         else:
             acc = Accumulator(scene, camera, depth=args.depth, seed=args.seed, resolution=(W, H),
-                              device=args.devices[0], nee=args.nee)
+                              device=args.devices[0], nee=args.nee, moments=bool(args.variance_batches))
         step = args.interval if args.interval > 0 else args.samples
         while acc.samples < args.samples:
             n = min(step, args.samples - acc.samples)
@@ -122,6 +151,19 @@ def main(argv=None):
         sums, samples, mean = acc.sums(), acc.samples, acc.mean()
         W, H = acc.W, acc.H
         world, seed, tile = acc.world, acc.seed, acc.tile
+        if acc.moments:
+            from . import denoise as D
+            feat = acc.features()
+            if acc.batches >= D.MIN_MOMENT_BATCHES:
+                given_var = acc.moments_state[..., 3]
+    elif args.variance_batches:
+        world, seed, tile = build_world(scene, tuple(args.devices)), args.seed, 64
+        sums, feat, mstate = render_batches(scene, camera, spp=args.samples, depth=args.depth,
+                                            variance_batches=args.variance_batches, seed=args.seed, resolution=(W, H),
+                                            device=args.devices[0], nee=args.nee, world=world)
+        samples, given_var = args.samples, mstate[..., 3]
+        # render(..., variance_batches=K)'s unfiltered mean, bit for bit
+        mean = sums / np.float32(samples)
     else:
         world, seed, tile = build_world(scene, tuple(args.devices)), args.seed, 64
         sums = render_sums(scene, camera, spp=args.samples, depth=args.depth, seed=args.seed, resolution=(W, H),
@@ -132,14 +174,16 @@ def main(argv=None):
     if args.denoise or args.aov:
         from . import denoise as D
         dev = args.devices[0]
-        feat = D.features_packed(world.device_scene(dev), camera.convert_to_taichi_camera().packed(), W, H,
-                                 samples=1, seed=seed, tile=tile)
+        if feat is None:
+            feat = D.features_packed(world.device_scene(dev), camera.convert_to_taichi_camera().packed(), W, H,
+                                     samples=1, seed=seed, tile=tile)
         if args.aov:
             write_aov(args.aov, feat)
         if args.denoise:
             it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
             if args.denoise_mode == "variance":
-                mean, var = D.denoise_variance(mean, feat, iterations=it, device=dev, return_variance=True)
+                mean, var = D.denoise_variance(mean, feat, iterations=it, device=dev, return_variance=True,
+                                               variance=given_var)
                 if args.aov:
                     np.save(os.path.join(args.aov, "variance.npy"), var)
             else:

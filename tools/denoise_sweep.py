@@ -11,6 +11,14 @@ ratio over the twelve frames.  The yardstick is the 4096-spp render, never the f
 at the fixed filter's defaults) on the same frames with the same score:
 
     python tools/denoise_sweep.py --mode variance --out profiles/denoise_var_sweep.txt
+
+--mode variance --variance-batches K [K ...] sweeps the same three parameters with the variance taken from
+per-pixel moments of K batch means (render_batches) instead of the 7 x 7 estimate, one section per K, on
+the spp columns that K divides.  The noisy frame is then the batch-order mean, so each section also scores
+the fixed filter's and the spatial estimate's defaults on those very frames:
+
+    python tools/denoise_sweep.py --mode variance --variance-batches 4 8 --spp 4 8 16 32 64 \
+        --out profiles/denoise_mom_sweep.txt
 """
 import argparse
 import itertools
@@ -76,6 +84,57 @@ def sweep_variance(a, frames):
               f"(geometric-mean ratio {g:.4f}, worst frame {max(ratios):.4f})")
 
 
+def sweep_moments(a):
+    """The --variance-batches leg: per K a table for sigma_l, eps_l, sigma_z with the moments' variance."""
+    from pyrenderer_amd import denoise as D
+    from pyrenderer_amd.core.tracing import build_world, render, render_batches
+    out = sys.stdout if a.out == "-" else open(a.out, "w")
+    worlds = {}
+    for which in ("cornell", "specular"):
+        scene, cam = load(which)
+        world = build_world(scene, (0,))
+        worlds[which] = (scene, cam, world, {size: render(scene, cam, spp=a.ref_spp, depth=a.depth, seed=1,
+                                                          resolution=(size, size), world=world) for size in a.sizes})
+        print(f"rendered {which} references", file=sys.stderr, flush=True)
+    for K in a.variance_batches:
+        frames = []
+        for which, (scene, cam, world, refs) in worlds.items():
+            for size in a.sizes:
+                for spp in (s for s in a.spp if s >= K and s % K == 0):
+                    sums, feat, state = render_batches(scene, cam, spp=spp, depth=a.depth, variance_batches=K, seed=2,
+                                                       resolution=(size, size), world=world)
+                    noisy = sums / np.float32(spp)
+                    frames.append((f"{which}-{size}-{spp}spp", noisy, feat, refs[size], rmse(noisy, refs[size]),
+                                   np.ascontiguousarray(state[..., 3])))
+        rows = []
+        for sl, el, sz in itertools.product(VAR_SIGMA_L, VAR_EPS_L, VAR_SIGMA_Z):
+            ratios = [rmse(D.denoise_variance(n, f, iterations=a.iterations, sigma_l=sl, sigma_z=sz, eps_l=el, variance=v), r) / e
+                      for _, n, f, r, e, v in frames]
+            rows.append((float(np.exp(np.mean(np.log(ratios)))), sl, el, sz, ratios))
+        rows.sort(key=lambda t: t[0])
+        fixed = [rmse(D.denoise(n, f, iterations=a.iterations), r) / e for _, n, f, r, e, _ in frames]
+        spatial = [rmse(D.denoise_variance(n, f, iterations=a.iterations), r) / e for _, n, f, r, e, _ in frames]
+        default = next(r for r in rows if (r[1], r[2], r[3]) == (D.VAR_SIGMA_L, D.VAR_EPS_L, D.VAR_SIGMA_Z))
+        gm = lambda v: float(np.exp(np.mean(np.log(v))))
+        print(f"# K = {K}: variance of the mean from {K} batch means; iterations {a.iterations}, depth {a.depth}, "
+              f"reference {a.ref_spp} spp (seed 1), noisy frames seed 2 (batch-order mean), eps_a {D.EPS_A:g}, "
+              f"eps_z {D.EPS_Z:g}", file=out)
+        print("# frames: " + " ".join(f[0] for f in frames), file=out)
+        print("# noisy RMSE: " + "  ".join(f"{f[0]} {f[4]:.5f}" for f in frames), file=out)
+        print(f"# fixed default    {gm(fixed):.4f} worst {max(fixed):.4f}  " + " ".join(f"{r:.4f}" for r in fixed), file=out)
+        print(f"# spatial default  {gm(spatial):.4f} worst {max(spatial):.4f}  " + " ".join(f"{r:.4f}" for r in spatial), file=out)
+        print(f"# moments default  {default[0]:.4f} worst {max(default[4]):.4f}  " + " ".join(f"{r:.4f}" for r in default[4]), file=out)
+        print("# columns: geometric-mean ratio, sigma_l, eps_l, sigma_z, then RMSE(denoised) / RMSE(noisy) per frame", file=out)
+        for g, sl, el, sz, ratios in rows:
+            print(f"{g:.4f} {sl:g} {el:g} {sz:g}  " + " ".join(f"{r:.4f}" for r in ratios), file=out)
+        out.flush()
+        safe = [r for r in rows if max(r[4]) < 1.0]
+        print(f"K {K}: fixed {gm(fixed):.4f} spatial {gm(spatial):.4f} moments default {default[0]:.4f} best {rows[0][:4]}"
+              + (f" best with every frame improved {safe[0][:4]} worst {max(safe[0][4]):.4f}" if safe else " (no set improves every frame)"))
+    if out is not sys.stdout:
+        out.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default="-", help="table file ('-' = stdout)")
@@ -87,7 +146,13 @@ def main():
     ap.add_argument("--mode", choices=("fixed", "variance"), default="fixed",
                     help="fixed: sigma_c, sigma_z, eps_a, eps_z of denoise(); variance: sigma_l, eps_l, sigma_z of "
                          "denoise_variance()")
+    ap.add_argument("--variance-batches", type=int, nargs="+", default=[], metavar="K",
+                    help="with --mode variance: take the variance from K batch means (one section per K)")
     a = ap.parse_args()
+    if a.variance_batches:
+        if a.mode != "variance" or min(a.variance_batches) < 2:
+            ap.error("--variance-batches needs --mode variance and K >= 2")
+        return sweep_moments(a)
     from pyrenderer_amd.core.tracing import build_world, render
     from pyrenderer_amd.denoise import denoise, features
 

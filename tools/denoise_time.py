@@ -4,6 +4,9 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
 
     python tools/denoise_time.py --sizes 512 4096
     python tools/denoise_time.py --mode variance --sizes 512 4096   # the variance-guided mode (prt_denoise_var_device)
+    python tools/denoise_time.py --mode given --sizes 512 4096      # ... with a given variance plane (prt_denoise_var_given_device)
+    python tools/denoise_time.py --mode moments --sizes 512 4096    # prt_moments_add_device over --frames frames (default 8)
+    python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
 """
 import argparse
 import json
@@ -24,7 +27,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--mode", choices=("fixed", "variance"), default="fixed")
+    ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "batching"), default="fixed")
+    ap.add_argument("--frames", type=int, default=8, help="--mode moments: n_frames per call")
     a = ap.parse_args()
     import torch
     from pyrenderer_amd import denoise as D
@@ -34,6 +38,8 @@ def main():
     scene, cam = read_file(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene.json"))
     world = build_world(scene, (0,))
     base = 512
+    if a.mode == "batching":
+        return time_batching(a, scene, cam, world)
     noisy = render(scene, cam, spp=8, depth=8, seed=2, resolution=(base, base), world=world)
     feat = D.features(scene, cam, resolution=(base, base), samples=1, seed=2, world=world)
     dev = torch.device("cuda:0")
@@ -44,7 +50,11 @@ def main():
         f = np.ascontiguousarray(np.tile(feat, (k, k, 1))[:size, :size])
         d_c, d_f = torch.from_numpy(c).to(dev), torch.from_numpy(f).to(dev)
         d_out = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
-        variance = a.mode == "variance"
+        if a.mode == "moments":
+            time_moments(a, size, c, d_f, stream)
+            continue
+        variance = a.mode in ("variance", "given")
+        d_iv = torch.from_numpy(D.denoise_variance(c, f, iterations=0, return_variance=True)[1]).to(dev) if a.mode == "given" else None
         need = D.work_bytes_variance(size, size) if variance else D.work_bytes(size, size)
         d_work = torch.empty(need, dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
@@ -52,7 +62,8 @@ def main():
         def run():
             if variance:
                 D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), size, size, d_out.data_ptr(), d_work.data_ptr(),
-                                          need, iterations=a.iterations, stream_ptr=stream.cuda_stream)
+                                          need, iterations=a.iterations, stream_ptr=stream.cuda_stream,
+                                          d_in_var_ptr=d_iv.data_ptr() if d_iv is not None else None)
                 return
             D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), size, size, d_out.data_ptr(), d_work.data_ptr(), need,
                              iterations=a.iterations, stream_ptr=stream.cuda_stream)
@@ -83,6 +94,10 @@ def main():
             per_pass = n * (16 + 16 + 8 + 4 + 16)
             fixed += n * ((16 + 16 + 8) + (16 + 4))
             what = "denoise_var_time"
+        if a.mode == "given":
+            # var_given_kernel reads (I, Z), the class plane and the variance and writes (I, var) and the depth
+            fixed += n * ((16 + 16 + 4) + (16 + 4)) - n * ((16 + 16 + 8) + (16 + 4))
+            what = "denoise_var_given_time"
         total = per_pass * a.iterations + fixed
         print(json.dumps(dict(what=what, size=size, iterations=a.iterations, median_ms=round(med, 4),
                               min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), reps=a.reps,
@@ -90,6 +105,79 @@ def main():
                               implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
                               hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))), flush=True)
         del d_c, d_f, d_out, d_work
+
+
+def _median_ms(run, stream, warmup, reps):
+    import torch
+    for _ in range(warmup):
+        run()
+    stream.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        run()
+        e1.record(stream)
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    return ms
+
+
+def time_moments(a, size, c, d_f, stream):
+    """prt_moments_add_device over a.frames packed frames of sums (the 8-spp mean times 8, perturbed per frame)."""
+    import torch
+    from pyrenderer_amd import denoise as D
+    dev = d_f.device
+    k = a.frames
+    scale = torch.linspace(0.5, 1.5, k, device=dev).reshape(k, 1, 1, 1)
+    d_s = (torch.from_numpy(c).to(dev)[None] * 8.0 * scale).contiguous()
+    d_state = torch.zeros((size, size, 4), dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+
+    def run():
+        D.moments_add_device(d_s.data_ptr(), k, 8.0, d_f.data_ptr(), size, size, d_state.data_ptr(),
+                             stream_ptr=stream.cuda_stream)
+
+    ms = _median_ms(run, stream, a.warmup, a.reps)
+    med = ms[len(ms) // 2]
+    n = size * size
+    total = n * (k * 12 + 32 + 16 + 16)   # the frames and the features read, the state read and written
+    print(json.dumps(dict(what="moments_add_time", size=size, n_frames=k, median_ms=round(med, 4), min_ms=round(ms[0], 4),
+                          max_ms=round(ms[-1], 4), reps=a.reps, bytes_total=total,
+                          implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
+                          hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))), flush=True)
+
+
+def time_batching(a, scene, cam, world):
+    """Host wall clock at 512^2, 64 spp, of the calls around variance_batches=8, taken in alternation (all
+    are synchronous): render() without a filter and render(denoise="variance"), the two unbatched paths
+    that the moments leave as they were; render(denoise="variance", variance_batches=8); and the
+    one-sample feature composition that both filtered calls contain."""
+    import time
+    from pyrenderer_amd import denoise as D
+    from pyrenderer_amd.core.tracing import render
+    kw = dict(spp=64, depth=8, seed=2, resolution=(512, 512), world=world)
+    ds, cam_packed = world.device_scene(0), cam.convert_to_taichi_camera().packed()
+    legs = {"render": lambda: render(scene, cam, **kw),
+            "render_variance": lambda: render(scene, cam, denoise="variance", **kw),
+            "render_variance_batches8": lambda: render(scene, cam, denoise="variance", variance_batches=8, **kw),
+            "features": lambda: D.features_packed(ds, cam_packed, 512, 512, samples=1, seed=2, tile=64)}
+    t = {k: [] for k in legs}
+    warm, reps = 2, 9
+    for i in range(warm + reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            if i >= warm:
+                t[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: sorted(v)[len(v) // 2] for k, v in t.items()}
+    out = dict(what="render_batching_time", size=512, spp=64, batches=8, reps=reps)
+    for k in legs:
+        out[k + "_ms"] = dict(median=round(med[k], 2), min=round(min(t[k]), 2), max=round(max(t[k]), 2))
+    out["batched_minus_unbatched_ms"] = round(med["render_variance_batches8"] - med["render_variance"], 2)
+    out["batched_over_unbatched"] = round(med["render_variance_batches8"] / med["render_variance"], 3)
+    print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

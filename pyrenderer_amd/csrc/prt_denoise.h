@@ -41,23 +41,20 @@ size_t var_work_bytes(int W, int H);
 // estimate of the demodulated luminance, before any pass; d_work holds var_work_bytes(W, H) bytes,
 // 16-byte aligned.  Returns the first launch error.
 //
+// d_in_var: null estimates the variance with the 7 x 7 window.  A plane of W x H floats (variance
+// from per-pixel sample moments) stands in its place: at a usable pixel a value that is finite and
+// >= 0 is taken as it is, anything else counts as 0, and d_out_var receives the variance actually
+// used.  d_in_var must not alias d_out or d_out_var.
+//
 // Finiteness: the variance planes are always finite (a variance that is not becomes 0, which is
 // what an overflow of l * l, |l| >= 2^64, ends in).  Every colour of a pixel that is not set aside
 // is finite while the demodulated radiance |C_c / fmax(A_c, eps_a)| <= 2^126 and the albedo
 // A_c <= 1: the luminance and the difference of two luminances then stay finite, so no weight is
 // inf / inf, and a weighted mean of such values times the albedo stays in range.
-hipError_t enqueue_var(const float* d_color, const float* d_feat, int W, int H, int iterations, const VarParams& p,
-                       float* d_out, float* d_out_var, void* d_work, hipStream_t stream);
+hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
+                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream);
 
 // ---- variance from per-pixel sample moments ----
-
-// enqueue_var with the variance plane d_in_var (W x H floats) in place of the 7 x 7 estimate: at a
-// usable pixel a value that is finite and >= 0 is taken as it is, anything else counts as 0.
-// d_out_var (may be null) receives the variance actually used.  Scratch: var_work_bytes(W, H).
-// d_in_var must not alias d_out or d_out_var.
-hipError_t enqueue_var_given(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
-                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
-                             hipStream_t stream);
 
 // Running Welford update of the demodulated luminance over n_frames frames of per-pixel radiance sums
 // (frame f at d_sums + f * frame_pitch floats, W x H x 3, each the sum of n_samples samples).

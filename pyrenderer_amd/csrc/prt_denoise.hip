@@ -78,12 +78,35 @@ __device__ __forceinline__ float e16(float x) {
     return r * r;
 }
 
-// one a-trous pass at `step`; sc2 = (sigma_c * 2^-i)^2
-__global__ __launch_bounds__(kBlockX* kBlockY) void atrous_kernel(const float4* __restrict__ src,
-                                                                  float4* __restrict__ dst,
-                                                                  const float4* __restrict__ nc,
-                                                                  const float2* __restrict__ grad, int W, int H,
-                                                                  int step, float sc2, float sigma_z, float eps_z) {
+// power-128 normal weight
+__device__ __forceinline__ float normal_weight(const float4& np, const float4& nq) {
+    float wn = fmaxf(0.0f, (np.x * nq.x + np.y * nq.y) + np.z * nq.z);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) wn = wn * wn;
+    return wn;
+}
+
+// depth weight of a tap at pixel offset (ox, oy): the depth difference against the centre's depth gradient
+__device__ __forceinline__ float depth_weight(float zp, float zq, const float2& g, float ox, float oy, float sigma_z,
+                                              float eps_z) {
+    const float gd = g.x * ox + g.y * oy;
+    return e16(fabsf(zp - zq) / (sigma_z * fabsf(gd) + eps_z));
+}
+
+__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+
+// One a-trous pass at `step`.  Fixed filter (kVar false): src is (I.rgb, Z), the colour term is the squared
+// colour distance over sigma = (sigma_c * 2^-i)^2; zp and eps_l are not read.  Variance-guided (kVar true; the
+// spatial half of SVGF, Schied et al. 2017): src is (I.rgb, var) with the depth in the plane zp, the colour
+// term is the luminance distance over sigma = sigma_l times the 3 x 3-prefiltered standard deviation, and
+// the variance is carried along.  tests/atrous_ref.py and tests/atrous_var_ref.py restate the two.
+template <bool kVar>
+__global__ __launch_bounds__(kBlockX* kBlockY) void pass_kernel(const float4* __restrict__ src,
+                                                                float4* __restrict__ dst,
+                                                                const float4* __restrict__ nc,
+                                                                const float2* __restrict__ grad,
+                                                                const float* __restrict__ zp, int W, int H, int step,
+                                                                float sigma, float sigma_z, float eps_z, float eps_l) {
     int x, y;
     if (!pixel_of_lane(W, H, x, y)) return;
     const size_t p = (size_t)x * (size_t)H + (size_t)y;
@@ -95,9 +118,33 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void atrous_kernel(const float4* 
         dst[p] = ip;
         return;
     }
+    float den = sigma, lp = 0.0f, zc = ip.w;
+    if constexpr (kVar) {
+        const float gk[3] = {0.25f, 0.125f, 0.0625f};
+        float gv = 0.0f, gs = 0.0f;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= W) continue;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy) {
+                const int qy = y + dy;
+                if (qy < 0 || qy >= H) continue;
+                const size_t q = (size_t)qx * (size_t)H + (size_t)qy;
+                if (__float_as_uint(nc[q].w) != cls) continue;
+                const float gq = gk[(dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)];
+                gv = gv + gq * src[q].w;
+                gs = gs + gq;
+            }
+        }
+        const float sd = sqrtf(gv / gs);
+        den = sigma * sd + eps_l;
+        lp = lum(ip.x, ip.y, ip.z);
+        zc = zp[p];
+    }
     const float2 g = grad[p];
     const float k[3] = {0.375f, 0.25f, 0.0625f};
-    float sum_w = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f;
+    float sum_w = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f;
 #pragma unroll
     for (int dx = -2; dx <= 2; ++dx) {
         const int qx = x + step * dx;
@@ -113,22 +160,31 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void atrous_kernel(const float4* 
             const float h = k[dx < 0 ? -dx : dx] * k[dy < 0 ? -dy : dy];
             float w = h;
             if (dx != 0 || dy != 0) {
-                float wn = fmaxf(0.0f, (np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) wn = wn * wn;
-                const float gd = g.x * (float)(step * dx) + g.y * (float)(step * dy);
-                const float xz = fabsf(ip.w - iq.w) / (sigma_z * fabsf(gd) + eps_z);
-                const float dr = ip.x - iq.x, dg = ip.y - iq.y, db = ip.z - iq.z;
-                const float xc = ((dr * dr + dg * dg) + db * db) / sc2;
-                w = ((h * wn) * e16(xz)) * e16(xc);
+                float zq = iq.w;
+                if constexpr (kVar) zq = zp[q];
+                const float wz = depth_weight(zc, zq, g, (float)(step * dx), (float)(step * dy), sigma_z, eps_z);
+                float xc;
+                if constexpr (kVar) {
+                    xc = fabsf(lp - lum(iq.x, iq.y, iq.z)) / den;
+                } else {
+                    const float dr = ip.x - iq.x, dg = ip.y - iq.y, db = ip.z - iq.z;
+                    xc = ((dr * dr + dg * dg) + db * db) / den;
+                }
+                w = ((h * normal_weight(np, nq)) * wz) * e16(xc);
             }
             sum_w = sum_w + w;
             s0 = s0 + w * iq.x;
             s1 = s1 + w * iq.y;
             s2 = s2 + w * iq.z;
+            if constexpr (kVar) sv = sv + (w * w) * iq.w;
         }
     }
-    dst[p] = make_float4(s0 / sum_w, s1 / sum_w, s2 / sum_w, ip.w);
+    float last = ip.w;   // the fixed filter carries the depth
+    if constexpr (kVar) {
+        last = sv / (sum_w * sum_w);
+        if (!finite_f(last)) last = 0.0f;
+    }
+    dst[p] = make_float4(s0 / sum_w, s1 / sum_w, s2 / sum_w, last);
 }
 
 // post-pass: re-modulate; a set-aside pixel returns its input colour
@@ -163,19 +219,9 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void post_kernel(const float4* __
     out[p * 3 + 2] = o2;
 }
 
-// ---- variance-guided mode (the spatial half of SVGF, Schied et al. 2017) ----
-// The pre-pass and the post-pass are the ones above.  Between them the colour travels as (I.rgb, var)
-// and the depth in a float plane of its own; tests/atrous_var_ref.py restates both kernels.
-
-__device__ __forceinline__ float lum(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
-
-// power-128 normal weight of the fixed filter
-__device__ __forceinline__ float normal_weight(const float4& np, const float4& nq) {
-    float wn = fmaxf(0.0f, (np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-#pragma unroll
-    for (int j = 0; j < 7; ++j) wn = wn * wn;
-    return wn;
-}
+// ---- variance-guided mode ----
+// The pre-pass, the passes and the post-pass are the ones above.  Between pre and post the colour travels as
+// (I.rgb, var) and the depth in a float plane of its own; tests/atrous_var_ref.py restates the estimate.
 
 // variance estimate: per hit pixel the weighted second central moment of the luminance over the
 // 7 x 7 window at step 1; repacks (I.rgb, Z) into (I.rgb, var) and the depth plane.  The block's
@@ -237,9 +283,8 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_estimate_kernel(const fl
                 float w = 1.0f;
                 if (dx != 0 || dy != 0) {
                     const float4 nq = make_float4(s_nx[cx + dx][cy + dy], s_ny[cx + dx][cy + dy], s_nz[cx + dx][cy + dy], 0.0f);
-                    const float gd = g.x * (float)dx + g.y * (float)dy;
-                    const float xz = fabsf(ip.w - s_z[cx + dx][cy + dy]) / (sigma_z * fabsf(gd) + eps_z);
-                    w = normal_weight(np, nq) * e16(xz);
+                    w = normal_weight(np, nq) *
+                        depth_weight(ip.w, s_z[cx + dx][cy + dy], g, (float)dx, (float)dy, sigma_z, eps_z);
                 }
                 const float l = s_l[cx + dx][cy + dy];
                 sw = sw + w;
@@ -254,81 +299,6 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_estimate_kernel(const fl
     iv[p] = make_float4(ip.x, ip.y, ip.z, var);
     zp[p] = ip.w;
     if (out_var) out_var[p] = var;
-}
-
-// one variance-guided pass at `step`: the fixed filter's taps with the colour term replaced by a
-// luminance term scaled by the 3 x 3-prefiltered standard deviation; carries the variance along
-__global__ __launch_bounds__(kBlockX* kBlockY) void var_atrous_kernel(const float4* __restrict__ src,
-                                                                      float4* __restrict__ dst,
-                                                                      const float4* __restrict__ nc,
-                                                                      const float2* __restrict__ grad,
-                                                                      const float* __restrict__ zp, int W, int H, int step,
-                                                                      float sigma_l, float sigma_z, float eps_z,
-                                                                      float eps_l) {
-    int x, y;
-    if (!pixel_of_lane(W, H, x, y)) return;
-    const size_t p = (size_t)x * (size_t)H + (size_t)y;
-    const float4 ip = src[p];
-    const float4 np = nc[p];
-    const uint32_t cls = __float_as_uint(np.w);
-    if (cls != kHit) {
-        dst[p] = ip;
-        return;
-    }
-    const float gk[3] = {0.25f, 0.125f, 0.0625f};
-    float gv = 0.0f, gs = 0.0f;
-#pragma unroll
-    for (int dx = -1; dx <= 1; ++dx) {
-        const int qx = x + dx;
-        if (qx < 0 || qx >= W) continue;
-#pragma unroll
-        for (int dy = -1; dy <= 1; ++dy) {
-            const int qy = y + dy;
-            if (qy < 0 || qy >= H) continue;
-            const size_t q = (size_t)qx * (size_t)H + (size_t)qy;
-            if (__float_as_uint(nc[q].w) != cls) continue;
-            const float gq = gk[(dx < 0 ? -dx : dx) + (dy < 0 ? -dy : dy)];
-            gv = gv + gq * src[q].w;
-            gs = gs + gq;
-        }
-    }
-    const float sd = sqrtf(gv / gs);
-    const float den = sigma_l * sd + eps_l;
-    const float lp = lum(ip.x, ip.y, ip.z);
-    const float zc = zp[p];
-    const float2 g = grad[p];
-    const float k[3] = {0.375f, 0.25f, 0.0625f};
-    float sum_w = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sv = 0.0f;
-#pragma unroll
-    for (int dx = -2; dx <= 2; ++dx) {
-        const int qx = x + step * dx;
-        if (qx < 0 || qx >= W) continue;
-#pragma unroll
-        for (int dy = -2; dy <= 2; ++dy) {
-            const int qy = y + step * dy;
-            if (qy < 0 || qy >= H) continue;
-            const size_t q = (size_t)qx * (size_t)H + (size_t)qy;
-            const float4 nq = nc[q];
-            if (__float_as_uint(nq.w) != cls) continue;
-            const float4 iq = src[q];
-            const float h = k[dx < 0 ? -dx : dx] * k[dy < 0 ? -dy : dy];
-            float w = h;
-            if (dx != 0 || dy != 0) {
-                const float gd = g.x * (float)(step * dx) + g.y * (float)(step * dy);
-                const float xz = fabsf(zc - zp[q]) / (sigma_z * fabsf(gd) + eps_z);
-                const float xl = fabsf(lp - lum(iq.x, iq.y, iq.z)) / den;
-                w = ((h * normal_weight(np, nq)) * e16(xz)) * e16(xl);
-            }
-            sum_w = sum_w + w;
-            s0 = s0 + w * iq.x;
-            s1 = s1 + w * iq.y;
-            s2 = s2 + w * iq.z;
-            sv = sv + (w * w) * iq.w;
-        }
-    }
-    float var = sv / (sum_w * sum_w);
-    if (!finite_f(var)) var = 0.0f;
-    dst[p] = make_float4(s0 / sum_w, s1 / sum_w, s2 / sum_w, var);
 }
 
 // ---- variance from per-pixel sample moments (tests/moments_ref.py restates both) ----
@@ -390,6 +360,52 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* 
     state[p] = make_float4(k, mean, m2, vm);
 }
 
+// the planes of a frame's scratch, in the order work_bytes / var_work_bytes count them
+struct Planes {
+    float4* a[2];   // ping-pong (I.rgb, Z) or (I.rgb, var)
+    float4* nc;     // (N.xyz, class)
+    float2* grad;   // depth gradient
+    float* zp;      // depth; only the variance-guided mode's scratch holds it
+    Planes(void* d_work, int W, int H, bool variance) {
+        const size_t n = (size_t)W * (size_t)H;
+        a[0] = static_cast<float4*>(d_work);
+        a[1] = a[0] + n;
+        nc = a[1] + n;
+        grad = reinterpret_cast<float2*>(nc + n);
+        zp = variance ? reinterpret_cast<float*>(grad + n) : nullptr;
+    }
+};
+
+const dim3 kBlock(kBlockY, kBlockX);
+
+dim3 grid_of(int W, int H) {
+    return dim3((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+}
+
+// `iterations` passes from s.a[0] and the post-pass; sigma is sigma_c (fixed) or sigma_l (variance-guided)
+template <bool kVar>
+hipError_t passes_and_post(const Planes& s, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                           float sigma, float sigma_z, float eps_a, float eps_z, float eps_l, float* d_out,
+                           hipStream_t stream) {
+    const dim3 grid = grid_of(W, H);
+    int cur = 0;
+    for (int i = 0; i < iterations; ++i) {
+        float sg = sigma;
+        if constexpr (!kVar) {
+            // sigma_c * 2^-i is an exact scaling; its square is one f32 multiplication
+            const float sc = sigma * (1.0f / (float)(1 << i));
+            sg = sc * sc;
+        }
+        pass_kernel<kVar><<<grid, kBlock, 0, stream>>>(s.a[cur], s.a[cur ^ 1], s.nc, s.grad, s.zp, W, H, 1 << i, sg,
+                                                       sigma_z, eps_z, eps_l);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        cur ^= 1;
+    }
+    post_kernel<<<grid, kBlock, 0, stream>>>(s.a[cur], s.nc, d_color, d_feat, W, H, eps_a, d_out);
+    return hipGetLastError();
+}
+
 }  // namespace
 
 size_t work_bytes(int W, int H) {
@@ -399,28 +415,13 @@ size_t work_bytes(int W, int H) {
 
 hipError_t enqueue(const float* d_color, const float* d_feat, int W, int H, int iterations, const Params& p,
                    float* d_out, void* d_work, hipStream_t stream) {
-    const size_t n = (size_t)W * (size_t)H;
-    float4* a[2] = {static_cast<float4*>(d_work), static_cast<float4*>(d_work) + n};
-    float4* nc = a[1] + n;
-    float2* grad = reinterpret_cast<float2*>(nc + n);
-    const dim3 block(kBlockY, kBlockX);
-    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+    const Planes s(d_work, W, H, false);
     (void)hipGetLastError();   // an error left on this thread by earlier, unrelated calls is not ours
-    pre_kernel<<<grid, block, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, a[0], nc, grad);
-    hipError_t e = hipGetLastError();
+    pre_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, s.a[0], s.nc, s.grad);
+    const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int cur = 0;
-    for (int i = 0; i < iterations; ++i) {
-        // sigma_c * 2^-i is an exact scaling; its square is one f32 multiplication
-        const float sc = p.sigma_c * (1.0f / (float)(1 << i));
-        atrous_kernel<<<grid, block, 0, stream>>>(a[cur], a[cur ^ 1], nc, grad, W, H, 1 << i, sc * sc, p.sigma_z,
-                                                  p.eps_z);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        cur ^= 1;
-    }
-    post_kernel<<<grid, block, 0, stream>>>(a[cur], nc, d_color, d_feat, W, H, p.eps_a, d_out);
-    return hipGetLastError();
+    return passes_and_post<false>(s, d_color, d_feat, W, H, iterations, p.sigma_c, p.sigma_z, p.eps_a, p.eps_z, 0.0f,
+                                  d_out, stream);
 }
 
 size_t var_work_bytes(int W, int H) {
@@ -428,72 +429,32 @@ size_t var_work_bytes(int W, int H) {
     return (n * 60 + 255) & ~(size_t)255;
 }
 
-hipError_t enqueue_var(const float* d_color, const float* d_feat, int W, int H, int iterations, const VarParams& p,
-                       float* d_out, float* d_out_var, void* d_work, hipStream_t stream) {
-    const size_t n = (size_t)W * (size_t)H;
-    float4* a[2] = {static_cast<float4*>(d_work), static_cast<float4*>(d_work) + n};
-    float4* nc = a[1] + n;
-    float2* grad = reinterpret_cast<float2*>(nc + n);
-    float* zp = reinterpret_cast<float*>(grad + n);
-    const dim3 block(kBlockY, kBlockX);
-    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
+                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream) {
+    const Planes s(d_work, W, H, true);
+    const dim3 grid = grid_of(W, H);
     (void)hipGetLastError();
-    // the pre-pass writes (I.rgb, Z) into the second ping-pong plane; the estimate repacks it into the first
-    pre_kernel<<<grid, block, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, a[1], nc, grad);
+    // the pre-pass writes (I.rgb, Z) into the second ping-pong plane; the estimate, or the caller's variance
+    // in its place, repacks it into the first
+    pre_kernel<<<grid, kBlock, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, s.a[1], s.nc, s.grad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    var_estimate_kernel<<<grid, block, 0, stream>>>(a[1], nc, grad, W, H, p.sigma_z, p.eps_z, a[0], zp, d_out_var);
+    if (d_in_var)
+        var_given_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, d_in_var, W, H, s.a[0], s.zp, d_out_var);
+    else
+        var_estimate_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, s.grad, W, H, p.sigma_z, p.eps_z, s.a[0], s.zp,
+                                                         d_out_var);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    int cur = 0;
-    for (int i = 0; i < iterations; ++i) {
-        var_atrous_kernel<<<grid, block, 0, stream>>>(a[cur], a[cur ^ 1], nc, grad, zp, W, H, 1 << i, p.sigma_l,
-                                                      p.sigma_z, p.eps_z, p.eps_l);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        cur ^= 1;
-    }
-    post_kernel<<<grid, block, 0, stream>>>(a[cur], nc, d_color, d_feat, W, H, p.eps_a, d_out);
-    return hipGetLastError();
-}
-
-hipError_t enqueue_var_given(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
-                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
-                             hipStream_t stream) {
-    const size_t n = (size_t)W * (size_t)H;
-    float4* a[2] = {static_cast<float4*>(d_work), static_cast<float4*>(d_work) + n};
-    float4* nc = a[1] + n;
-    float2* grad = reinterpret_cast<float2*>(nc + n);
-    float* zp = reinterpret_cast<float*>(grad + n);
-    const dim3 block(kBlockY, kBlockX);
-    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
-    (void)hipGetLastError();
-    // enqueue_var's planes and launches, with the caller's variance in place of the 7 x 7 estimate
-    pre_kernel<<<grid, block, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, a[1], nc, grad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    var_given_kernel<<<grid, block, 0, stream>>>(a[1], nc, d_in_var, W, H, a[0], zp, d_out_var);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    int cur = 0;
-    for (int i = 0; i < iterations; ++i) {
-        var_atrous_kernel<<<grid, block, 0, stream>>>(a[cur], a[cur ^ 1], nc, grad, zp, W, H, 1 << i, p.sigma_l,
-                                                      p.sigma_z, p.eps_z, p.eps_l);
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        cur ^= 1;
-    }
-    post_kernel<<<grid, block, 0, stream>>>(a[cur], nc, d_color, d_feat, W, H, p.eps_a, d_out);
-    return hipGetLastError();
+    return passes_and_post<true>(s, d_color, d_feat, W, H, iterations, p.sigma_l, p.sigma_z, p.eps_a, p.eps_z, p.eps_l,
+                                 d_out, stream);
 }
 
 hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
                            float eps_a, int W, int H, float* d_io_state, hipStream_t stream) {
-    const dim3 block(kBlockY, kBlockX);
-    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
     (void)hipGetLastError();
-    moments_kernel<<<grid, block, 0, stream>>>(d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
-                                               reinterpret_cast<float4*>(d_io_state));
+    moments_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
+                                                         reinterpret_cast<float4*>(d_io_state));
     return hipGetLastError();
 }
 

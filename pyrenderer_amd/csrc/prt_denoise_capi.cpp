@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/prt.h"
 #include "prt_denoise.h"
@@ -27,6 +28,12 @@ int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(PRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
     } while (0)
 
+#define DN_TRY(expr)                  \
+    do {                              \
+        const int rc_ = (expr);       \
+        if (rc_ != PRT_OK) return rc_; \
+    } while (0)
+
 // Makes `dev` current for its lifetime; `err` is hipSetDevice's result, which the caller checks
 // before it enqueues anything (an invalid ordinal must not run on whatever device was current).
 struct DeviceGuard {
@@ -40,35 +47,93 @@ struct DeviceGuard {
 };
 
 // device ordinal against the visible devices: PRT_ERR_HIP without a device, PRT_ERR_ARG out of range
-int check_device(const char* fn, int device) {
+int check_device(const std::string& who, int device) {
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
         (void)hipGetLastError();
-        return fail(PRT_ERR_HIP, std::string(fn) + ": no HIP device");
+        return fail(PRT_ERR_HIP, who + ": no HIP device");
     }
-    if (device >= n_dev) return fail(PRT_ERR_ARG, std::string(fn) + ": no such device");
+    if (device >= n_dev) return fail(PRT_ERR_ARG, who + ": no such device");
     return PRT_OK;
 }
 
-struct DevMem {
-    void* p = nullptr;
-    DevMem() = default;
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { if (p) (void)hipFree(p); }
+// Device buffers of a host-form entry point, freed when it returns.  The buffers are allocated first,
+// one after the other (after a failure nothing more is allocated and oom() tells); then upload() copies
+// in every buffer that has a source and, after the kernels, download() copies out every one that has
+// a destination.  The copies on the null stream follow the kernels and block until they are done.
+class Staging {
+    struct Buf {
+        void* d;
+        const void* from;
+        void* to;
+        size_t bytes;
+    };
+    std::vector<Buf> bufs_;
+    bool oom_ = false;
+
+    hipError_t copy(bool up) const {
+        for (const Buf& b : bufs_) {
+            hipError_t e = hipSuccess;
+            if (up && b.from) e = hipMemcpy(b.d, b.from, b.bytes, hipMemcpyHostToDevice);
+            if (!up && b.to) e = hipMemcpy(b.to, b.d, b.bytes, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    }
+
+public:
+    Staging() = default;
+    Staging(const Staging&) = delete;
+    Staging& operator=(const Staging&) = delete;
+    ~Staging() { for (const Buf& b : bufs_) (void)hipFree(b.d); }
+
+    void* bytes(size_t n_bytes, const void* from = nullptr, void* to = nullptr) {
+        void* d = nullptr;
+        if (oom_ || hipMalloc(&d, n_bytes) != hipSuccess) {
+            oom_ = true;
+            return nullptr;
+        }
+        bufs_.push_back({d, from, to, n_bytes});
+        return d;
+    }
+    const float* in(const float* host, size_t count) { return static_cast<float*>(bytes(count * sizeof(float), host)); }
+    // a null `host` is an output nobody asked for: nothing is allocated
+    float* out(float* host, size_t count) {
+        return host ? static_cast<float*>(bytes(count * sizeof(float), nullptr, host)) : nullptr;
+    }
+    float* inout(float* host, size_t count) { return static_cast<float*>(bytes(count * sizeof(float), host, host)); }
+    bool oom() const { return oom_; }
+    hipError_t upload() const { return copy(true); }
+    hipError_t download() const { return copy(false); }
 };
+
+int fail_oom(const std::string& who) {
+    (void)hipGetLastError();
+    return fail(PRT_ERR_OOM, who + ": device allocation failed");
+}
 
 bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
 
-// shape and parameter checks shared by both entry points; fills `p`
-int check_args(const char* fn, int device, int W, int H, int iterations, const float* params4, prt_dn::Params* p) {
-    const std::string who(fn);
+// device ordinal and frame shape, shared by every entry point
+int check_frame(const std::string& who, int device, int W, int H) {
     if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
     if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
     if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
         return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
+    return PRT_OK;
+}
+
+int check_iterations(const std::string& who, int iterations) {
     if (iterations < 0 || iterations > prt_dn::kMaxIterations)
         return fail(PRT_ERR_ARG, who + ": iterations must be in 0.." + std::to_string(prt_dn::kMaxIterations));
+    return PRT_OK;
+}
+
+// shape and parameter checks of the fixed filter's entry points; fills `p`
+int check_args(const std::string& who, int device, int W, int H, int iterations, const float* params4,
+               prt_dn::Params* p) {
+    DN_TRY(check_frame(who, device, W, H));
+    DN_TRY(check_iterations(who, iterations));
     if (!params4) return fail(PRT_ERR_ARG, who + ": params4 is NULL");
     p->sigma_c = params4[0];
     p->sigma_z = params4[1];
@@ -86,15 +151,10 @@ int check_args(const char* fn, int device, int W, int H, int iterations, const f
 }
 
 // check_args for the variance-guided entry points (params5 = sigma_l, sigma_z, eps_a, eps_z, eps_l)
-int check_var_args(const char* fn, int device, int W, int H, int iterations, const float* params5,
+int check_var_args(const std::string& who, int device, int W, int H, int iterations, const float* params5,
                    prt_dn::VarParams* p) {
-    const std::string who(fn);
-    if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
-    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
-    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
-        return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
-    if (iterations < 0 || iterations > prt_dn::kMaxIterations)
-        return fail(PRT_ERR_ARG, who + ": iterations must be in 0.." + std::to_string(prt_dn::kMaxIterations));
+    DN_TRY(check_frame(who, device, W, H));
+    DN_TRY(check_iterations(who, iterations));
     if (!params5) return fail(PRT_ERR_ARG, who + ": params5 is NULL");
     p->sigma_l = params5[0];
     p->sigma_z = params5[1];
@@ -109,13 +169,9 @@ int check_var_args(const char* fn, int device, int W, int H, int iterations, con
 }
 
 // checks of the moments entry points; a frame_pitch of 0 (packed) is replaced by W * H * 3
-int check_moments_args(const char* fn, int device, int n_frames, int64_t* frame_pitch, float n_samples, float eps_a,
-                       int W, int H) {
-    const std::string who(fn);
-    if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
-    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
-    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
-        return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
+int check_moments_args(const std::string& who, int device, int n_frames, int64_t* frame_pitch, float n_samples,
+                       float eps_a, int W, int H) {
+    DN_TRY(check_frame(who, device, W, H));
     if (n_frames < 1) return fail(PRT_ERR_ARG, who + ": n_frames must be >= 1");
     const int64_t packed = (int64_t)W * (int64_t)H * 3;
     if (*frame_pitch == 0) *frame_pitch = packed;
@@ -125,6 +181,66 @@ int check_moments_args(const char* fn, int device, int n_frames, int64_t* frame_
     if (!std::isfinite(n_samples) || n_samples < 1.0f)
         return fail(PRT_ERR_ARG, who + ": n_samples must be finite and >= 1");
     if (!positive_finite(eps_a)) return fail(PRT_ERR_ARG, who + ": eps_a must be positive and finite");
+    return PRT_OK;
+}
+
+// a caller's scratch (not NULL: the entry point has looked) against `need`, the value of `need_fn`(W, H)
+int check_scratch(const std::string& who, const void* d_work, int64_t work_bytes, size_t need, const char* need_fn) {
+    if (work_bytes < (int64_t)need)
+        return fail(PRT_ERR_ARG, who + ": d_work is smaller than " + need_fn + "(W, H)");
+    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0) return fail(PRT_ERR_ARG, who + ": d_work must be 16-byte aligned");
+    return PRT_OK;
+}
+
+// aliasing rules of the device entry points; d_out_var and d_in_var may be null
+int check_aliasing(const std::string& who, const float* d_color, const float* d_feat, const float* d_out,
+                   const float* d_out_var, const float* d_in_var) {
+    if (d_out == d_color) return fail(PRT_ERR_ARG, who + ": d_out must not alias d_color");
+    if (d_out_var && (d_out_var == d_out || d_out_var == d_color || d_out_var == d_feat))
+        return fail(PRT_ERR_ARG, who + ": d_out_var must not alias d_out, d_color or d_feat");
+    if (d_in_var && (d_in_var == d_out || d_in_var == d_out_var))
+        return fail(PRT_ERR_ARG, who + ": d_in_var must not alias d_out or d_out_var");
+    return PRT_OK;
+}
+
+// prt_denoise_var_device and, with `given` (d_in_var is then required), prt_denoise_var_given_device
+int var_device(const std::string& who, bool given, int device, const float* d_color, const float* d_feat,
+               const float* d_in_var, int W, int H, int iterations, const float* params5, float* d_out,
+               float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
+    prt_dn::VarParams p;
+    if (!d_color || !d_feat || (given && !d_in_var) || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
+    DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::var_work_bytes(W, H), "prt_denoise_var_work_bytes"));
+    DN_TRY(check_aliasing(who, d_color, d_feat, d_out, d_out_var, d_in_var));
+    DN_TRY(check_device(who, device));
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
+                                   static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+// prt_denoise_var and, with `given` (in_var is then required), prt_denoise_var_given
+int var_host(const std::string& who, bool given, int device, const float* color, const float* feat, const float* in_var,
+             int W, int H, int iterations, const float* params5, float* out, float* out_var) {
+    prt_dn::VarParams p;
+    if (!color || !feat || (given && !in_var) || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
+    DN_TRY(check_device(who, device));
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    const size_t n = (size_t)W * (size_t)H;
+    Staging s;
+    const float* d_color = s.in(color, n * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    const float* d_in_var = given ? s.in(in_var, n) : nullptr;
+    float* d_out = s.out(out, n * 3);
+    float* d_out_var = s.out(out_var, n);
+    void* d_work = s.bytes(prt_dn::var_work_bytes(W, H));
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, nullptr));
+    DN_HIP_TRY(s.download());
     return PRT_OK;
 }
 
@@ -141,18 +257,13 @@ int64_t prt_denoise_work_bytes(int W, int H) {
 
 int prt_denoise_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
                        const float* params4, float* d_out, void* d_work, int64_t work_bytes, void* stream) {
+    const std::string who("prt_denoise_device");
     prt_dn::Params p;
-    if (!d_color || !d_feat || !d_out || !d_work)
-        return fail(PRT_ERR_ARG, "prt_denoise_device: NULL pointer");
-    int rc = check_args("prt_denoise_device", device, W, H, iterations, params4, &p);
-    if (rc != PRT_OK) return rc;
-    if (work_bytes < (int64_t)prt_dn::work_bytes(W, H))
-        return fail(PRT_ERR_ARG, "prt_denoise_device: d_work is smaller than prt_denoise_work_bytes(W, H)");
-    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0)
-        return fail(PRT_ERR_ARG, "prt_denoise_device: d_work must be 16-byte aligned");
-    if (d_out == d_color) return fail(PRT_ERR_ARG, "prt_denoise_device: d_out must not alias d_color");
-    rc = check_device("prt_denoise_device", device);
-    if (rc != PRT_OK) return rc;
+    if (!d_color || !d_feat || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_args(who, device, W, H, iterations, params4, &p));
+    DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::work_bytes(W, H), "prt_denoise_work_bytes"));
+    DN_TRY(check_aliasing(who, d_color, d_feat, d_out, nullptr, nullptr));
+    DN_TRY(check_device(who, device));
     DeviceGuard g(device);
     DN_HIP_TRY(g.err);
     DN_HIP_TRY(prt_dn::enqueue(d_color, d_feat, W, H, iterations, p, d_out, d_work, static_cast<hipStream_t>(stream)));
@@ -161,27 +272,23 @@ int prt_denoise_device(int device, const float* d_color, const float* d_feat, in
 
 int prt_denoise(int device, const float* color, const float* feat, int W, int H, int iterations,
                 const float* params4, float* out) {
+    const std::string who("prt_denoise");
     prt_dn::Params p;
-    if (!color || !feat || !out) return fail(PRT_ERR_ARG, "prt_denoise: NULL pointer");
-    int rc = check_args("prt_denoise", device, W, H, iterations, params4, &p);
-    if (rc != PRT_OK) return rc;
-    rc = check_device("prt_denoise", device);
-    if (rc != PRT_OK) return rc;
+    if (!color || !feat || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_args(who, device, W, H, iterations, params4, &p));
+    DN_TRY(check_device(who, device));
     DeviceGuard g(device);
     DN_HIP_TRY(g.err);
     const size_t n = (size_t)W * (size_t)H;
-    DevMem d_color, d_feat, d_out, d_work;
-    if (hipMalloc(&d_color.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&d_out.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_work.p, prt_dn::work_bytes(W, H)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PRT_ERR_OOM, "prt_denoise: device allocation failed");
-    }
-    DN_HIP_TRY(hipMemcpy(d_color.p, color, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(prt_dn::enqueue(static_cast<const float*>(d_color.p), static_cast<const float*>(d_feat.p), W, H, iterations,
-                               p, static_cast<float*>(d_out.p), d_work.p, nullptr));
-    // the copy on the null stream follows the kernels and blocks until it is done
-    DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    Staging s;
+    const float* d_color = s.in(color, n * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    float* d_out = s.out(out, n * 3);
+    void* d_work = s.bytes(prt_dn::work_bytes(W, H));
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(prt_dn::enqueue(d_color, d_feat, W, H, iterations, p, d_out, d_work, nullptr));
+    DN_HIP_TRY(s.download());
     return PRT_OK;
 }
 
@@ -193,54 +300,13 @@ int64_t prt_denoise_var_work_bytes(int W, int H) {
 int prt_denoise_var_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
                            const float* params5, float* d_out, float* d_out_var, void* d_work, int64_t work_bytes,
                            void* stream) {
-    prt_dn::VarParams p;
-    if (!d_color || !d_feat || !d_out || !d_work)
-        return fail(PRT_ERR_ARG, "prt_denoise_var_device: NULL pointer");
-    int rc = check_var_args("prt_denoise_var_device", device, W, H, iterations, params5, &p);
-    if (rc != PRT_OK) return rc;
-    if (work_bytes < (int64_t)prt_dn::var_work_bytes(W, H))
-        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_work is smaller than prt_denoise_var_work_bytes(W, H)");
-    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0)
-        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_work must be 16-byte aligned");
-    if (d_out == d_color) return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_out must not alias d_color");
-    if (d_out_var && (d_out_var == d_out || d_out_var == d_color || d_out_var == d_feat))
-        return fail(PRT_ERR_ARG, "prt_denoise_var_device: d_out_var must not alias d_out, d_color or d_feat");
-    rc = check_device("prt_denoise_var_device", device);
-    if (rc != PRT_OK) return rc;
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, W, H, iterations, p, d_out, d_out_var, d_work,
-                                   static_cast<hipStream_t>(stream)));
-    return PRT_OK;
+    return var_device("prt_denoise_var_device", false, device, d_color, d_feat, nullptr, W, H, iterations, params5,
+                      d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var(int device, const float* color, const float* feat, int W, int H, int iterations,
                     const float* params5, float* out, float* out_var) {
-    prt_dn::VarParams p;
-    if (!color || !feat || !out) return fail(PRT_ERR_ARG, "prt_denoise_var: NULL pointer");
-    int rc = check_var_args("prt_denoise_var", device, W, H, iterations, params5, &p);
-    if (rc != PRT_OK) return rc;
-    rc = check_device("prt_denoise_var", device);
-    if (rc != PRT_OK) return rc;
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    const size_t n = (size_t)W * (size_t)H;
-    DevMem d_color, d_feat, d_out, d_var, d_work;
-    if (hipMalloc(&d_color.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&d_out.p, n * 3 * sizeof(float)) != hipSuccess || (out_var && hipMalloc(&d_var.p, n * sizeof(float)) != hipSuccess) ||
-        hipMalloc(&d_work.p, prt_dn::var_work_bytes(W, H)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PRT_ERR_OOM, "prt_denoise_var: device allocation failed");
-    }
-    DN_HIP_TRY(hipMemcpy(d_color.p, color, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(prt_dn::enqueue_var(static_cast<const float*>(d_color.p), static_cast<const float*>(d_feat.p), W, H,
-                                   iterations, p, static_cast<float*>(d_out.p), static_cast<float*>(d_var.p), d_work.p,
-                                   nullptr));
-    // the copies on the null stream follow the kernels and block until they are done
-    DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_var) DN_HIP_TRY(hipMemcpy(out_var, d_var.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return PRT_OK;
+    return var_host("prt_denoise_var", false, device, color, feat, nullptr, W, H, iterations, params5, out, out_var);
 }
 
 // ---- variance from per-pixel sample moments ----
@@ -248,71 +314,24 @@ int prt_denoise_var(int device, const float* color, const float* feat, int W, in
 int prt_denoise_var_given_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
-    const char* fn = "prt_denoise_var_given_device";
-    const std::string who(fn);
-    prt_dn::VarParams p;
-    if (!d_color || !d_feat || !d_in_var || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    int rc = check_var_args(fn, device, W, H, iterations, params5, &p);
-    if (rc != PRT_OK) return rc;
-    if (work_bytes < (int64_t)prt_dn::var_work_bytes(W, H))
-        return fail(PRT_ERR_ARG, who + ": d_work is smaller than prt_denoise_var_work_bytes(W, H)");
-    if (reinterpret_cast<uintptr_t>(d_work) % 16 != 0) return fail(PRT_ERR_ARG, who + ": d_work must be 16-byte aligned");
-    if (d_out == d_color) return fail(PRT_ERR_ARG, who + ": d_out must not alias d_color");
-    if (d_out_var && (d_out_var == d_out || d_out_var == d_color || d_out_var == d_feat))
-        return fail(PRT_ERR_ARG, who + ": d_out_var must not alias d_out, d_color or d_feat");
-    if (d_in_var == d_out || d_in_var == d_out_var)
-        return fail(PRT_ERR_ARG, who + ": d_in_var must not alias d_out or d_out_var");
-    rc = check_device(fn, device);
-    if (rc != PRT_OK) return rc;
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    DN_HIP_TRY(prt_dn::enqueue_var_given(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
-                                         static_cast<hipStream_t>(stream)));
-    return PRT_OK;
+    return var_device("prt_denoise_var_given_device", true, device, d_color, d_feat, d_in_var, W, H, iterations,
+                      params5, d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var_given(int device, const float* color, const float* feat, const float* in_var, int W, int H,
                           int iterations, const float* params5, float* out, float* out_var) {
-    const char* fn = "prt_denoise_var_given";
-    prt_dn::VarParams p;
-    if (!color || !feat || !in_var || !out) return fail(PRT_ERR_ARG, std::string(fn) + ": NULL pointer");
-    int rc = check_var_args(fn, device, W, H, iterations, params5, &p);
-    if (rc != PRT_OK) return rc;
-    rc = check_device(fn, device);
-    if (rc != PRT_OK) return rc;
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    const size_t n = (size_t)W * (size_t)H;
-    DevMem d_color, d_feat, d_in, d_out, d_var, d_work;
-    if (hipMalloc(&d_color.p, n * 3 * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&d_in.p, n * sizeof(float)) != hipSuccess || hipMalloc(&d_out.p, n * 3 * sizeof(float)) != hipSuccess ||
-        (out_var && hipMalloc(&d_var.p, n * sizeof(float)) != hipSuccess) ||
-        hipMalloc(&d_work.p, prt_dn::var_work_bytes(W, H)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PRT_ERR_OOM, std::string(fn) + ": device allocation failed");
-    }
-    DN_HIP_TRY(hipMemcpy(d_color.p, color, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_in.p, in_var, n * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(prt_dn::enqueue_var_given(static_cast<const float*>(d_color.p), static_cast<const float*>(d_feat.p),
-                                         static_cast<const float*>(d_in.p), W, H, iterations, p,
-                                         static_cast<float*>(d_out.p), static_cast<float*>(d_var.p), d_work.p, nullptr));
-    // the copies on the null stream follow the kernels and block until they are done
-    DN_HIP_TRY(hipMemcpy(out, d_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    if (out_var) DN_HIP_TRY(hipMemcpy(out_var, d_var.p, n * sizeof(float), hipMemcpyDeviceToHost));
-    return PRT_OK;
+    return var_host("prt_denoise_var_given", true, device, color, feat, in_var, W, H, iterations, params5, out,
+                    out_var);
 }
 
 int prt_moments_add_device(int device, const float* d_sums, int n_frames, int64_t frame_pitch, float n_samples,
                            const float* d_feat, float eps_a, int W, int H, float* d_io_state, void* stream) {
-    const char* fn = "prt_moments_add_device";
-    if (!d_sums || !d_feat || !d_io_state) return fail(PRT_ERR_ARG, std::string(fn) + ": NULL pointer");
-    int rc = check_moments_args(fn, device, n_frames, &frame_pitch, n_samples, eps_a, W, H);
-    if (rc != PRT_OK) return rc;
+    const std::string who("prt_moments_add_device");
+    if (!d_sums || !d_feat || !d_io_state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_moments_args(who, device, n_frames, &frame_pitch, n_samples, eps_a, W, H));
     if (reinterpret_cast<uintptr_t>(d_io_state) % 16 != 0)
-        return fail(PRT_ERR_ARG, std::string(fn) + ": d_io_state must be 16-byte aligned");
-    rc = check_device(fn, device);
-    if (rc != PRT_OK) return rc;
+        return fail(PRT_ERR_ARG, who + ": d_io_state must be 16-byte aligned");
+    DN_TRY(check_device(who, device));
     DeviceGuard g(device);
     DN_HIP_TRY(g.err);
     DN_HIP_TRY(prt_dn::enqueue_moments(d_sums, n_frames, (size_t)frame_pitch, n_samples, d_feat, eps_a, W, H, d_io_state,
@@ -322,31 +341,23 @@ int prt_moments_add_device(int device, const float* d_sums, int n_frames, int64_
 
 int prt_moments_add(int device, const float* sums, int n_frames, int64_t frame_pitch, float n_samples,
                     const float* feat, float eps_a, int W, int H, float* io_state) {
-    const char* fn = "prt_moments_add";
-    if (!sums || !feat || !io_state) return fail(PRT_ERR_ARG, std::string(fn) + ": NULL pointer");
-    int rc = check_moments_args(fn, device, n_frames, &frame_pitch, n_samples, eps_a, W, H);
-    if (rc != PRT_OK) return rc;
-    rc = check_device(fn, device);
-    if (rc != PRT_OK) return rc;
+    const std::string who("prt_moments_add");
+    if (!sums || !feat || !io_state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_moments_args(who, device, n_frames, &frame_pitch, n_samples, eps_a, W, H));
+    DN_TRY(check_device(who, device));
     DeviceGuard g(device);
     DN_HIP_TRY(g.err);
     const size_t n = (size_t)W * (size_t)H;
+    Staging s;
     // the frames as they lie in the caller's memory, gaps of a pitch included
-    const size_t span = (size_t)(n_frames - 1) * (size_t)frame_pitch + n * 3;
-    DevMem d_sums, d_feat, d_state;
-    if (hipMalloc(&d_sums.p, span * sizeof(float)) != hipSuccess || hipMalloc(&d_feat.p, n * 8 * sizeof(float)) != hipSuccess ||
-        hipMalloc(&d_state.p, n * 4 * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(PRT_ERR_OOM, std::string(fn) + ": device allocation failed");
-    }
-    DN_HIP_TRY(hipMemcpy(d_sums.p, sums, span * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_feat.p, feat, n * 8 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(hipMemcpy(d_state.p, io_state, n * 4 * sizeof(float), hipMemcpyHostToDevice));
-    DN_HIP_TRY(prt_dn::enqueue_moments(static_cast<const float*>(d_sums.p), n_frames, (size_t)frame_pitch, n_samples,
-                                       static_cast<const float*>(d_feat.p), eps_a, W, H, static_cast<float*>(d_state.p),
+    const float* d_sums = s.in(sums, (size_t)(n_frames - 1) * (size_t)frame_pitch + n * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    float* d_state = s.inout(io_state, n * 4);
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(prt_dn::enqueue_moments(d_sums, n_frames, (size_t)frame_pitch, n_samples, d_feat, eps_a, W, H, d_state,
                                        nullptr));
-    // the copy on the null stream follows the kernel and blocks until it is done
-    DN_HIP_TRY(hipMemcpy(io_state, d_state.p, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    DN_HIP_TRY(s.download());
     return PRT_OK;
 }
 

@@ -103,6 +103,22 @@ def features(scene, camera, *, resolution=None, samples=1, seed=0, device=0, til
                            samples=samples, seed=seed, tile=tile)
 
 
+def _frame_and_features(mean, feat):
+    """`mean` (W, H, 3) and `feat` (W, H, 8) as C-contiguous float32 arrays, and W, H."""
+    mean = np.ascontiguousarray(mean, np.float32)
+    feat = np.ascontiguousarray(feat, np.float32)
+    if mean.ndim != 3 or mean.shape[2] != 3:
+        raise ValueError(f"mean must be (W, H, 3), not {mean.shape}")
+    if feat.shape != mean.shape[:2] + (FEATURE_CHANNELS,):
+        raise ValueError(f"feat must be {mean.shape[:2] + (FEATURE_CHANNELS,)}, not {feat.shape}")
+    return mean, feat, mean.shape[0], mean.shape[1]
+
+
+def _vp(address):
+    """A device address as a ctypes pointer; None or 0 is NULL."""
+    return ctypes.c_void_p(address) if address else None
+
+
 def _params(sigma_c, sigma_z, eps_a, eps_z):
     return np.array([sigma_c, sigma_z, eps_a, eps_z], np.float32)
 
@@ -116,13 +132,7 @@ def denoise(mean, feat, *, iterations=ITERATIONS, sigma_c=SIGMA_C, sigma_z=SIGMA
     edge-stopping width relative to the local depth gradient; eps_a: albedo floor of the
     demodulation; eps_z: depth floor.  Pixels without a first hit, and pixels whose colour or
     features are not finite, are returned unchanged."""
-    mean = np.ascontiguousarray(mean, np.float32)
-    feat = np.ascontiguousarray(feat, np.float32)
-    if mean.ndim != 3 or mean.shape[2] != 3:
-        raise ValueError(f"mean must be (W, H, 3), not {mean.shape}")
-    if feat.shape != mean.shape[:2] + (FEATURE_CHANNELS,):
-        raise ValueError(f"feat must be {mean.shape[:2] + (FEATURE_CHANNELS,)}, not {feat.shape}")
-    W, H = mean.shape[:2]
+    mean, feat, W, H = _frame_and_features(mean, feat)
     out = np.zeros_like(mean)
     par = _params(sigma_c, sigma_z, eps_a, eps_z)
     N.check_denoise(N.lib().prt_denoise(int(device), N.ptr(mean), N.ptr(feat), W, H, int(iterations), N.ptr(par),
@@ -140,10 +150,9 @@ def denoise_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_
     """prt_denoise_device: the same filter on device pointers (e.g. torch tensors' data_ptr()),
     enqueued on `stream_ptr` (a hipStream_t; None = the null stream) without a host synchronisation."""
     par = _params(sigma_c, sigma_z, eps_a, eps_z)
-    vp = ctypes.c_void_p
-    N.check_denoise(N.lib().prt_denoise_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
-                                               int(iterations), N.ptr(par), vp(d_out_ptr), vp(d_work_ptr),
-                                               int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))
+    N.check_denoise(N.lib().prt_denoise_device(int(device), _vp(d_color_ptr), _vp(d_feat_ptr), int(W), int(H),
+                                               int(iterations), N.ptr(par), _vp(d_out_ptr), _vp(d_work_ptr),
+                                               int(n_work_bytes), _vp(stream_ptr)))
 
 
 # ---- variance-guided mode (prt_denoise_var; DESIGN.md §11) ----
@@ -173,25 +182,18 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
     channel 3 of a moments state (moments_add), is used in its place (prt_denoise_var_given): at a pixel
     that is filtered a finite value >= 0 is taken as it is, anything else counts as 0.  The variance
     returned with return_variance=True is then the one actually used."""
-    mean = np.ascontiguousarray(mean, np.float32)
-    feat = np.ascontiguousarray(feat, np.float32)
-    if mean.ndim != 3 or mean.shape[2] != 3:
-        raise ValueError(f"mean must be (W, H, 3), not {mean.shape}")
-    if feat.shape != mean.shape[:2] + (FEATURE_CHANNELS,):
-        raise ValueError(f"feat must be {mean.shape[:2] + (FEATURE_CHANNELS,)}, not {feat.shape}")
-    W, H = mean.shape[:2]
+    mean, feat, W, H = _frame_and_features(mean, feat)
     out = np.zeros_like(mean)
     var = np.zeros((W, H), np.float32) if return_variance else None
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
+    fn, given = N.lib().prt_denoise_var, []
     if variance is not None:
-        given = np.ascontiguousarray(variance, np.float32)
-        if given.shape != (W, H):
-            raise ValueError(f"variance must be {(W, H)}, not {given.shape}")
-        N.check_denoise(N.lib().prt_denoise_var_given(int(device), N.ptr(mean), N.ptr(feat), N.ptr(given), W, H,
-                                                      int(iterations), N.ptr(par), N.ptr(out), N.ptr(var)))
-        return (out, var) if return_variance else out
-    N.check_denoise(N.lib().prt_denoise_var(int(device), N.ptr(mean), N.ptr(feat), W, H, int(iterations), N.ptr(par),
-                                            N.ptr(out), N.ptr(var)))
+        plane = np.ascontiguousarray(variance, np.float32)
+        if plane.shape != (W, H):
+            raise ValueError(f"variance must be {(W, H)}, not {plane.shape}")
+        fn, given = N.lib().prt_denoise_var_given, [N.ptr(plane)]
+    N.check_denoise(fn(int(device), N.ptr(mean), N.ptr(feat), *given, W, H, int(iterations), N.ptr(par), N.ptr(out),
+                       N.ptr(var)))
     return (out, var) if return_variance else out
 
 
@@ -208,17 +210,12 @@ def denoise_variance_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr
     `d_in_var_ptr` (W x H floats, optional) is denoise_variance's `variance` (prt_denoise_var_given_device,
     same scratch); it must not alias the output or `d_out_var_ptr`."""
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
-    vp = ctypes.c_void_p
+    fn, given = N.lib().prt_denoise_var_device, []
     if d_in_var_ptr:
-        N.check_denoise(N.lib().prt_denoise_var_given_device(
-            int(device), vp(d_color_ptr), vp(d_feat_ptr), vp(d_in_var_ptr), int(W), int(H), int(iterations), N.ptr(par),
-            vp(d_out_ptr), vp(d_out_var_ptr) if d_out_var_ptr else None, vp(d_work_ptr), int(n_work_bytes),
-            vp(stream_ptr) if stream_ptr else None))
-        return
-    N.check_denoise(N.lib().prt_denoise_var_device(int(device), vp(d_color_ptr), vp(d_feat_ptr), int(W), int(H),
-                                                   int(iterations), N.ptr(par), vp(d_out_ptr),
-                                                   vp(d_out_var_ptr) if d_out_var_ptr else None, vp(d_work_ptr),
-                                                   int(n_work_bytes), vp(stream_ptr) if stream_ptr else None))
+        fn, given = N.lib().prt_denoise_var_given_device, [_vp(d_in_var_ptr)]
+    N.check_denoise(fn(int(device), _vp(d_color_ptr), _vp(d_feat_ptr), *given, int(W), int(H), int(iterations),
+                       N.ptr(par), _vp(d_out_ptr), _vp(d_out_var_ptr), _vp(d_work_ptr), int(n_work_bytes),
+                       _vp(stream_ptr)))
 
 
 # ---- variance from per-pixel sample moments (prt_moments_add, prt_denoise_var_given; DESIGN.md §11) ----
@@ -262,7 +259,6 @@ def moments_add_device(d_sums_ptr, n_frames, n_samples, d_feat_ptr, W, H, d_stat
     """prt_moments_add_device: moments_add on device pointers, enqueued on `stream_ptr` without a host
     synchronisation.  Frame f starts at d_sums_ptr + f * frame_pitch floats (0 = packed); the state
     (W x H x 4 floats, 16-byte aligned) is updated in place."""
-    vp = ctypes.c_void_p
-    N.check_denoise(N.lib().prt_moments_add_device(int(device), vp(d_sums_ptr), int(n_frames), int(frame_pitch),
-                                                   float(n_samples), vp(d_feat_ptr), float(eps_a), int(W), int(H),
-                                                   vp(d_state_ptr), vp(stream_ptr) if stream_ptr else None))
+    N.check_denoise(N.lib().prt_moments_add_device(int(device), _vp(d_sums_ptr), int(n_frames), int(frame_pitch),
+                                                   float(n_samples), _vp(d_feat_ptr), float(eps_a), int(W), int(H),
+                                                   _vp(d_state_ptr), _vp(stream_ptr)))

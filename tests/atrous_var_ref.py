@@ -1,5 +1,5 @@
 """NumPy float32 restatement of the variance-guided a-trous mode (prt_denoise_var,
-pyrenderer_amd/csrc/prt_denoise.hip: var_estimate_kernel and var_atrous_kernel).
+pyrenderer_amd/csrc/prt_denoise.hip: var_estimate_kernel and pass_kernel<true>).
 
 A helper module like atrous_ref.py, whose pre-pass, post-pass, e(x) and tap windows it shares.
 `atrous_var(color, feat, iterations, sigma_l, sigma_z, eps_a, eps_z, eps_l)` returns what

@@ -227,6 +227,42 @@ def test_device_entry_points_on_a_side_stream(restated_moments, restated_given):
     assert np.array_equal(_bits(d_out.cpu().numpy()), _bits(want_img)) and (d_var.cpu().numpy() == -1.0).all()
 
 
+def test_modes_alternating_on_one_scratch_leave_nothing_behind(restated_given):
+    """The modes share their launch and scratch code: given variance, fixed, spatial estimate and fixed again
+    on one NaN-filled scratch and one stream, with no host synchronisation in between.  A plane that one
+    mode left behind and the next one read would show in the bits."""
+    import torch
+    from pyrenderer_amd import denoise as D
+    fixed_par = dict(sigma_c=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3)   # test_gpu_denoise.py's
+    W, H = 70, 130
+    C, F, iv, _, wants = restated_given[(W, H)]
+    want_given = wants[5][0]
+    want_fixed = R.atrous(C, F, 5, **fixed_par)
+    want_spatial = V.atrous_var(C, F, 5, **PAR)[0]
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(dev)
+    d_c, d_f, d_iv = (torch.from_numpy(a).to(dev) for a in (C, F, iv))
+    need_var, need_fixed = D.work_bytes_variance(W, H), D.work_bytes(W, H)
+    assert need_fixed < need_var
+    d_work = torch.full((need_var,), 0xFF, dtype=torch.uint8, device=dev)
+    assert d_work.data_ptr() % 16 == 0
+    outs = [torch.zeros((W, H, 3), dtype=torch.float32, device=dev) for _ in range(4)]
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[0].data_ptr(), d_work.data_ptr(), need_var,
+                              d_in_var_ptr=d_iv.data_ptr(), iterations=5, stream_ptr=stream.cuda_stream, **PAR)
+    D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[1].data_ptr(), d_work.data_ptr(), need_fixed,
+                     iterations=5, stream_ptr=stream.cuda_stream, **fixed_par)
+    D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[2].data_ptr(), d_work.data_ptr(), need_var,
+                              iterations=5, stream_ptr=stream.cuda_stream, **PAR)
+    D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[3].data_ptr(), d_work.data_ptr(), need_fixed,
+                     iterations=5, stream_ptr=stream.cuda_stream, **fixed_par)
+    stream.synchronize()
+    for name, got, want in zip(("given", "fixed", "spatial", "fixed again"), outs,
+                               (want_given, want_fixed, want_spatial, want_fixed)):
+        diff = np.argwhere(np.any(_bits(got.cpu().numpy()) != _bits(want), axis=-1))
+        assert len(diff) == 0, (name, len(diff), diff[:5])
+
+
 # -------------------------------------------------------------- end to end ----
 
 def test_render_and_accumulator_agree_end_to_end(cornell, tmp_path):

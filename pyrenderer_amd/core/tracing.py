@@ -54,20 +54,11 @@ class PathTracer:
 
     def render_sums(self, cam_packed, spp, seed=0, devices=(0,), tile=64, flags=0):
         """Per-pixel radiance SUMS over spp samples, (W, H, 3) [x][y]."""
-        W, H = self.img_w, self.img_h
-        devices = tuple(devices)
-        if len(devices) > 1:
-            return render_multi([self.world.device_scene(d) for d in devices], cam_packed, W, H, tile, spp,
-                                self.depth, seed, flags)
-        ds = self.world.device_scene(devices[0])
-        ids = interleaved_tiles(W, H, tile)
-        sums, _ = ds.render_tiles(cam_packed, W, H, tile, tile, ids, spp, self.depth, seed, flags)
-        return unpack_tiles(sums, W, H, tile, tile, ids)
+        return _Frame(self.world, cam_packed, self.img_w, self.img_h, depth=self.depth, seed=seed, devices=devices,
+                      tile=tile, flags=flags).sums(spp)
 
     def render(self, cam_packed, spp, seed=0, devices=(0,), tile=64, nee="reference"):
-        if spp <= 0:
-            return np.zeros((self.img_w, self.img_h, 3), np.float32)
-        return self.render_sums(cam_packed, spp, seed, devices, tile, nee_flags(nee)) / np.float32(spp)
+        return _mean(self.render_sums(cam_packed, spp, seed, devices, tile, nee_flags(nee)), spp)
 
 
 def nee_flags(nee):
@@ -90,7 +81,8 @@ def build_world(scene, devices=(0,)):
 
 
 def _check_variance_batches(variance_batches, spp, denoise, devices):
-    """render()'s rules for variance_batches; returns K (0 = off)."""
+    """The rules for variance_batches, render()'s and the command line's; returns K (0 = off).  spp None:
+    the caller's own passes are the batches (progressive rendering), K only switches the moments on."""
     if isinstance(variance_batches, (bool, np.bool_)) or not isinstance(variance_batches, (int, np.integer)):
         raise ValueError(f"variance_batches must be an integer, not {variance_batches!r}")
     K = int(variance_batches)
@@ -100,17 +92,93 @@ def _check_variance_batches(variance_batches, spp, denoise, devices):
         raise ValueError(f"variance_batches must be 0 or >= 2, not {K}")
     if not (isinstance(denoise, str) and denoise == "variance"):
         raise ValueError("variance_batches is a variance source of denoise='variance'")
-    if spp < K or spp % K:
+    if spp is not None and (spp < K or spp % K):
         raise ValueError(f"spp ({spp}) must be a positive multiple of variance_batches ({K})")
     if len(tuple(devices)) != 1:
         raise ValueError("variance_batches renders on one device (prt_render_multi has no first-sample argument)")
     return K
 
 
-def _render_batch(ds, cam, W, H, tile, ids, first_sample, spp, depth, seed, flags):
-    """Slot sums of samples first_sample .. first_sample + spp - 1, rendered from zero sums."""
-    slots = np.zeros((ids.shape[0] * tile * tile, 3), np.float32)
-    return ds.render_tiles_accumulate(cam, W, H, tile, tile, ids, first_sample, spp, depth, slots, seed, flags)
+def _mean(sums, spp):
+    """pixels / samples (main_taichi.py:61-64, before the sqrt tone map); zeros without samples."""
+    return sums / np.float32(spp) if spp > 0 else np.zeros_like(sums)
+
+
+class _Frame:
+    """What every entry point sets up once and the steps they share: the frame size, the world, the packed
+    camera, the tile ids, the estimator flags and the devices.  The first of `devices` serves batches,
+    features and the filter; all of them serve sums()."""
+
+    def __init__(self, world, cam, W, H, *, depth, seed=0, devices=(0,), tile=64, flags=0):
+        self.world, self.cam, self.W, self.H = world, cam, int(W), int(H)
+        self.depth, self.seed, self.tile, self.flags = int(depth), int(seed), int(tile), flags
+        self.devices = tuple(devices)
+        self.device = self.devices[0]
+        self.ids = interleaved_tiles(self.W, self.H, self.tile)
+        self._feat = None
+
+    @classmethod
+    def of(cls, scene, camera, *, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None, nee="reference"):
+        """The frame of a scene and a camera; the world is built only if none is given."""
+        W, H = resolution if resolution is not None else camera.resolution
+        return cls(world or build_world(scene, devices), camera.convert_to_taichi_camera().packed(), W, H,
+                   depth=depth, seed=seed, devices=devices, tile=tile, flags=nee_flags(nee))
+
+    @property
+    def ds(self):
+        return self.world.device_scene(self.device)
+
+    def zero_slots(self):
+        return np.zeros((self.ids.shape[0] * self.tile * self.tile, 3), np.float32)
+
+    def unpack(self, slots, frame=None):
+        return unpack_tiles(slots, self.W, self.H, self.tile, self.tile, self.ids, frame)
+
+    def sums(self, spp):
+        """Radiance sums (W, H, 3) over samples 0 .. spp - 1, added in sample order on the device(s);
+        zeros, without a render, for spp <= 0."""
+        W, H, t = self.W, self.H, self.tile
+        if spp <= 0:
+            return np.zeros((W, H, 3), np.float32)
+        if len(self.devices) > 1:
+            return render_multi([self.world.device_scene(d) for d in self.devices], self.cam, W, H, t, spp,
+                                self.depth, self.seed, self.flags)
+        slots, _ = self.ds.render_tiles(self.cam, W, H, t, t, self.ids, spp, self.depth, self.seed, self.flags)
+        return self.unpack(slots)
+
+    def add_samples(self, first_sample, spp, onto=None):
+        """Samples first_sample .. first_sample + spp - 1 added in sample order onto the slot sums `onto`
+        (modified in place and returned); by default onto zero sums, which makes them one batch."""
+        t, slots = self.tile, self.zero_slots() if onto is None else onto
+        return self.ds.render_tiles_accumulate(self.cam, self.W, self.H, t, t, self.ids, first_sample, spp,
+                                               self.depth, slots, self.seed, self.flags)
+
+    def batches(self, spp, K):
+        """render_batches(): (sums, feat, state) of spp samples as K batches of spp / K."""
+        from .. import denoise as D
+        n = spp // K
+        feat = self.features()
+        frames = np.zeros((K, self.W, self.H, 3), np.float32)
+        total = self.zero_slots()
+        for j in range(K):
+            batch = self.add_samples(j * n, n)
+            total += batch
+            self.unpack(batch, frames[j])
+        state = D.moments_add(D.moments_state(self.W, self.H), frames, n, feat, device=self.device)
+        return self.unpack(total), feat, state
+
+    def features(self):
+        """One-sample first-hit features of the frame's camera, seed and resolution, composed once and kept."""
+        if self._feat is None:
+            from .. import denoise as D
+            self._feat = D.features_packed(self.ds, self.cam, self.W, self.H, samples=1, seed=self.seed,
+                                           tile=self.tile)
+        return self._feat
+
+    def filter(self, mean, mode="fixed", **params):
+        """`mean` filtered by pyrenderer_amd.denoise.filtered in `mode`, guided by features()."""
+        from .. import denoise as D
+        return D.filtered(mean, self.features(), mode, device=self.device, **params)
 
 
 def render_batches(scene, camera, *, spp, depth, variance_batches, seed=0, resolution=None, device=0, tile=64,
@@ -120,25 +188,11 @@ def render_batches(scene, camera, *, spp, depth, variance_batches, seed=0, resol
     rendered from zero sums; `sums` adds the batch sums in batch order on the host, an association that
     differs in the last bits from render_sums()'s sample-order sum.  `feat` are the one-sample features
     render(denoise=...) uses and `state` is pyrenderer_amd.denoise.moments_add's over the K batches."""
-    from .. import denoise as D
     K = _check_variance_batches(variance_batches, spp, "variance", (device,))
     if K == 0:
         raise ValueError("variance_batches must be >= 2")
-    W, H = (int(v) for v in (resolution if resolution is not None else camera.resolution))
-    world = world or build_world(scene, (device,))
-    ds = world.device_scene(device)
-    cam = camera.convert_to_taichi_camera().packed()
-    ids = interleaved_tiles(W, H, tile)
-    n, flags = spp // K, nee_flags(nee)
-    feat = D.features_packed(ds, cam, W, H, samples=1, seed=seed, tile=tile)
-    frames = np.zeros((K, W, H, 3), np.float32)
-    total = np.zeros((ids.shape[0] * tile * tile, 3), np.float32)
-    for j in range(K):
-        batch = _render_batch(ds, cam, W, H, tile, ids, j * n, n, depth, seed, flags)
-        total += batch
-        unpack_tiles(batch, W, H, tile, tile, ids, frame=frames[j])
-    state = D.moments_add(D.moments_state(W, H), frames, n, feat, device=device)
-    return unpack_tiles(total, W, H, tile, tile, ids), feat, state
+    return _Frame.of(scene, camera, depth=depth, seed=seed, resolution=resolution, devices=(device,), tile=tile,
+                     world=world, nee=nee).batches(spp, K)
 
 
 def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None,
@@ -167,37 +221,23 @@ def render(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), 
     if not (isinstance(denoise, (bool, np.bool_)) or (isinstance(denoise, str) and denoise == "variance")):
         raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
     K = _check_variance_batches(variance_batches, spp, denoise, devices)
+    frame = _Frame.of(scene, camera, depth=depth, seed=seed, resolution=resolution, devices=devices, tile=tile,
+                      world=world, nee=nee)
     if K:
-        from .. import denoise as D
-        dev = tuple(devices)[0]
-        sums, feat, state = render_batches(scene, camera, spp=spp, depth=depth, variance_batches=K, seed=seed,
-                                           resolution=resolution, device=dev, tile=tile, world=world, nee=nee)
-        return D.denoise_variance(sums / np.float32(spp), feat, device=dev, variance=state[..., 3])
-    W, H = resolution if resolution is not None else camera.resolution
-    world = world or build_world(scene, devices)
-    tracer = PathTracer(world, depth, int(W), int(H))
-    cam = camera.convert_to_taichi_camera().packed()
-    mean = tracer.render(cam, spp, seed, devices, tile, nee)
+        sums, _, state = frame.batches(spp, K)
+        return frame.filter(_mean(sums, spp), "variance", variance=state[..., 3])
+    mean = _mean(frame.sums(spp), spp)
     if not denoise:
         return mean
-    from .. import denoise as D
-    dev = tuple(devices)[0]
-    feat = D.features_packed(world.device_scene(dev), cam, int(W), int(H), samples=1, seed=seed, tile=tile)
-    if denoise == "variance":
-        return D.denoise_variance(mean, feat, device=dev)
-    return D.denoise(mean, feat, device=dev)
+    return frame.filter(mean, "variance" if isinstance(denoise, str) else "fixed")
 
 
 def render_sums(scene, camera, *, spp, depth, seed=0, resolution=None, devices=(0,), tile=64, world=None,
                 nee="reference"):
     """Per-pixel radiance SUMS (W, H, 3) float32 [x][y] over spp samples — the reference's `pixels`
     field after spp render() passes (main_taichi.py:97); render() returns these / spp."""
-    W, H = resolution if resolution is not None else camera.resolution
-    world = world or build_world(scene, devices)
-    tracer = PathTracer(world, depth, int(W), int(H))
-    if spp <= 0:
-        return np.zeros((int(W), int(H), 3), np.float32)
-    return tracer.render_sums(camera.convert_to_taichi_camera().packed(), spp, seed, devices, tile, nee_flags(nee))
+    return _Frame.of(scene, camera, depth=depth, seed=seed, resolution=resolution, devices=devices, tile=tile,
+                     world=world, nee=nee).sums(spp)
 
 
 class Accumulator:
@@ -223,22 +263,20 @@ class Accumulator:
 
     def __init__(self, scene, camera, *, depth, seed=0, resolution=None, device=0, tile=64, world=None,
                  nee="reference", moments=False):
-        W, H = resolution if resolution is not None else camera.resolution
-        self.W, self.H, self.depth, self.seed, self.tile = int(W), int(H), int(depth), int(seed), int(tile)
-        self.device = device
-        self.world = world or build_world(scene, (device,))
-        self.cam = camera.convert_to_taichi_camera().packed()
-        self.ids = interleaved_tiles(self.W, self.H, self.tile)
-        self.slots = np.zeros((self.ids.shape[0] * self.tile * self.tile, 3), np.float32)
+        self.frame = _Frame.of(scene, camera, depth=depth, seed=seed, resolution=resolution, devices=(device,),
+                               tile=tile, world=world, nee=nee)
+        self.slots = self.frame.zero_slots()
         self.samples = 0
-        self.flags = nee_flags(nee)
         self.moments = bool(moments)
         self.batch_spp = 0        # moments: the spp of every batch, 0 before the first
         self.moments_state = None
-        self._feat = None
         if self.moments:
             from .. import denoise as D
-            self.moments_state = D.moments_state(self.W, self.H)
+            self.moments_state = D.moments_state(self.frame.W, self.frame.H)
+
+    @property
+    def world(self):
+        return self.frame.world
 
     @property
     def batches(self):
@@ -246,16 +284,8 @@ class Accumulator:
         return self.samples // self.batch_spp if self.batch_spp else 0
 
     def features(self):
-        """One-sample first-hit features of the accumulator's camera, seed and resolution; with
-        moments=True composed once and kept."""
-        from .. import denoise as D
-        if self._feat is not None:
-            return self._feat
-        feat = D.features_packed(self.world.device_scene(self.device), self.cam, self.W, self.H, samples=1,
-                                 seed=self.seed, tile=self.tile)
-        if self.moments:
-            self._feat = feat
-        return feat
+        """One-sample first-hit features of the accumulator's camera, seed and resolution (the frame's)."""
+        return self.frame.features()
 
     def _add_batch(self, spp):
         from .. import denoise as D
@@ -263,12 +293,9 @@ class Accumulator:
             return self
         if self.batch_spp and spp != self.batch_spp:
             raise ValueError(f"moments=True needs equal batches: add({spp}) after batches of {self.batch_spp} spp")
-        ds = self.world.device_scene(self.device)
-        batch = _render_batch(ds, self.cam, self.W, self.H, self.tile, self.ids, self.samples, spp, self.depth,
-                              self.seed, self.flags)
+        batch = self.frame.add_samples(self.samples, spp)
         self.slots += batch
-        frame = unpack_tiles(batch, self.W, self.H, self.tile, self.tile, self.ids)
-        D.moments_add(self.moments_state, frame, spp, self.features(), device=self.device)
+        D.moments_add(self.moments_state, self.frame.unpack(batch), spp, self.features(), device=self.frame.device)
         self.batch_spp = spp
         self.samples += spp
         return self
@@ -286,20 +313,16 @@ class Accumulator:
             raise ValueError("spp must be >= 0")
         if self.moments:
             return self._add_batch(int(spp))
-        ds = self.world.device_scene(self.device)
-        ds.render_tiles_accumulate(self.cam, self.W, self.H, self.tile, self.tile, self.ids, self.samples, spp,
-                                   self.depth, self.slots, self.seed, self.flags)
+        self.frame.add_samples(self.samples, spp, onto=self.slots)
         self.samples += spp
         return self
 
     def sums(self):
         """Per-pixel radiance sums (W, H, 3) [x][y] — the reference's `pixels` field."""
-        return unpack_tiles(self.slots, self.W, self.H, self.tile, self.tile, self.ids)
+        return self.frame.unpack(self.slots)
 
     def mean(self):
-        if self.samples == 0:
-            return np.zeros((self.W, self.H, 3), np.float32)
-        return self.sums() / np.float32(self.samples)
+        return _mean(self.sums(), self.samples)
 
     def denoised(self, mode="fixed", **params):
         """The running mean filtered by the a-trous denoiser (pyrenderer_amd.denoise.denoise; `params`
@@ -309,21 +332,16 @@ class Accumulator:
         moments=True and at least pyrenderer_amd.denoise.MIN_MOMENT_BATCHES batches it passes the moments
         state's variance of the mean as `variance` (what render(..., variance_batches=K) does); with
         fewer batches it leaves the filter its spatial estimate."""
-        from .. import denoise as D
-        if mode not in D.MODES:
-            raise ValueError(f"mode must be one of {D.MODES}, not {mode!r}")
-        feat = self.features()
-        if mode == "variance":
-            if self.moments and self.batches >= D.MIN_MOMENT_BATCHES and "variance" not in params:
-                params = dict(params, variance=self.moments_state[..., 3])
-            return D.denoise_variance(self.mean(), feat, device=self.device, **params)
-        return D.denoise(self.mean(), feat, device=self.device, **params)
+        from ..denoise import MIN_MOMENT_BATCHES
+        if mode == "variance" and self.moments and self.batches >= MIN_MOMENT_BATCHES:
+            params.setdefault("variance", self.moments_state[..., 3])   # one given by the caller wins
+        return self.frame.filter(self.mean(), mode, **params)
 
     def state(self):
-        d = dict(slots=self.slots, samples=np.int64(self.samples), seed=np.int64(self.seed),
-                 depth=np.int64(self.depth), resolution=np.array([self.W, self.H], np.int64),
-                 tile=np.int64(self.tile), flags=np.int64(self.flags), camera=self.cam,
-                 scene_sha=np.array(scene_fingerprint(self.world.flat)))
+        f = self.frame
+        d = dict(slots=self.slots, samples=np.int64(self.samples), seed=np.int64(f.seed), depth=np.int64(f.depth),
+                 resolution=np.array([f.W, f.H], np.int64), tile=np.int64(f.tile), flags=np.int64(f.flags),
+                 camera=f.cam, scene_sha=np.array(scene_fingerprint(f.world.flat)))
         if self.moments:
             d.update(moments=self.moments_state, batch_spp=np.int64(self.batch_spp))
         return d
@@ -347,7 +365,7 @@ class Accumulator:
                   moments="moments" in z.files)
         if z["slots"].shape != acc.slots.shape:
             raise ValueError("saved accumulation does not match the frame layout")
-        if "camera" in z.files and not np.array_equal(z["camera"], acc.cam):
+        if "camera" in z.files and not np.array_equal(z["camera"], acc.frame.cam):
             raise ValueError("saved accumulation was rendered with a different camera")
         if "scene_sha" in z.files and str(z["scene_sha"]) != scene_fingerprint(acc.world.flat):
             raise ValueError("saved accumulation was rendered from a different scene")

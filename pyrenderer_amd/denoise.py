@@ -9,7 +9,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .device_scene import interleaved_tiles
+from .device_scene import interleaved_tiles, unpack_tiles
 
 # defaults chosen by tools/denoise_sweep.py (profiles/denoise_sweep.txt): the lowest
 # geometric-mean RMSE ratio among the parameter sets that improve every frame of the sweep
@@ -34,20 +34,6 @@ def _slots_in_frame(W, H, tile, ids):
     x = (ids % tx)[:, None, None] * tile + np.arange(tile)[None, None, :]
     y = (ids // tx)[:, None, None] * tile + np.arange(tile)[None, :, None]
     return ((x < W) & (y < H)).reshape(-1)
-
-
-def _unpack_into(slots, frame, tile, tile_ids):
-    """device_scene.unpack_tiles for any channel count, into an existing [x][y] frame: (n_tiles * tile *
-    tile, C) slot rows (tile-major, then row ly, then column lx) -> frame (W, H, C)."""
-    W, H, C = frame.shape
-    tx = (W + tile - 1) // tile
-    s = slots.reshape(len(tile_ids), tile, tile, C)
-    for k, tid in enumerate(tile_ids):
-        x0 = (int(tid) % tx) * tile
-        y0 = (int(tid) // tx) * tile
-        w = min(tile, W - x0)
-        h = min(tile, H - y0)
-        frame[x0:x0 + w, y0:y0 + h] = s[k, :h, :w].transpose(1, 0, 2)
 
 
 def features_packed(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_rays=CHUNK_RAYS):
@@ -84,7 +70,7 @@ def features_packed(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_r
         acc[:, 0:6] /= n_f32
         acc[:, 6] /= np.maximum(hits_sum, np.float32(1.0))
         acc[:, 7] /= n_f32
-        _unpack_into(acc, feat, tile, gid)
+        unpack_tiles(acc, W, H, tile, tile, gid, feat)
     return feat
 
 
@@ -96,11 +82,9 @@ def features(scene, camera, *, resolution=None, samples=1, seed=0, device=0, til
     toward the ray; misses add 0), [6] depth (sum of t over the hitting samples / max(hits, 1)),
     [7] hit fraction (hits / samples).
     """
-    from .core.tracing import build_world
-    W, H = resolution if resolution is not None else camera.resolution
-    world = world or build_world(scene, (device,))
-    return features_packed(world.device_scene(device), camera.convert_to_taichi_camera().packed(), W, H,
-                           samples=samples, seed=seed, tile=tile)
+    from .core.tracing import _Frame
+    f = _Frame.of(scene, camera, depth=0, seed=seed, resolution=resolution, devices=(device,), tile=tile, world=world)
+    return features_packed(f.ds, f.cam, f.W, f.H, samples=samples, seed=seed, tile=tile)
 
 
 def _frame_and_features(mean, feat):
@@ -195,6 +179,20 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
     N.check_denoise(fn(int(device), N.ptr(mean), N.ptr(feat), *given, W, H, int(iterations), N.ptr(par), N.ptr(out),
                        N.ptr(var)))
     return (out, var) if return_variance else out
+
+
+def filtered(mean, feat, mode="fixed", *, variance=None, return_variance=False, **params):
+    """The one choice of filter: denoise() in mode "fixed", denoise_variance() in mode "variance" (with
+    `variance`, if given, in place of its spatial estimate); `params` are the filter's keyword parameters.
+    return_variance=True returns the pair (image, variance used), None for the fixed filter, which has none."""
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, not {mode!r}")
+    if mode == "variance":
+        return denoise_variance(mean, feat, variance=variance, return_variance=return_variance, **params)
+    if variance is not None:
+        raise TypeError("variance is a parameter of mode 'variance'")
+    out = denoise(mean, feat, **params)
+    return (out, None) if return_variance else out
 
 
 def work_bytes_variance(W, H):

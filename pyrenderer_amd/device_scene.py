@@ -54,11 +54,12 @@ def max_tiles_per_rank(W, H, tile, world, scheme="latin"):
 
 
 def unpack_tiles(slots, W, H, tw, th, tile_ids, frame=None):
-    """(n_tiles*tw*th, 3) slot sums → (W, H, 3) frame indexed [x][y] (main_taichi.py:25)."""
+    """(n_tiles*tw*th, C) slot rows → (W, H, C) frame indexed [x][y] (main_taichi.py:25): new, or `frame`."""
     tx = (W + tw - 1) // tw
+    C = np.shape(slots)[-1]
     if frame is None:
-        frame = np.zeros((W, H, 3), np.float32)
-    s = np.asarray(slots).reshape(len(tile_ids), th, tw, 3)
+        frame = np.zeros((W, H, C), np.float32)
+    s = np.asarray(slots).reshape(len(tile_ids), th, tw, C)
     for k, tid in enumerate(np.asarray(tile_ids)):
         x0 = (int(tid) % tx) * tw
         y0 = (int(tid) // tx) * th

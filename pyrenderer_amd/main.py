@@ -14,12 +14,14 @@ Every sample runs through libprt's HIP path (core.tracing.render / Accumulator);
 no CPU fallback.
 """
 import argparse
+import functools
 import os
 import time
 
 import numpy as np
 
-from .core.tracing import Accumulator, as_image, build_world, render_batches, render_sums
+from . import denoise as D
+from .core.tracing import Accumulator, _check_variance_batches, _Frame, _mean, as_image
 from .io_utils.read_tungsten import read_file
 from .tone_map import finish, reinhard_extended, save_hdr, to_uint8, write_png
 
@@ -70,22 +72,19 @@ def parse(argv=None):
         if not 0 <= args.denoise_iterations <= 8:
             ap.error(f"--denoise-iterations must be in 0..8, not {args.denoise_iterations}")
         args.denoise = True
-    K = args.variance_batches
-    if K:
-        if K < 2:
-            ap.error(f"--variance-batches must be 0 or >= 2, not {K}")
-        if not (args.denoise and args.denoise_mode == "variance"):
-            ap.error("--variance-batches needs --denoise --denoise-mode variance")
-        if len(args.devices) != 1:
-            ap.error("--variance-batches renders on one device")
+    try:   # render()'s rules; with --interval every pass is a batch, whatever K is
+        _check_variance_batches(args.variance_batches, None if args.interval > 0 else args.samples,
+                                "variance" if args.denoise and args.denoise_mode == "variance" else args.denoise,
+                                args.devices)
+    except ValueError as e:
+        ap.error(f"--variance-batches: {e}")
+    if args.variance_batches:
         if args.interval > 0:
             if args.samples % args.interval:
                 ap.error(f"--variance-batches with --interval {args.interval} needs --samples to be a multiple of it "
                          f"(equal batches), not {args.samples}")
         elif args.state:
             ap.error("--variance-batches with --state needs --interval (every pass is a batch)")
-        elif args.samples < K or args.samples % K:
-            ap.error(f"--variance-batches {K} needs --samples to be a positive multiple of it, not {args.samples}")
     if args.hdr and args.hdr.lower().endswith(".npy"):
         # rounds <= 4 took a .npy FILE here; a directory named out.npy would silently replace it
         ap.error(f"--hdr takes a directory (hdr.npy and spp.npy are written into it), not a .npy file: {args.hdr}")
@@ -115,7 +114,6 @@ def main(argv=None):
     scene, camera = read_file(args.scene)
     W, H = args.resolution if args.resolution else camera.resolution
     t0 = time.perf_counter()
-    feat = given_var = None   # --variance-batches: the features it composed and the moments' variance plane
     if args.interval > 0 or args.state:
         if len(args.devices) != 1:
             raise SystemExit("progressive rendering (--interval/--state) runs on one device")
@@ -125,8 +123,8 @@ def main(argv=None):
             # the saved estimator settings win; refuse a command line that asks for others
             given = {"depth": args.depth, "seed": args.seed, "resolution": (W, H),
                      "nee": args.nee}
-            saved = {"depth": acc.depth, "seed": acc.seed, "resolution": (acc.W, acc.H),
-                     "nee": "mis" if acc.flags else "reference"}
+            saved = {"depth": acc.frame.depth, "seed": acc.frame.seed, "resolution": (acc.frame.W, acc.frame.H),
+                     "nee": "mis" if acc.frame.flags else "reference"}
             clash = [f"--{k} {given[k]} (saved: {saved[k]})" for k in given if given[k] != saved[k]]
             if clash:
                 raise SystemExit(f"{state} was rendered with other settings: " + ", ".join(clash))
@@ -139,6 +137,7 @@ def main(argv=None):
         else:
             acc = Accumulator(scene, camera, depth=args.depth, seed=args.seed, resolution=(W, H),
                               device=args.devices[0], nee=args.nee, moments=bool(args.variance_batches))
+        frame, W, H = acc.frame, acc.frame.W, acc.frame.H
         step = args.interval if args.interval > 0 else args.samples
         while acc.samples < args.samples:
             n = min(step, args.samples - acc.samples)
@@ -148,46 +147,25 @@ def main(argv=None):
             print(f"{n / dt:.2f} samples/s ({acc.samples} spp, {W * H * n / dt / 1e6:.1f} Msamples/s)", flush=True)
             if state:
                 acc.save(state)
-        sums, samples, mean = acc.sums(), acc.samples, acc.mean()
-        W, H = acc.W, acc.H
-        world, seed, tile = acc.world, acc.seed, acc.tile
-        if acc.moments:
-            from . import denoise as D
-            feat = acc.features()
-            if acc.batches >= D.MIN_MOMENT_BATCHES:
-                given_var = acc.moments_state[..., 3]
-    elif args.variance_batches:
-        world, seed, tile = build_world(scene, tuple(args.devices)), args.seed, 64
-        sums, feat, mstate = render_batches(scene, camera, spp=args.samples, depth=args.depth,
-                                            variance_batches=args.variance_batches, seed=args.seed, resolution=(W, H),
-                                            device=args.devices[0], nee=args.nee, world=world)
-        samples, given_var = args.samples, mstate[..., 3]
-        # render(..., variance_batches=K)'s unfiltered mean, bit for bit
-        mean = sums / np.float32(samples)
+        sums, samples, mean, denoised = acc.sums(), acc.samples, acc.mean(), acc.denoised
     else:
-        world, seed, tile = build_world(scene, tuple(args.devices)), args.seed, 64
-        sums = render_sums(scene, camera, spp=args.samples, depth=args.depth, seed=args.seed, resolution=(W, H),
-                           devices=tuple(args.devices), nee=args.nee, world=world)
-        samples = max(args.samples, 0)
-        # render()'s mean, bit for bit: pixels / samples (main_taichi.py:61-64)
-        mean = sums / np.float32(samples) if samples else np.zeros_like(sums)
-    if args.denoise or args.aov:
-        from . import denoise as D
-        dev = args.devices[0]
-        if feat is None:
-            feat = D.features_packed(world.device_scene(dev), camera.convert_to_taichi_camera().packed(), W, H,
-                                     samples=1, seed=seed, tile=tile)
-        if args.aov:
-            write_aov(args.aov, feat)
-        if args.denoise:
-            it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
-            if args.denoise_mode == "variance":
-                mean, var = D.denoise_variance(mean, feat, iterations=it, device=dev, return_variance=True,
-                                               variance=given_var)
-                if args.aov:
-                    np.save(os.path.join(args.aov, "variance.npy"), var)
-            else:
-                mean = D.denoise(mean, feat, iterations=it, device=dev)
+        frame = _Frame.of(scene, camera, depth=args.depth, seed=args.seed, resolution=(W, H),
+                          devices=tuple(args.devices), nee=args.nee)
+        samples, variance = max(args.samples, 0), None
+        if args.variance_batches:
+            sums, _, mstate = frame.batches(samples, args.variance_batches)
+            variance = mstate[..., 3]
+        else:
+            sums = frame.sums(samples)
+        mean = _mean(sums, samples)
+        denoised = functools.partial(frame.filter, mean, variance=variance)
+    if args.aov:
+        write_aov(args.aov, frame.features())
+    if args.denoise:
+        it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
+        mean, var = denoised(args.denoise_mode, iterations=it, return_variance=True)
+        if args.aov and var is not None:
+            np.save(os.path.join(args.aov, "variance.npy"), var)
     dt = time.perf_counter() - t0
     _write(args, sums, samples, mean)
     print(f"{W}x{H} x {args.samples} spp, depth {args.depth}: {dt:.2f} s "

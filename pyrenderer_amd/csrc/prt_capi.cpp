@@ -128,6 +128,9 @@ struct Scene {
     int leaf_break = -1;             // env PRT_LEAF_BREAK (0..64); -1: per variant (trace launch)
     int leaf_exit = -1;              // env PRT_LEAF_EXIT (0..64); -1: per variant (trace launch)
     int resume_min = 32;             // resume variants (env PRT_RESUME_MIN; C4 after the r02 BVH fixes: 16 / 24 / 32 / 40 / 48 -> 19.4 / 19.1 / 19.0 / 19.4 / 19.8 ms)
+    int pool_resume_min = 12;        // pooled kernel's extension-tail suspension (env PRT_POOL_RESUME_MIN, 0..64; 0: off;
+                                     // C2 one-frame launches at 0 / 8 / 12 / 16 / 24: 3.89 / 3.62 / 3.61 / 3.61 / 3.63 ms,
+                                     // profiles/r07/pool_resume/)
     uint32_t guard_trips = 1u << 20; // traversal phases per query before the watchdog trips (env PRT_GUARD_TRIPS)
     int spill_lds = 16;              // LDS part of the spill variants' stack (env PRT_SPILL_LDS: 4, 16 or 32)
     std::string wave_clock_path;     // env PRT_WAVE_CLOCK: append each trace launch's per-wave clocks here
@@ -323,6 +326,7 @@ void scene_params(Scene* s, prt::TraceParams& P) {
     P.n_light = s->n_light;
     P.dl_r = s->direct_rgb[0]; P.dl_g = s->direct_rgb[1]; P.dl_b = s->direct_rgb[2];
     P.resume_min = s->resume_min;
+    P.pool_resume_min = s->pool_resume_min;
     P.stats = (unsigned long long*)s->stats.p;
     scene_sizes(s, P);
     P.guard_trips = s->guard_trips;
@@ -378,6 +382,10 @@ int trace_setup(Scene* s, RenderCtx* cx, uint32_t flags, int64_t n_items, prt::T
     P.leaf_exit = s->leaf_exit >= 0 ? s->leaf_exit : (lds_var ? 8 : 24);
     int& occ = s->occ[2 * var + (stats ? 1 : 0)];
     if (occ == 0) occ = std::max(1, prt::trace_blocks_per_cu(stack, var, stats, prt::trace_smem_bytes(stack, var, P)));
+    // suspended extension tails pay only while finished lanes can be refilled: a launch with at most one
+    // item per resident lane runs without them (a wave learns that the queue is empty only at its first
+    // refill with an idle lane; C1's one-frame launches 0.096 vs 0.083 ms with the threshold left on)
+    if (n_items <= (int64_t)occ * s->cus * 256) P.pool_resume_min = 0;
     if (spill) {
         // entries [spill_lds, need4] of every lane of the largest grid, plus one slot of headroom
         size_t per_lane = (size_t)std::max(1, s->need4 + 2 - s->spill_lds);
@@ -801,6 +809,7 @@ int prt_scene_create(int device, const float* tri_v, const float* tri_n, const i
         if (const char* gt = std::getenv("PRT_GUARD_TRIPS"))
             s->guard_trips = (uint32_t)std::max(1LL, std::min((long long)UINT32_MAX, std::atoll(gt)));
         if (const char* rm = std::getenv("PRT_RESUME_MIN")) s->resume_min = std::max(1, std::min(64, std::atoi(rm)));
+        if (const char* pr = std::getenv("PRT_POOL_RESUME_MIN")) s->pool_resume_min = std::max(0, std::min(64, std::atoi(pr)));
         if (const char* sl = std::getenv("PRT_SPILL_LDS")) {
             int v = std::atoi(sl);
             s->spill_lds = v == 4 ? 4 : v == 32 ? 32 : 16;

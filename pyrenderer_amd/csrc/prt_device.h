@@ -1639,8 +1639,8 @@ __device__ __forceinline__ void copy_octant_nodes(float4* __restrict__ sn, const
 //      then shades it; a lane whose NEE sample needs a visibility test writes the shadow ray
 //      (o = p, d = w, t_max = t_at_light) to its slot of the block's LDS pool and its thread id
 //      to the block's shadow queue;
-//   S: (after a barrier) the queue's n rays are traversed by the first ceil(n / 64) waves, 64
-//      per wave — whichever wave issued them — and each lane writes the any-hit result to the
+//   S: (after a barrier) the queue's n rays are traversed by the first waves to claim them, one per
+//      free lane (64 per wave) — whichever wave issued them — and each lane writes the any-hit result to the
 //      owner's slot; the other waves are idle (their SIMD slots go to other blocks' waves);
 //   R: (after a second barrier) each owner adds its pending NEE radiance if unoccluded and moves
 //      on to its next bounce.
@@ -1668,10 +1668,19 @@ constexpr int kCtlF4 = 3;                      // ctl: 12 words
 // the answers resolved in between).  A lane's S answer is resolved in the NEXT iteration, after
 // its next extension traversal (which does not depend on it) and before it shades that hit, so
 // the reference's order of additions holds and images stay bit-identical.  A wave with a pending
-// shadow ray waits only until the previous S phase's chunks are answered (an LDS counter, normally
-// done by then); S waves run beside the other waves' next traversals, and waves without a chunk go
+// shadow ray waits only until the previous S phase's entries are answered (an LDS counter, normally
+// done by then); S waves run beside the other waves' next traversals, and waves without a claim go
 // straight on to their refill (C2 4.049 vs 4.080 ms, C3 at 1024^2 x 32 spp 9.455 vs 9.570 ms per
 // launch against the two-barrier kernel, profiles/r04/pool1b/).
+// Suspended extension tails (round 7, P.pool_resume_min): a wave's extension traversal lasted as long
+// as its longest query (7.4 node and 9.6 triangle trips for queries of 3.2 visits and 3.3 tests).  The
+// wave now leaves it once at most pool_resume_min lanes are still traversing; those lanes park their
+// traversal state in rows 3..5 of their pool slot, skip shading, keep their item and resume in the next
+// iteration, while the finished lanes shade and are refilled.  A suspended lane's LDS stack holds its
+// query, so it answers no pooled shadow ray: the S phase hands the queue to the waves' free lanes and
+// counts answered entries (every enqueuing lane is free, so the free lanes cover the queue).  Which
+// lane finishes when changes no query's result: images stay bit-identical.  C2 3.79 -> 3.61 ms per
+// one-frame launch at 12 lanes (profiles/r07/pool_resume/).
 // PLAIN: the lean build for scenes without spheres and metal / dielectric materials (P.plain; C1, C2,
 // C5): without that code the kernel's loop keeps 17 fewer uniform values in spilled SGPRs and is a
 // third shorter
@@ -1719,11 +1728,15 @@ void trace_kernel_pool(TraceParams P) {
     int item = -1;
     int bounce = 0;
     bool my_sh = false;      // this lane waits for the result of its pooled shadow ray
+    // this lane's extension query was suspended (P.pool_resume_min): its traversal state is parked in rows
+    // 3..5 of its pool slot and its LDS stack holds the query's entries, so it takes no S work
+    bool susp = false;
     uint32_t st = 0;
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0), wi = v3(0, 0, 0);
     V3 beta = v3(1, 1, 1), L = v3(0, 0, 0), pend = v3(0, 0, 0);
     Counters cn = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t n_e = 0, n_s = 0, lanes_s = 0, pre_hits = 0;
+    uint64_t n_susp = 0, n_res = 0;   // STATS (diag words 176, 177): queries suspended, queries resumed
     // STATS lane table (diag words 160..175, tools/lane_table.py): (wave trips, lane trips) of E inner
     // visits, E triangle tests, S inner visits, S triangle tests, the shading block, the Lambert
     // block, the loop iteration (lanes busy after the refill) and the resolve of shadow answers
@@ -1739,9 +1752,9 @@ void trace_kernel_pool(TraceParams P) {
         lt[k] += w; lt[k + 1] += l;
     };
     uint32_t chunk_s = 0, chunk_xy0 = 0;
-    // control words (kCtlF4): queue length [0..2], alive [3..5], chunk claims [6..8], S chunks done
-    // [9..11], one triple entry per iteration mod 3 (a slot is reset two iterations after its use)
-    uint32_t slot = 0, slot_prev = 0, nch_prev = 0;
+    // control words (kCtlF4): queue length [0..2], alive [3..5], queue entries claimed [6..8], entries
+    // answered [9..11], one triple entry per iteration mod 3 (a slot is reset two iterations after its use)
+    uint32_t slot = 0, slot_prev = 0, nq_prev = 0;
     // the queue's buffer (2 x 256 entries) alternates with the iteration's parity: entries enqueued in
     // iteration i are read in i's S phase, and the next enqueue into the
     // same buffer (iteration i + 2) comes after barrier i + 1, which every reader has passed
@@ -1831,18 +1844,37 @@ void trace_kernel_pool(TraceParams P) {
         if (STATS && item >= 0) book(12);
         // (a) extension traversal: every busy lane except one whose pending shadow ray ends its path
         const bool trav = item >= 0 && !(my_sh && bounce + 1 >= Q.depth);
+        // The wave leaves the traversal once at most pool_resume_min lanes are still traversing (RES,
+        // traverse_ww4; 0: never, 64: after every round that leaves a lane unfinished): those lanes keep their query (ts, their LDS stack, the same (o, d)) and resume it
+        // in the next iteration, the finished ones shade and are refilled.  Off once the work queue is
+        // exhausted: suspending pays only while finished lanes can be refilled.
         int hid = -1;
         float ht = 0.0f;
-        bool hit = false;
+        bool hit = false, done = false;
+        TState ts = {0, 0, 0, 0, 0.0f};
         if (__ballot(trav) != 0) {
             if (STATS && lane == __builtin_amdgcn_readfirstlane(lane)) n_e++;
             if (trav) {
-                if (STATS) { cn.ext++; cn.q0 = cn.nodes; }
-                hit = traverse_ww4<STATS, 1, Stk, false, false, true>(
-                    g_nodes, g_tris, o, d, kTMin, kTMax, false, stk, hid, ht, cn, nullptr, 0, Q.fault,
-                    exhausted ? 0 : Q.leaf_break, exhausted ? 0 : Q.leaf_exit, Q.guard_trips);
-                if (STATS) { cn.max_q = max(cn.max_q, cn.nodes - cn.q0); book_trav(0); }
-                if (!PLAIN && Q.n_sph > 0) {
+                if (susp) {
+                    const uint32_t cl = __float_as_uint(pool[3 * kBlock + tid]), sb = __float_as_uint(pool[4 * kBlock + tid]);
+                    ts.cur = (int)(short)(cl & 0xFFFFu); ts.leaf = (int)cl >> 16;
+                    ts.sp = (int)(sb & 0xFFFFu); ts.best_id = (int)sb >> 16;
+                    ts.best = pool[5 * kBlock + tid];
+                    if (STATS) n_res++;
+                } else {
+                    tstate_init(ts, stk, kTMax);
+                    if (STATS) { cn.ext++; cn.q0 = cn.nodes; }
+                }
+                done = traverse_ww4<STATS, 1, Stk, false, true, true>(
+                    g_nodes, g_tris, o, d, kTMin, kTMax, false, stk, hid, ht, cn, &ts, exhausted ? 0 : Q.pool_resume_min + 1,
+                    Q.fault, exhausted ? 0 : Q.leaf_break, exhausted ? 0 : Q.leaf_exit, Q.guard_trips);
+                hit = done && hid >= 0;
+                if (STATS) {
+                    if (done) cn.max_q = max(cn.max_q, cn.nodes - cn.q0);
+                    book_trav(0);
+                }
+                // spheres once, against the completed query's closest triangle
+                if (!PLAIN && done && Q.n_sph > 0) {
                     float best = hit ? ht : kTMax;
                     for (int k = 0; k < Q.n_sph; ++k) {
                         float root;
@@ -1858,7 +1890,7 @@ void trace_kernel_pool(TraceParams P) {
         }
         PRT_CLOCK(5);
         // (b) the previous S phase's answers (its waves ran it beside this wave's traversal): a wave
-        // with a pending shadow ray waits until every chunk of the previous queue has been answered
+        // with a pending shadow ray waits until every entry of the previous queue has been answered
         if (__ballot(my_sh) != 0) {
             // bounded: a wait that never ends (a logic error) raises the watchdog flag instead of
             // hanging the device: 2^20 sleeps of 64 clocks ~ 30 ms, against a worst case of ~0.1 ms for
@@ -1867,7 +1899,7 @@ void trace_kernel_pool(TraceParams P) {
             // did not arrive ends with NaN radiance (counted by STATS' non-finite samples), so a tripped
             // wait cannot pass for a valid image even before prt_check_faults reports it.
             bool late = false;
-            const uint32_t need = nch_prev;
+            const uint32_t need = nq_prev;
             for (uint32_t spin = 0;
                  need && __hip_atomic_load(&ctl[9 + slot_prev], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need;
                  ++spin) {
@@ -1893,8 +1925,19 @@ void trace_kernel_pool(TraceParams P) {
                 }
             }
         }
-        // (c) shading of this iteration's extension hits
-        if (trav) {
+        // A suspended query parks its state in rows 3..5 of its lane's pool slot (free after (b): the lane
+        // enqueues no shadow ray, and the previous S phase has read the one it had), so the state holds no
+        // registers across shading and the S phase: cur | leaf << 16, sp | best_id << 16 (16-bit references
+        // and LDS addresses, lds_fits4), best.  The lane skips (c) and keeps its item.
+        susp = trav && !done;
+        if (susp) {
+            pool[3 * kBlock + tid] = __uint_as_float(((uint32_t)ts.cur & 0xFFFFu) | ((uint32_t)ts.leaf << 16));
+            pool[4 * kBlock + tid] = __uint_as_float(((uint32_t)ts.sp & 0xFFFFu) | ((uint32_t)ts.best_id << 16));
+            pool[5 * kBlock + tid] = ts.best;
+            if (STATS) n_susp++;
+        }
+        // (c) shading of this iteration's completed extension queries
+        if (trav && done) {
             if (STATS) book(8);
             {
                 bool finished = false;
@@ -2052,25 +2095,28 @@ void trace_kernel_pool(TraceParams P) {
         PRT_CLOCK(1);
         // ------------------------------------------------------------------ S phase
         const uint32_t n_q = ctl[slot];
-        // the queue's rays in ceil(n / 64) chunks, one to each of the first waves to claim one (<= 4
-        // chunks, one claim per wave); the others refill the lanes that finished in E meanwhile,
-        // off the critical path
-        const uint32_t n_chunks = (n_q + 63u) >> 6;
-        uint32_t chunk = 0xFFFFFFFFu;
-        if (n_chunks) {
-            if (lane == 0) chunk = atomicAdd(&ctl[6 + slot], 1u);
-            chunk = __builtin_amdgcn_readfirstlane(chunk);
+        // the queue's rays go to the free lanes (those holding no suspended query: an S traversal uses
+        // the lane's own stack) of the first waves to claim some, one claim per wave of as many
+        // entries as it has free lanes; the others refill the lanes that finished in E meanwhile, off
+        // the critical path.  Every enqueuing lane is free, so the block's free lanes cover the queue.
+        // Without suspended lanes these are the 64-ray chunks of the earlier kernel and one partial
+        // (equal-size chunks: C2 +0.5 %, C3 +0.8 %; the arrival-ordered claim with an early refill by
+        // the first two waves at barrier 1: C2 +1.2 %, C3 +0.9 %; profiles/r03/pool/)
+        const uint64_t free_m = __ballot(!susp);
+        const uint32_t n_free = (uint32_t)__popcll(free_m);
+        uint32_t e0 = 0xFFFFFFFFu;
+        if (n_q && n_free) {
+            if (lane == 0) e0 = atomicAdd(&ctl[6 + slot], n_free);
+            e0 = __builtin_amdgcn_readfirstlane(e0);
         }
-        if (chunk < n_chunks) {
+        if (e0 < n_q) {
             // the S waves hold up their whole block at barrier 2: issue priority over other blocks
             __builtin_amdgcn_s_setprio(PRT_POOL_S_PRIO);
-            // full 64-ray chunks and one partial (equal-size chunks: C2 +0.5 %, C3 +0.8 %; the
-            // arrival-ordered claim with an early refill by the first two waves at barrier 1: C2
-            // +1.2 %, C3 +0.9 %; profiles/r03/pool/)
-            const uint32_t e0 = chunk * 64u, e1 = min(n_q, e0 + 64u);
-            const uint32_t e = e0 + (uint32_t)lane;
+            const uint32_t e1 = min(n_q, e0 + n_free);
+            const uint32_t e = e0 + __builtin_amdgcn_mbcnt_hi((uint32_t)(free_m >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)free_m, 0u));
             if (STATS && lane == 0) { n_s++; lanes_s += e1 - e0; }
-            const bool sq = e < e1;
+            const bool sq = !susp && e < e1;
             int owner = 0;
             V3 so = v3(0, 0, 0), sd = v3(1, 1, 1);
             float stm = 0.0f;
@@ -2098,11 +2144,11 @@ void trace_kernel_pool(TraceParams P) {
                 pool[6 * kBlock + owner] = hit ? __int_as_float(0x7FC00000) : 0.0f;
             }
             __builtin_amdgcn_s_setprio(0);
-            // publish the answers (LDS stores above) before counting the chunk as done
+            // publish the answers (LDS stores above) before counting the entries as answered
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            if (lane == 0) __hip_atomic_fetch_add(&ctl[9 + slot], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (lane == 0) __hip_atomic_fetch_add(&ctl[9 + slot], e1 - e0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
-        nch_prev = n_chunks;
+        nq_prev = n_q;
         PRT_CLOCK(2);
         const bool alive = ctl[3 + slot] != 0u;
         slot_prev = slot;
@@ -2141,6 +2187,11 @@ void trace_kernel_pool(TraceParams P) {
             uint64_t v = lt[k];
             for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
             if (lane == 0 && v) atomicAdd(P.stats + 160 + k, (unsigned long long)v);
+        }
+        for (int off = 32; off > 0; off >>= 1) { n_susp += __shfl_down(n_susp, off); n_res += __shfl_down(n_res, off); }
+        if (lane == 0 && n_susp) {
+            atomicAdd(P.stats + 176, (unsigned long long)n_susp);
+            atomicAdd(P.stats + 177, (unsigned long long)n_res);
         }
         uint32_t msp = cn.max_sp, nf = cn.nonfinite, mq = cn.max_q;
         for (int off = 32; off > 0; off >>= 1) {

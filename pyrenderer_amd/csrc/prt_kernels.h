@@ -62,6 +62,8 @@ struct TraceParams {
     int plain;                // 1: no spheres and no metal / dielectric material (the pool kernel's lean build)
     int shade_fast;           // 1: every material's rho in [2^-40, 2^40] and every face normal's length in
                               // [0.5, 2] (host-checked): the shading quotients' cheap guards (prt_device.h)
+    int pool_resume_min;      // pool kernel: leave the extension traversal once at most this many lanes still traverse and
+                              // resume the unfinished queries in the next iteration (0: off; env PRT_POOL_RESUME_MIN)
 };
 
 // trace kernel variants (selectable at run time through PRT_FLAG_VARIANT).  All run the

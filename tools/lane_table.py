@@ -10,7 +10,8 @@ The STATS build of trace_kernel_pool books, for each phase, the wave-level trips
     iteration          one loop iteration (lanes holding a path after the refill)
     resolve            lanes resolving a pooled shadow answer
 
-lanes = lane trips / (64 x wave trips).  With --clocks <lib built with -D PRT_POOL_CLOCKS>, the
+lanes = lane trips / (64 x wave trips).  Words 176 / 177 count the extension queries suspended and
+resumed (env PRT_POOL_RESUME_MIN, -1 in the output: the scene default).  With --clocks <lib built with -D PRT_POOL_CLOCKS>, the
 wave-cycle split of the same render (tools/pool_clocks.py's phases) is added.  One process, one
 full frame of the chosen config (default: config 2, variant 7 = trace_kernel_pool).
 
@@ -78,6 +79,11 @@ def main():
            "ext_queries_per_sample": round(float(w[2]) / samples, 4),
            "shadow_rays_per_sample": round(float(w[3]) / samples, 4),
            "answered_by_light_test_per_sample": round(float(w[20]) / samples, 4),
+           # suspended extension tails (PRT_POOL_RESUME_MIN, diag words 176 / 177): a query counts once
+           # per suspension; every suspended query is resumed in the wave's next iteration
+           "pool_resume_min": int(os.environ.get("PRT_POOL_RESUME_MIN", "-1")),
+           "suspensions_per_ext_query": round(float(w[176]) / max(float(w[2]), 1.0), 4),
+           "resumes_per_ext_query": round(float(w[177]) / max(float(w[2]), 1.0), 4),
            "lane_table": table}
     if a.clocks:
         from tools.ab_builds import load

@@ -23,7 +23,10 @@ TRACE_INST = "prt_trace_inst.hip"
 # stacks: 4 (the spill test's LDS part), 10 / 16 (LDS-resident scenes, the global scene's LDS
 # part), 32 (deeper LDS-resident BVHs, PRT_SPILL_LDS=32)
 TRACE_SETS = [(s, t) for s in (4, 10, 16, 32) for t in (0, 1)]
-HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_device.h"]
+# prt_device.h is the umbrella over the device code's headers by role (math, traversal, shared shading,
+# the two trace kernels, the variant table)
+HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_device.h", "prt_math.h", "prt_traverse.h", "prt_shade.h",
+           "prt_trace.h", "prt_pool.h", "prt_variants.h"]
 # the denoiser: units of their own, compiled with the same FLAGS and linked into
 # libprt.so.  They include none of HEADERS and nothing above includes theirs, so they cannot change
 # the trace kernels' code: they are dependencies of the build (_stale) but NOT part of kernel_sha(),

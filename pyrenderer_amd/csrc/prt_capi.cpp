@@ -778,7 +778,7 @@ int prt_scene_create(int device, const float* tri_v, const float* tri_n, const i
         s->plain = n_sph == 0;
         for (int32_t i = 0; i < n_mat; ++i)
             if (mat[8 * i + 5] == 2.0f || mat[8 * i + 5] == 3.0f) s->plain = false;   // metal / dielectric
-        // the shading quotients' cheap guards (prt_device.h lambert_div / nee_div) assume albedos and
+        // the shading quotients' cheap guards (prt_math.h lambert_div / nee_div) assume albedos and
         // emitters in [2^-40, 2^40] and face normals of length in [0.5, 2]; other scenes keep div3's guard
         s->shade_fast = true;
         for (int32_t i = 0; i < n_mat && s->shade_fast; ++i)

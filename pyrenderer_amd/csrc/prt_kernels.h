@@ -61,13 +61,13 @@ struct TraceParams {
     int lds_stack;            // pool kernel: 16-bit LDS traversal stack entries per lane (>= the BVH4's need)
     int plain;                // 1: no spheres and no metal / dielectric material (the pool kernel's lean build)
     int shade_fast;           // 1: every material's rho in [2^-40, 2^40] and every face normal's length in
-                              // [0.5, 2] (host-checked): the shading quotients' cheap guards (prt_device.h)
+                              // [0.5, 2] (host-checked): the shading quotients' cheap guards (prt_math.h)
     int pool_resume_min;      // pool kernel: leave the extension traversal once at most this many lanes still traverse and
                               // resume the unfinished queries in the next iteration (0: off; env PRT_POOL_RESUME_MIN)
 };
 
 // trace kernel variants (selectable at run time through PRT_FLAG_VARIANT).  All run the
-// while-while BVH4 traversal (prt_device.h traverse_ww4) and give bit-identical images;
+// while-while BVH4 traversal (prt_traverse.h traverse_ww4) and give bit-identical images;
 // the measured history of the variants this set replaced is in DESIGN.md §2.
 constexpr int kVarLds = 1;         // LDS-resident scene, phase-aligned ext/shadow iterations, >= 7 waves/SIMD
                                    // (72 VGPRs: C2 4.40 -> 4.23 ms against the 6-wave build)

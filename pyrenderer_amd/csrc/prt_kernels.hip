@@ -85,19 +85,7 @@ __global__ __launch_bounds__(kBlock) void hits_kernel(TraceParams P, const float
     float ht = 0.0f;
     bool hit = traverse_ww4<false, ANY ? 2 : 1, LdsStack, QN>(P.nodes, P.tris, o, d, a.w, b.w, ANY, stk, hid, ht, cn,
                                                               nullptr, 0, P.fault, 0, 0, P.guard_trips);
-    if (P.n_sph > 0 && !(ANY && hit)) {
-        float best = hit ? ht : b.w;
-        for (int k = 0; k < P.n_sph; ++k) {
-            float root;
-            if (sphere_hit(P.sph[k], o, d, a.w, best, root)) {
-                best = root;
-                hid = P.n_tri + k;
-                hit = true;
-                if (ANY) break;
-            }
-        }
-        ht = best;
-    }
+    sphere_hits(P, o, d, a.w, b.w, ANY, hit, hid, ht);
     hit_id[i] = hit ? hid : -1;
     hit_t[i] = hit ? ht : 0.0f;
 }
@@ -123,32 +111,14 @@ __global__ __launch_bounds__(kBlock) void hit_shade_kernel(TraceParams P, const 
     r[1] = b.w;   // closest_so_far: t_max on a miss
     if (hid >= 0) {
         const float t = hit_t[i];
-        const V3 p = o + d * t;
-        V3 ng;
-        int mid;
-        if (hid < P.n_tri) {
-            const float4 nm = P.tri_nm[hid];
-            ng = xyz(nm);
-            mid = __float_as_int(nm.w);
-        } else {
-            const float4 sc = P.sph[hid - P.n_tri];
-            ng = v3((p.x - sc.x) / sc.w, (p.y - sc.y) / sc.w, (p.z - sc.z) / sc.w);
-            mid = P.sph_mat[hid - P.n_tri];
-        }
-        const float* m = P.mats + 8 * mid;
-        const bool flip = m[4] == 0.0f && dot(ng, neg(d)) < 0.0f;
-        const V3 nn = flip ? neg(ng) : ng;
+        const Surface sf = hit_surface<false>(P, P.tri_nm, P.mats, o, d, t, hid);
+        const V3 p = sf.p, nn = sf.n;
+        const float* m = sf.m;
         uint32_t st = rng_key(P.seed_lo, P.seed_hi, (uint32_t)i, 0u);
         const float u0 = rng_next(st);
         const float u1 = rng_next(st);
         const V3 l = cosine_hemisphere<false>(u0, u1);
-        V3 wi;
-        if (hid < P.n_tri) {
-            const float4* fr = P.tri_frame + ((size_t)hid * 2 + (flip ? 1 : 0)) * 3;
-            wi = normalize(xyz(fr[0]) * l.x + xyz(fr[1]) * l.y + xyz(fr[2]) * l.z);
-        } else {
-            wi = to_world(nn, l);
-        }
+        const V3 wi = frame_dir<false, false>(P, frame_rows<false>(P, P.tri_frame, hid, sf.flip), hid, nn, l);
         const V3 vals[5] = {p, nn, v3(m[0], m[1], m[2]), wi, v3(0, 0, 0)};
         r[0] = 1.0f;
         r[1] = t;
@@ -240,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(const float* __restrict_
 // (collapse_bvh4's bound; scenes needing more than 32 take the spill-stack global variant)
 int stack_variant(int depth) { return depth + 1 <= 10 ? 10 : depth + 1 <= 16 ? 16 : 32; }
 
-// LDS-resident scene (prt_device.h trace_kernel): the BVH4 as 8 octant copies of 7 float4 per
+// LDS-resident scene (prt_trace.h trace_kernel): the BVH4 as 8 octant copies of 7 float4 per
 // node (n_node_f4 counts the 8 float4 of a global BVH4 node), triangles, shading data
 size_t lds_scene_bytes(const TraceParams& P) {
     return 16 * (7 * (size_t)P.n_node_f4 + P.n_tri_f4 + 7 * (size_t)P.n_tri + 2 * (size_t)P.n_mat + 4 * (size_t)P.n_lt) +
@@ -404,50 +374,13 @@ hipError_t launch_reduce(const float* buf, float* acc, int n_slots, int64_t j0, 
     return hipGetLastError();
 }
 
-bool variant_mis(int var) {
-    switch (var) {
-#define X(id, bits, lds, wpe) case id: return (bits & 256) != 0;
-        PRT_VARIANTS(X)
-#undef X
-        default: return false;
-    }
-}
-
-bool variant_quantized(int var) {
-    switch (var) {
-#define X(id, bits, lds, wpe) case id: return (bits & 64) != 0;
-        PRT_VARIANTS(X)
-#undef X
-        default: return false;
-    }
-}
-
-bool variant_spills(int var) {
-    switch (var) {
-#define X(id, bits, lds, wpe) case id: return (bits & 32) != 0;
-        PRT_VARIANTS(X)
-#undef X
-        default: return false;
-    }
-}
-
-bool variant_pool(int var) {
-    switch (var) {
-#define X(id, bits, lds, wpe) case id: return (bits & 512) != 0;
-        PRT_VARIANTS(X)
-#undef X
-        default: return false;
-    }
-}
-
-bool variant_uses_lds(int var) {
-    switch (var) {
-#define X(id, bits, lds, wpe) case id: return lds;
-        PRT_VARIANTS(X)
-#undef X
-        default: return false;
-    }
-}
+// look-ups in the variant table (prt_variants.h kVariants); unknown ids answer false
+bool variant_pool(int var) { const Variant* v = find_variant(var); return v && v->pool; }
+bool variant_mis(int var) { const Variant* v = find_variant(var); return v && v->mis; }
+bool variant_uses_lds(int var) { const Variant* v = find_variant(var); return v && v->lds; }
+// the global-scene trace kernels traverse quantised nodes with a spill stack
+bool variant_spills(int var) { const Variant* v = find_variant(var); return v && !v->lds; }
+bool variant_quantized(int var) { return variant_spills(var); }
 
 int trace_blocks_per_cu(int stack, int var, bool stats, size_t smem) {
     switch (stack) {

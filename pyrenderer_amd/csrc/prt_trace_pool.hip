@@ -1,4 +1,4 @@
-// prt_trace_pool.hip — the block-pooled shadow-query trace kernel (prt_device.h trace_kernel_pool)
+// prt_trace_pool.hip — the block-pooled shadow-query trace kernel (prt_pool.h trace_kernel_pool)
 // in its own compilation unit: pyrenderer_amd/build.py compiles it with LLVM's AMDGPU
 // register-pressure trackers (-mllvm --amdgpu-use-amdgpu-trackers), under which the kernel fits
 // the 72 VGPRs of 7 waves per SIMD with 3 spilled registers instead of 39 (the other trace

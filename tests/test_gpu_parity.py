@@ -524,6 +524,33 @@ def test_mis_variant_on_the_specular_scene():
     ds.close()
 
 
+@pytest.mark.parametrize("variant", [1, 3, 5, 7])
+def test_kernels_bit_identical_on_the_specular_scene(variant):
+    """Config 3's materials (analytic sphere, rough metal, dielectric) through each kernel that calls the
+    shared shading pieces (prt_shade.h): the phase-aligned LDS kernel (variant 1), the global-scene kernel
+    (3), the global-scene MIS kernel (5) and the pooled kernel's full build (7), each forced, bit for bit
+    the oracle's image (64 x 64, 4 spp, depth 8)."""
+    from pyrenderer_amd import _native as N
+    from pyrenderer_amd.device_scene import DeviceScene
+    scene, cam, flat = _specular_scene(0.35)
+    ds = DeviceScene(flat, 0)
+    osc = O.OracleScene.from_flat(flat)
+    c = cam.convert_to_taichi_camera().packed()
+    ids = np.arange(4, dtype=np.int32)
+    mis = variant in N.VAR_MIS
+    O.set_nee_mode(mis)
+    try:
+        o = osc.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, seed=13)
+    finally:
+        O.set_nee_mode(False)
+    flags = (variant << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
+    assert ds.kernel_info(n_items=64 * 64 * 4, flags=flags)["variant"] == variant
+    g, _ = ds.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, 13, flags)
+    assert np.isfinite(g).all() and g.sum() > 0
+    np.testing.assert_array_equal(g, o)
+    ds.close()
+
+
 def test_launch_size_selects_the_pooled_kernel(gpu_scene):
     """prt_launch_kernel: on the Cornell box every launch takes the block-pooled shadow kernel (round 6:
     config 1's 65 k items and an 8-rank shard of config 2 too, now that it is faster there than the

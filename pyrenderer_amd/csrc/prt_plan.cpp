@@ -1,0 +1,179 @@
+// prt_plan.cpp — see prt_plan.h.  Compiled with the library's flags (-ffp-contract=off): tri_frame and
+// the camera terms feed bit-exact shading, so their f32 operation order is part of the contract.
+#include "prt_plan.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+namespace prt {
+namespace {
+
+float bits_f(int32_t v) { float f; std::memcpy(&f, &v, 4); return f; }
+
+// rotate_to / rotate_z_to rows (mathematics/mat4_taichi.py:9-52) for a normal, in the kernel's f32
+// arithmetic: rows (x, z, v) with v = normalize(n), x = normalize(v x (0,1,0)), z = normalize(x x v).
+struct F3 { float x, y, z; };
+F3 f3_norm(F3 a) {
+    float l = std::sqrt(a.x * a.x + a.y * a.y + a.z * a.z);
+    return F3{a.x / l, a.y / l, a.z / l};
+}
+F3 f3_cross(F3 a, F3 b) { return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+void frame_rows(F3 n, float* out12) {
+    F3 v = f3_norm(n);
+    F3 r1, r2, r3;
+    if (v.y == 1.0f) {
+        r1 = F3{1, 0, 0}; r2 = F3{0, 0, 1}; r3 = F3{0, 1, 0};
+    } else if (v.y == -1.0f) {
+        r1 = F3{1, 0, 0}; r2 = F3{0, 0, 1}; r3 = F3{0, -1, 0};
+    } else {
+        F3 x = f3_norm(f3_cross(v, F3{0.0f, 1.0f, 0.0f}));
+        F3 z = f3_norm(f3_cross(x, v));
+        r1 = x; r2 = z; r3 = v;
+    }
+    const F3 rows[3] = {r1, r2, r3};
+    for (int k = 0; k < 3; ++k) {
+        out12[4 * k] = rows[k].x; out12[4 * k + 1] = rows[k].y; out12[4 * k + 2] = rows[k].z; out12[4 * k + 3] = 0.0f;
+    }
+}
+
+bool bad(std::string* err, const std::string& msg) { *err = msg; return false; }
+
+}  // namespace
+
+bool validate_scene(const SceneArgs& a, std::string* err) {
+    if (a.n_tri < 0 || (a.n_tri > 0 && (!a.tri_v || !a.tri_n || !a.tri_mat))) return bad(err, "bad triangle arrays");
+    if (a.n_sph < 0 || (a.n_sph > 0 && (!a.sph || !a.sph_mat))) return bad(err, "bad sphere arrays");
+    for (int64_t k = 0; k < a.n_sph; ++k) {
+        if (a.sph_mat[k] < 0 || a.sph_mat[k] >= a.n_mat) return bad(err, "sphere material id out of range");
+        if (!(a.sph[4 * k + 3] > 0.0f)) return bad(err, "sphere radius must be > 0");
+    }
+    if (a.n_tri + a.n_sph >= ((int64_t)1 << 31)) return bad(err, "too many primitives");
+    if (a.n_mat < 1 || !a.mat) return bad(err, "need at least one material");
+    if (a.n_light < 1 || !a.light_off || !a.light_tri) return bad(err, "There is no lights!!! (n_light < 1)");
+    for (int64_t i = 0; i < a.n_tri; ++i)
+        if (a.tri_mat[i] < 0 || a.tri_mat[i] >= a.n_mat)
+            return bad(err, "material id out of range at triangle " + std::to_string(i));
+    if (a.light_off[0] != 0) return bad(err, "light_off[0] must be 0");
+    for (int l = 0; l < a.n_light; ++l)
+        if (a.light_off[l + 1] <= a.light_off[l]) return bad(err, "every light needs >= 1 triangle");
+    for (int32_t k = 0; k < a.light_off[a.n_light]; ++k)
+        if (a.light_tri[k] < 0 || a.light_tri[k] >= a.n_tri) return bad(err, "light triangle out of range");
+    return true;
+}
+
+void pack_scene(const SceneArgs& a, PackedScene* out) {
+    const int64_t n_tri = a.n_tri;
+    out->tri_nm.assign((size_t)std::max<int64_t>(n_tri, 1) * 4, 0.0f);
+    out->tri_frame.assign((size_t)std::max<int64_t>(n_tri, 1) * 24, 0.0f);
+    for (int64_t i = 0; i < n_tri; ++i) {
+        const F3 nn{a.tri_n[3 * i], a.tri_n[3 * i + 1], a.tri_n[3 * i + 2]};
+        float* nm = out->tri_nm.data() + 4 * i;
+        nm[0] = nn.x; nm[1] = nn.y; nm[2] = nn.z;
+        nm[3] = bits_f(a.tri_mat[i]);
+        frame_rows(nn, out->tri_frame.data() + 24 * i);
+        frame_rows(F3{-nn.x, -nn.y, -nn.z}, out->tri_frame.data() + 24 * i + 12);
+    }
+    out->n_lt = a.light_off[a.n_light];
+    out->light_v.assign((size_t)out->n_lt * 16, 0.0f);
+    for (int k = 0; k < out->n_lt; ++k) {
+        const int64_t t = a.light_tri[k];
+        float* lv = out->light_v.data() + 16 * (size_t)k;
+        for (int c = 0; c < 3; ++c) {
+            lv[c] = a.tri_v[9 * t + c];
+            lv[4 + c] = a.tri_v[9 * t + 3 + c];
+            lv[8 + c] = a.tri_v[9 * t + 6 + c];
+            lv[12 + c] = a.tri_n[3 * t + c];
+        }
+        lv[15] = bits_f(a.tri_mat[t]);
+    }
+    out->plain = a.n_sph == 0;
+    for (int32_t i = 0; i < a.n_mat; ++i)
+        if (a.mat[8 * i + 5] == 2.0f || a.mat[8 * i + 5] == 3.0f) out->plain = false;   // metal / dielectric
+    // the shading quotients' cheap guards (prt_math.h lambert_div / nee_div) assume albedos and
+    // emitters in [2^-40, 2^40] and face normals of length in [0.5, 2]; other scenes keep div3's guard
+    out->shade_fast = true;
+    for (int32_t i = 0; i < a.n_mat && out->shade_fast; ++i)
+        for (int c = 0; c < 3; ++c) {
+            const float r = a.mat[8 * i + c];
+            if (!(r >= 0x1p-40f && r <= 0x1p40f)) out->shade_fast = false;
+        }
+    for (int64_t i = 0; i < n_tri && out->shade_fast; ++i) {
+        const double x = a.tri_n[3 * i], y = a.tri_n[3 * i + 1], z = a.tri_n[3 * i + 2];
+        const double l2 = x * x + y * y + z * z;
+        if (!(l2 >= 0.25 && l2 <= 4.0)) out->shade_fast = false;
+    }
+}
+
+long long env_int(const char* name, long long lo, long long hi, long long fallback) {
+    const char* v = std::getenv(name);
+    return v ? std::max(lo, std::min(hi, std::atoll(v))) : fallback;
+}
+
+std::vector<uint32_t> tile_origins(const int32_t* ids, int64_t n, int tiles_x, int tw, int th) {
+    std::vector<uint32_t> xy((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        xy[(size_t)i] = ids[i] < 0 ? 0xFFFF0000u
+                                   : ((uint32_t)((ids[i] % tiles_x) * tw) << 16) | (uint32_t)((ids[i] / tiles_x) * th);
+    return xy;
+}
+
+std::vector<int32_t> window_tiles(int W, int x0, int y0, int w, int h, int tw, int th) {
+    const int tiles_x = (W + tw - 1) / tw;
+    std::vector<int32_t> ids;
+    for (int ty = y0 / th; ty <= (y0 + h - 1) / th; ++ty)
+        for (int tx = x0 / tw; tx <= (x0 + w - 1) / tw; ++tx) ids.push_back(ty * tiles_x + tx);
+    return ids;
+}
+
+int latin_stride(int n) {
+    int s = std::max(1, (int)std::lround(0.38 * n));
+    auto gcd = [](int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; };
+    while (gcd(s, n) != 1) ++s;
+    return s;
+}
+
+std::vector<std::vector<int32_t>> latin_tile_ids(int W, int H, int tile, int n_ranks) {
+    const int tiles_x = (W + tile - 1) / std::max(tile, 1), tiles_y = (H + tile - 1) / std::max(tile, 1);
+    const int stride = latin_stride(n_ranks);
+    std::vector<std::vector<int32_t>> ids((size_t)n_ranks);
+    for (int id = 0; id < tiles_x * tiles_y; ++id)
+        ids[(size_t)((id % tiles_x + (int64_t)stride * (id / tiles_x)) % n_ranks)].push_back(id);
+    return ids;
+}
+
+bool slot_in_frame(const std::vector<uint32_t>& origins, int64_t slot, int tw, int th, int W, int H) {
+    const int64_t tpx = (int64_t)tw * th, loc = slot % tpx;
+    const uint32_t xy0 = origins[(size_t)(slot / tpx)];
+    return (int64_t)(xy0 >> 16) + loc % tw < W && (int64_t)(xy0 & 0xFFFFu) + loc / tw < H;
+}
+
+ChunkPlan plan_chunks(int64_t T, int64_t n_slots, int64_t bytes_per_sample, size_t budget) {
+    int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)budget / bytes_per_sample));
+    chunk = std::min<int64_t>(chunk, std::max<int64_t>(1, ((int64_t)1 << 31) / n_slots - 1));
+    const int64_t nc = (T + chunk - 1) / chunk;
+    chunk = (T + nc - 1) / nc;
+    return ChunkPlan{chunk, (T + chunk - 1) / chunk};
+}
+
+FrameSpan launch_frames(int64_t s0, int64_t n, int64_t spp, int64_t n_frames) {
+    return FrameSpan{s0 / spp, std::min<int64_t>(n_frames, (s0 + n + spp - 1) / spp)};
+}
+
+bool camera_is_fast(const float* cam) {
+    bool fin = true;
+    for (int i = 0; i < 20; ++i) fin = fin && std::isfinite(cam[i]);
+    return fin && !(cam[19] > 0.0f) && cam[12] == 0.0f && cam[13] == 0.0f && cam[14] == 0.0f && cam[15] == 1.0f;
+}
+
+void camera_terms(const float* cam, float cam_o[3], float cam_k[3]) {
+    const float rd2 = -cam[18];
+    for (int i = 0; i < 3; ++i) {
+        const float* c = cam + 4 * i;
+        cam_o[i] = 0.0f * c[0] + 0.0f * c[1] + 0.0f * c[2] + 1.0f * c[3];
+        cam_k[i] = rd2 * c[2];
+    }
+}
+
+}  // namespace prt

@@ -1,0 +1,67 @@
+// prt_plan.h — the host arithmetic of libprt that needs no GPU: scene argument checks and packing,
+// environment knobs, tile and window arithmetic, the launch-chunk plan and the camera's host-evaluated
+// terms.  Standard library + prt_internal.h only (no HIP include), plain arrays and small structs in
+// and out, so tools/sanitize/host_check.cpp runs all of it on the CPU under ASan + UBSan.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "prt_internal.h"
+
+namespace prt {
+
+// the scene arrays as prt_scene_create receives them (include/prt.h)
+struct SceneArgs {
+    const float* tri_v; const float* tri_n; const int32_t* tri_mat; int64_t n_tri;
+    const float* sph; const int32_t* sph_mat; int64_t n_sph;
+    const float* mat; int32_t n_mat;
+    const int32_t* light_tri; const int32_t* light_off; int32_t n_light;
+};
+// prt_scene_create's argument checks, in its order; false: *err holds the message of the first one failed
+bool validate_scene(const SceneArgs& a, std::string* err);
+
+struct PackedScene {
+    std::vector<float> tri_nm;     // per triangle: (face normal xyz, material id bits)
+    std::vector<float> tri_frame;  // per triangle: rotate_z_to rows (x, z, v) of n and of -n, 2 x 12 floats
+    std::vector<float> light_v;    // per emitter triangle: V0, V1, V2, (normal xyz, material id bits)
+    int n_lt = 0;                  // emitter triangles
+    bool plain = false;            // no spheres, no metal / dielectric material (TraceParams::plain)
+    bool shade_fast = false;       // TraceParams::shade_fast
+};
+void pack_scene(const SceneArgs& a, PackedScene* out);   // of validated arguments
+
+// integer environment knob: `fallback` when unset, else its value clamped to [lo, hi]
+long long env_int(const char* name, long long lo, long long hi, long long fallback);
+// PRT_SPILL_LDS takes 4, 16 or 32 entries; every other value means 16
+inline int spill_lds_entries(long long v) { return v == 4 ? 4 : v == 32 ? 32 : 16; }
+
+// per-tile pixel origins (x0 << 16 | y0) of tile ids in a frame of tiles_x columns of tw x th tiles; a
+// padding slot (id -1) gets x0 = 0xFFFF, past any frame's width (<= 65535), so the scatter drops its pixels
+std::vector<uint32_t> tile_origins(const int32_t* ids, int64_t n, int tiles_x, int tw, int th);
+// tile ids of a window, ascending (tiles of tw x th in the W-wide frame)
+std::vector<int32_t> window_tiles(int W, int x0, int y0, int w, int h, int tw, int th);
+// 'latin' tile owner of device_scene.tile_owner: rank = (tx + s * ty) mod n with s the
+// integer nearest 0.38 n that is coprime with n (every rank owns tiles in every row)
+int latin_stride(int n);
+std::vector<std::vector<int32_t>> latin_tile_ids(int W, int H, int tile, int n_ranks);   // per rank, ascending
+// slot -> pixel as the kernels map it (pixel_of): tile-major, then row-major within the tile
+bool slot_in_frame(const std::vector<uint32_t>& origins, int64_t slot, int tw, int th, int W, int H);
+
+// Launches of a render of T samples (spp * n_frames) of n_slots pixels at bytes_per_sample each: as many
+// samples per launch as the budget holds (at least one), every launch's item count below 2^31 (32-bit
+// work counter), then equal launches: no short last launch paying a whole launch tail for a few samples.
+struct ChunkPlan { int64_t chunk, n_launches; };
+ChunkPlan plan_chunks(int64_t T, int64_t n_slots, int64_t bytes_per_sample, size_t budget);
+// the frames [f0, f1) that the launch samples [s0, s0 + n) overlap (frame f = samples [f spp, (f + 1) spp))
+struct FrameSpan { int64_t f0, f1; };
+FrameSpan launch_frames(int64_t s0, int64_t n, int64_t spp, int64_t n_frames);
+
+// Pinhole camera with an affine matrix (no aperture, last row (0,0,0,1), all finite):
+// the kernels may use the exact gen_ray shortcut (TraceParams::cam_fast) ...
+bool camera_is_fast(const float* cam);
+// ... with its host-evaluated constant terms: the ray origin M (0,0,0,1) and rd.z * M[i][2]
+void camera_terms(const float* cam, float cam_o[3], float cam_k[3]);
+
+}  // namespace prt

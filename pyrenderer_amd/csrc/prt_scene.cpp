@@ -1,0 +1,289 @@
+// prt_scene.cpp — the library's identity calls, host BVH handles, and a scene's life: validate, build
+// the BVH, pack, upload, query the device, read the environment knobs; plus the choice of trace-kernel
+// variant that follows from the scene's sizes (prt_host.h).
+#include <cstdlib>
+#include <new>
+
+#include "prt_host.h"
+
+namespace prt {
+
+thread_local std::string g_err;
+
+namespace {
+
+int upload(DevBuf& b, const void* host, size_t bytes, size_t* total) {
+    HIP_TRY(b.ensure(std::max<size_t>(bytes, 16)));
+    if (bytes) HIP_TRY(hipMemcpy(b.p, host, bytes, hipMemcpyHostToDevice));
+    *total += b.bytes;
+    return PRT_OK;
+}
+
+// The buffers free themselves (DevBuf); what needs an order: the scene's device current, and the
+// device idle before the render contexts' buffers (streams of the caller may still run on them) go.
+void destroy_scene(Scene* s) {
+    if (!s) return;
+    DeviceGuard g(s->device);
+    if (!s->ctx.empty()) (void)hipDeviceSynchronize();
+    for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
+    if (s->scatter_ev) (void)hipEventDestroy(s->scatter_ev);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+// LDS-resident scene: BVH + triangles small enough to sit beside the stack
+constexpr int64_t kLdsSceneBytes = 24 * 1024;
+// the scene's sizes alone (all that the LDS footprints depend on), with the pooled kernel's stack
+TraceParams size_params(const Scene* s) {
+    TraceParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.n_node_f4 = (int)s->n_node4_f4; P.n_tri_f4 = (int)s->n_tri_f4; P.n_tri = (int)s->n_tri;
+    P.n_mat = s->n_mat; P.n_lt = s->n_lt; P.n_light = s->n_light;
+    P.lds_stack = s->need4;
+    return P;
+}
+
+// LDS-resident scene when it fits; the >= 7 (>= 6) waves/SIMD build when seven (six) blocks'
+// LDS still fit one CU (160 KiB), so the occupancy target is not defeated by LDS.
+// Everything else (and BVH4s deeper than the 64-entry LDS stack) takes the global-scene
+// kernel: 64-B quantised nodes, 16-entry LDS stack + spill, suspended traversal tails,
+// >= 6 waves/SIMD (C4: 28.6 ms at 5 waves, 27.2 at 6, 28.6 at 7 with spills).
+// An LDS-resident scene whose pooled-shadow kernel still fits seven blocks per CU takes that kernel
+// (C2 4.06 vs 4.28 ms, C3 73.6 vs 77.5 ms, profiles/r03/pool/) at every launch size: since round 6
+// it also wins the small launches that round 3 left to the phase-aligned kernel (config 1 0.080 vs
+// 0.094 ms per launch; DESIGN.md §2, profiles/r06/kernarg/variants/).
+int default_variant(const Scene* s) {
+    if (!lds_fits4(s) || !s->stack4) return kVarGlobal;
+    const TraceParams P = size_params(s);
+    if (s->need4 <= 32 && trace_smem_bytes(16, kVarLdsPool, P) * 7 <= 160 * 1024) return kVarLdsPool;
+    size_t smem = trace_smem_bytes(s->stack4, kVarLds, P);
+    return smem * 7 <= 160 * 1024 ? kVarLds : smem * 6 <= 160 * 1024 ? kVarLds6 : kVarLdsAnyOcc;
+}
+
+}  // namespace
+
+// ... and whose node indices and leaf references fit the LDS kernels' 16-bit stack entries
+// (inner nodes < 0x7FFF, the sentinel; leaf refs >= -32768)
+bool lds_fits4(const Scene* s) {
+    const int64_t n_refs = s->n_tri_f4 / 3;
+    return (int64_t)lds_scene_bytes(size_params(s)) <= kLdsSceneBytes && s->n_node4_f4 / 8 < 0x7FFF &&
+           n_refs * 8 <= 32768;
+}
+
+// the traversal stack entries of variant `var` (LDS part for the spill variants; the pool kernel's
+// instantiation set, its LDS stack being the launch parameter P.lds_stack)
+int variant_stack(const Scene* s, int var) {
+    return variant_pool(var) ? 16 : variant_spills(var) ? s->spill_lds : s->stack4;
+}
+
+// the variant a launch takes: the one the flags name, else the scene's default
+int launch_variant(const Scene* s, uint32_t flags) {
+    int var = (int)((flags >> PRT_FLAG_VARIANT_SHIFT) & 0xFFu);
+    const bool mis = (flags & PRT_FLAG_MIS_NEE) != 0;
+    if (var == 0) var = !mis ? default_variant(s) : (lds_fits4(s) && s->stack4) ? kVarLdsMis : kVarGlobalMis;
+    return var;
+}
+
+// blocks per CU of variant `var`'s persistent grid (>= 1), queried once per (variant, stats)
+int variant_occ(Scene* s, int var, bool stats) {
+    int& occ = s->occ[2 * var + (stats ? 1 : 0)];
+    const int stack = variant_stack(s, var);
+    if (occ == 0) occ = std::max(1, trace_blocks_per_cu(stack, var, stats, trace_smem_bytes(stack, var, size_params(s))));
+    return occ;
+}
+
+// Scene part of a trace launch's parameters (everything but the work description).
+void scene_params(Scene* s, TraceParams& P) {
+    P = size_params(s);
+    P.lds_stack = 0;   // set per launch (trace_setup)
+    P.nodes = (const float4*)s->nodes4.p; P.tris = (const float4*)s->tris.p;
+    P.tri_nm = (const float4*)s->tri_nm.p; P.tri_frame = (const float4*)s->tri_frame.p;
+    P.mats = (const float*)s->mats.p;
+    P.light_v = (const float4*)s->light_v.p; P.light_off = (const int*)s->light_off.p;
+    P.dl_r = s->direct_rgb[0]; P.dl_g = s->direct_rgb[1]; P.dl_b = s->direct_rgb[2];
+    P.resume_min = s->resume_min; P.pool_resume_min = s->pool_resume_min;
+    P.stats = (unsigned long long*)s->stats.p;
+    P.guard_trips = s->guard_trips;
+    P.n_sph = (int)s->n_sph; P.sph = (const float4*)s->sph.p; P.sph_mat = (const int*)s->sph_mat.p;
+    P.plain = s->plain ? 1 : 0; P.shade_fast = s->shade_fast ? 1 : 0;
+    P.frame_spp = 0xFFFFFFFFu;   // one frame: global sample = s0 + j0 + the chunk's sample
+}
+
+namespace {
+
+// device half of prt_scene_create: uploads, device properties, environment knobs
+int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedScene& pk) {
+    hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) return fail(PRT_ERR_HIP, std::string("hipStreamCreate: ") + hipGetErrorString(e));
+    size_t* total = &s->device_bytes;
+    {
+        Bvh4Host b4;
+        collapse_bvh4(bvh, &b4);
+        s->n_node4_f4 = (int64_t)b4.nodes.size() / 4;
+        s->stack4 = b4.stack_need <= 32 ? stack_variant(b4.stack_need - 1) : 0;
+        s->need4 = b4.stack_need;
+        if (int rc = upload(s->nodes4, b4.nodes.data(), sizeof(float) * b4.nodes.size(), total)) return rc;
+        std::vector<float> q4;
+        quantize_bvh4(b4, bvh.pad, &q4);
+        s->n_node4q_f4 = (int64_t)q4.size() / 4;
+        if (int rc = upload(s->nodes4q, q4.data(), sizeof(float) * q4.size(), total)) return rc;
+    }
+    s->n_lt = pk.n_lt;
+    s->n_sph = a.n_sph;
+    s->plain = pk.plain;
+    s->shade_fast = pk.shade_fast;
+    if (int rc = upload(s->tris, bvh.tris.data(), sizeof(float) * bvh.tris.size(), total)) return rc;
+    if (int rc = upload(s->tri_nm, pk.tri_nm.data(), sizeof(float) * pk.tri_nm.size(), total)) return rc;
+    if (int rc = upload(s->tri_frame, pk.tri_frame.data(), sizeof(float) * pk.tri_frame.size(), total)) return rc;
+    if (int rc = upload(s->mats, a.mat, sizeof(float) * 8 * (size_t)a.n_mat, total)) return rc;
+    if (int rc = upload(s->light_v, pk.light_v.data(), sizeof(float) * pk.light_v.size(), total)) return rc;
+    if (int rc = upload(s->light_off, a.light_off, sizeof(int32_t) * (size_t)(a.n_light + 1), total)) return rc;
+    if (int rc = upload(s->sph, a.sph, sizeof(float) * 4 * (size_t)a.n_sph, total)) return rc;
+    if (int rc = upload(s->sph_mat, a.sph_mat, sizeof(int32_t) * (size_t)a.n_sph, total)) return rc;
+    if ((e = s->work.ensure(64)) != hipSuccess || (e = s->stats.ensure(8 * kStatWords)) != hipSuccess)
+        return fail(PRT_ERR_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    // the hit-query watchdog flag is read by prt_check_faults before any hit query ran
+    if ((e = hipMemset(s->work.p, 0, 64)) != hipSuccess) return fail(PRT_ERR_HIP, hipGetErrorString(e));
+    hipDeviceProp_t prop;
+    if ((e = hipGetDeviceProperties(&prop, s->device)) != hipSuccess) return fail(PRT_ERR_HIP, hipGetErrorString(e));
+    s->cus = prop.multiProcessorCount;
+    s->n_tri_f4 = (int64_t)bvh.tris.size() / 4;
+    s->leaf_exit = (int)env_int("PRT_LEAF_EXIT", 0, 64, s->leaf_exit);
+    s->leaf_break = (int)env_int("PRT_LEAF_BREAK", 0, 64, s->leaf_break);
+    if (const char* wc = std::getenv("PRT_WAVE_CLOCK")) s->wave_clock_path = wc;
+    s->guard_trips = (uint32_t)env_int("PRT_GUARD_TRIPS", 1, UINT32_MAX, s->guard_trips);
+    s->resume_min = (int)env_int("PRT_RESUME_MIN", 1, 64, s->resume_min);
+    s->pool_resume_min = (int)env_int("PRT_POOL_RESUME_MIN", 0, 64, s->pool_resume_min);
+    s->spill_lds = spill_lds_entries(env_int("PRT_SPILL_LDS", INT32_MIN, INT32_MAX, s->spill_lds));
+    s->blocks_per_cu = variant_occ(s, default_variant(s), false);
+    if (const long long cb = env_int("PRT_CHUNK_BYTES", 1LL << 20, INT64_MAX, 0)) {
+        s->chunk_bytes = (size_t)cb;
+    } else {
+        // the default budget takes at most a quarter of the memory free at scene creation (16 GiB
+        // of an idle MI355X's 288 GB); enqueue_render also caps it by the memory free when a
+        // render stream's buffers grow
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+            s->chunk_bytes = std::max<size_t>((size_t)1 << 28, std::min(s->chunk_bytes, free_b / 4));
+    }
+    return PRT_OK;
+}
+
+}  // namespace
+}  // namespace prt
+
+using namespace prt;
+
+extern "C" {
+
+int prt_abi_version(void) { return PRT_ABI_VERSION; }
+
+const char* prt_last_error(void) { return g_err.c_str(); }
+
+int prt_device_count(int* n) {
+    if (!n) return fail(PRT_ERR_ARG, "n is NULL");
+    int c = 0;
+    if (hipGetDeviceCount(&c) != hipSuccess) c = 0;
+    *n = c;
+    return PRT_OK;
+}
+
+int prt_bvh_build(const float* tri_v, int64_t n_tri, int32_t max_leaf, void** out_bvh) {
+    if (!out_bvh || (n_tri > 0 && !tri_v)) return fail(PRT_ERR_ARG, "NULL argument");
+    auto* b = new (std::nothrow) BvhHost();
+    if (!b) return fail(PRT_ERR_OOM, "host allocation failed");
+    std::string err;
+    try {
+        if (!build_bvh(tri_v, n_tri, max_leaf, b, &err)) { delete b; return fail(PRT_ERR_ARG, err); }
+    } catch (const std::bad_alloc&) {
+        delete b;
+        return fail(PRT_ERR_OOM, "host allocation failed during BVH build");
+    }
+    *out_bvh = b;
+    return PRT_OK;
+}
+
+int prt_bvh_info(void* bvh, int64_t* info6) {
+    auto* b = (BvhHost*)bvh;
+    if (!b || !info6) return fail(PRT_ERR_ARG, "NULL argument");
+    int32_t padbits;
+    std::memcpy(&padbits, &b->pad, 4);
+    info6[0] = b->n_nodes; info6[1] = b->depth; info6[2] = b->n_leaves; info6[3] = (int64_t)b->order.size();
+    info6[4] = padbits; info6[5] = (int64_t)(b->sah_cost * 1000.0 + 0.5);
+    return PRT_OK;
+}
+
+int prt_bvh_export(void* bvh, float* nodes, float* tris, int32_t* order) {
+    auto* b = (BvhHost*)bvh;
+    if (!b) return fail(PRT_ERR_ARG, "NULL argument");
+    if (nodes) std::memcpy(nodes, b->nodes.data(), sizeof(float) * b->nodes.size());
+    if (tris) std::memcpy(tris, b->tris.data(), sizeof(float) * b->tris.size());
+    if (order) std::memcpy(order, b->order.data(), sizeof(int32_t) * b->order.size());
+    return PRT_OK;
+}
+
+void prt_bvh_destroy(void* bvh) { delete (BvhHost*)bvh; }
+
+int prt_scene_create(int device, const float* tri_v, const float* tri_n, const int32_t* tri_mat, int64_t n_tri,
+                     const float* sph, const int32_t* sph_mat, int64_t n_sph, const float* mat, int32_t n_mat,
+                     const int32_t* light_tri, const int32_t* light_off, int32_t n_light, const float* direct_rgb,
+                     void** out_scene) {
+    if (!out_scene) return fail(PRT_ERR_ARG, "out_scene is NULL");
+    *out_scene = nullptr;
+    const SceneArgs a{tri_v, tri_n, tri_mat, n_tri, sph, sph_mat, n_sph, mat, n_mat, light_tri, light_off, n_light};
+    std::string err;
+    if (!validate_scene(a, &err)) return fail(PRT_ERR_ARG, err);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(PRT_ERR_HIP, "no HIP device available");
+    if (device < 0 || device >= ndev) return fail(PRT_ERR_ARG, "device index out of range");
+
+    BvhHost bvh;
+    PackedScene pk;
+    try {
+        if (!build_bvh(tri_v, n_tri, (int)env_int("PRT_MAX_LEAF", INT32_MIN, INT32_MAX, 4), &bvh, &err))
+            return fail(PRT_ERR_ARG, err);
+        pack_scene(a, &pk);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_ERR_OOM, "host allocation failed during BVH build");
+    }
+    auto* s = new (std::nothrow) Scene();
+    if (!s) return fail(PRT_ERR_OOM, "host allocation failed");
+    s->device = device;
+    s->n_tri = n_tri;
+    s->n_nodes = bvh.n_nodes;
+    s->depth = bvh.depth;
+    s->n_light = n_light;
+    s->n_mat = n_mat;
+    if (direct_rgb) std::memcpy(s->direct_rgb, direct_rgb, sizeof(float) * 3);
+    DeviceGuard g(device);
+    if (int rc = fill_scene(s, a, bvh, pk)) { destroy_scene(s); return rc; }
+    *out_scene = s;
+    return PRT_OK;
+}
+
+int prt_scene_info(void* scene, int64_t* info8) {
+    auto* s = (Scene*)scene;
+    if (!s || !info8) return fail(PRT_ERR_ARG, "NULL argument");
+    info8[0] = s->device; info8[1] = s->n_tri; info8[2] = s->n_nodes; info8[3] = s->depth;
+    info8[4] = s->stack4; info8[5] = (int64_t)s->device_bytes; info8[6] = s->blocks_per_cu; info8[7] = s->cus;
+    return PRT_OK;
+}
+
+void prt_scene_destroy(void* scene) { destroy_scene((Scene*)scene); }
+
+int prt_scene_kernel(void* scene, int32_t* out4) { return prt_launch_kernel(scene, INT64_MAX, 0, out4); }
+
+int prt_launch_kernel(void* scene, int64_t n_items, uint32_t flags, int32_t* out4) {
+    auto* s = (Scene*)scene;
+    if (!s || !out4) return fail(PRT_ERR_ARG, "NULL argument");
+    if (n_items < 0) return fail(PRT_ERR_ARG, "n_items < 0");
+    int var = launch_variant(s, flags);
+    out4[0] = var;
+    out4[1] = 4;
+    out4[2] = (variant_uses_lds(var) ? 1 : 0) | (variant_quantized(var) ? 2 : 0);
+    // the pooled kernel's LDS stack is sized to the BVH4's exact bound (P.lds_stack = need4)
+    out4[3] = variant_pool(var) ? s->need4 : variant_stack(s, var);
+    return PRT_OK;
+}
+
+}  // extern "C"

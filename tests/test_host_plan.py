@@ -1,0 +1,297 @@
+"""The host arithmetic of libprt that needs no GPU (pyrenderer_amd/csrc/prt_plan.cpp: scene checks and
+packing, environment knobs, tile / window / ownership arithmetic, the launch-chunk plan, camera terms),
+run in its AddressSanitizer + UndefinedBehaviorSanitizer build through the stand-alone driver
+tools/sanitize/host_check.cpp and compared with numpy restatements.  A subprocess per call: exit code 0,
+no sanitizer text on stderr, one JSON line on stdout."""
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from scene_cases import ARRAYS, REJECTED, base_scene, scene
+
+SAN = os.path.join(ROOT, "tools", "sanitize")
+OUT = os.path.join(ROOT, "build", "sanitize")
+F = np.float32
+
+
+@pytest.fixture(scope="module")
+def built():
+    subprocess.run(["make", "-s", "-C", SAN, os.path.join(OUT, "host_check")], check=True, capture_output=True,
+                   timeout=600)
+    return os.path.join(OUT, "host_check")
+
+
+def _run(built, *args, **env):
+    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1", **env)
+    r = subprocess.run([built] + [str(a) for a in args], env=e, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+# ---------------------------------------------------------------- tiles, windows, ownership
+
+@pytest.mark.parametrize("tw,th", [(8, 8), (16, 4)])
+def test_tile_origins_decode_to_the_tile_corner(built, tw, th):
+    W, H = 100, 70   # the ragged frame of test_gpu_boundary
+    tiles_x, tiles_y = -(-W // tw), -(-H // th)
+    ids = list(range(tiles_x * tiles_y)) + [-1]
+    xy = _run(built, "origins", tiles_x, tw, th, *ids)["origins"]
+    assert len(xy) == len(ids)
+    for i, v in zip(ids[:-1], xy[:-1]):
+        assert (v >> 16, v & 0xFFFF) == ((i % tiles_x) * tw, (i // tiles_x) * th)
+    assert xy[-1] == 0xFFFF0000
+
+
+@pytest.mark.parametrize("win", [(0, 0, 100, 70), (37, 41, 1, 1), (8, 16, 24, 16)],
+                         ids=["full_frame", "one_pixel", "ends_on_tile_edge"])
+def test_window_tiles_cover_the_window_and_only_touched_tiles(built, win):
+    W, H, tw, th = 100, 70, 8, 8
+    x0, y0, w, h = win
+    ids = _run(built, "window", W, x0, y0, w, h, tw, th)["ids"]
+    tiles_x = -(-W // tw)
+    ty, tx = np.meshgrid(np.arange(y0 // th, (y0 + h - 1) // th + 1), np.arange(x0 // tw, (x0 + w - 1) // tw + 1),
+                         indexing="ij")
+    assert ids == (ty * tiles_x + tx).ravel().tolist()
+    covered = np.zeros((W + tw, H + th), bool)
+    for i in ids:
+        cx, cy = (i % tiles_x) * tw, (i // tiles_x) * th
+        # every tile touches the window ...
+        assert cx < x0 + w and cx + tw > x0 and cy < y0 + h and cy + th > y0
+        covered[cx:cx + tw, cy:cy + th] = True
+    # ... and together they cover it
+    assert covered[x0:x0 + w, y0:y0 + h].all()
+
+
+def test_slots_outside_a_ragged_frame_are_flagged(built):
+    W, H, tw, th = 100, 70, 8, 8
+    tiles_x = -(-W // tw)
+    ids = [0, tiles_x - 1, tiles_x * 8, tiles_x * 9 - 1]   # inner, right edge, bottom edge, corner
+    got = np.array(_run(built, "in_frame", W, H, tw, th, *ids)["in_frame"]).reshape(len(ids), th, tw)
+    for k, i in enumerate(ids):
+        x = (i % tiles_x) * tw + np.arange(tw)[None, :]
+        y = (i // tiles_x) * th + np.arange(th)[:, None]
+        assert np.array_equal(got[k].astype(bool), (x < W) & (y < H))
+    assert got[0].all() and not got[3].all()
+
+
+def test_latin_stride_matches_the_python_owner(built):
+    from pyrenderer_amd.device_scene import latin_stride
+    assert _run(built, "latin_stride", 1, 64)["strides"] == [latin_stride(n) for n in range(1, 65)]
+
+
+@pytest.mark.parametrize("W,H,tile", [(128, 128, 16), (100, 70, 8)])
+def test_per_rank_tile_lists_match_tile_owner(built, W, H, tile):
+    from pyrenderer_amd.device_scene import tile_owner
+    for n in (1, 2, 3, 5, 8):
+        owner = tile_owner(W, H, tile, n, "latin")
+        ids = _run(built, "latin", W, H, tile, n)["ids"]
+        assert ids == [np.nonzero(owner == r)[0].tolist() for r in range(n)]
+
+
+# ---------------------------------------------------------------- chunk plan
+
+def test_chunk_plan_properties(built):
+    cases = []
+    for T in (1, 2, 7, 20, 64, 1000):
+        for n_slots in (64, 4096, 1 << 22, 1 << 30):
+            for per_slot in (28, 44):   # radiance + ray, + per-ray origin
+                b = per_slot * n_slots
+                for budget in (b // 2, b, 3 * b + 5, (T // 2 + 1) * b, T * b, 10 * T * b):
+                    cases.append((T, n_slots, b, budget))
+    plans = _run(built, "chunks", *[v for c in cases for v in c])["plans"]
+    assert len(plans) == len(cases)
+    for (T, n_slots, b, budget), (chunk, launches) in zip(cases, plans):
+        sizes = [min(chunk, T - s0) for s0 in range(0, T, chunk)]
+        assert sum(sizes) == T and len(sizes) == launches and max(sizes) <= chunk and min(sizes) >= 1
+        assert chunk * n_slots < 1 << 31
+        assert chunk * b <= budget or chunk == 1
+        # the most samples one launch may hold: the budget's (at least one), the 2^31 item bound's
+        cap = min(max(1, budget // b), ((1 << 31) - 1) // n_slots, T)
+        assert launches == -(-T // cap), (T, n_slots, b, budget, chunk, launches)
+
+
+def test_chunk_plan_worked_case(built):
+    # 4096 slots at 28 B per slot and sample, 1 MiB: the budget holds 9 samples, 20 samples take
+    # three launches, evened out to 7, 7, 6
+    assert (1 << 20) // (28 * 4096) == 9
+    assert _run(built, "chunks", 20, 4096, 28 * 4096, 1 << 20)["plans"] == [[7, 3]]
+    assert [l[1] for l in _run(built, "frames", 20, 1, 7)["launches"]] == [7, 7, 6]
+
+
+@pytest.mark.parametrize("chunk", [7, 20, 100], ids=["straddles_three_frames", "chunk_eq_T", "chunk_gt_T"])
+def test_frame_windows_of_a_launch(built, chunk):
+    spp, n_frames = 4, 5
+    T = spp * n_frames
+    got = _run(built, "frames", spp, n_frames, chunk)["launches"]
+    want = [[s0, min(chunk, T - s0), s0 // spp, min(n_frames, -(-(s0 + min(chunk, T - s0)) // spp))]
+            for s0 in range(0, T, chunk)]
+    assert got == want
+    if chunk == 7:
+        assert got[1] == [7, 7, 1, 4]   # samples 7..13: frames 1, 2 and 3
+    else:
+        assert got == [[0, T, 0, n_frames]]
+
+
+# ---------------------------------------------------------------- knobs and camera
+
+def test_env_int_clamps_and_falls_back(built):
+    assert _run(built, "env", "PRT_T_UNSET", 0, 64, -1)["value"] == -1
+    assert _run(built, "env", "PRT_T", 0, 64, -1, PRT_T="100")["value"] == 64
+    assert _run(built, "env", "PRT_T", 1, 64, 32, PRT_T="-5")["value"] == 1
+    assert _run(built, "env", "PRT_T", 0, 64, 12, PRT_T="abc")["value"] == 0
+    assert _run(built, "env", "PRT_T", 1, 0xFFFFFFFF, 1 << 20, PRT_T="99999999999")["value"] == 0xFFFFFFFF
+    assert _run(built, "env", "PRT_T", 1 << 20, (1 << 63) - 1, 0, PRT_T=str(1 << 34))["value"] == 1 << 34
+    assert _run(built, "env", "PRT_T", 1 << 20, (1 << 63) - 1, 0, PRT_T="4096")["value"] == 1 << 20
+    spill = [_run(built, "env", "PRT_T", -(1 << 31), (1 << 31) - 1, 16, PRT_T=v)["spill_lds"] for v in "4 16 32 7 0".split()]
+    assert spill == [4, 16, 32, 16, 16]
+    assert _run(built, "env", "PRT_T_UNSET", -(1 << 31), (1 << 31) - 1, 16)["spill_lds"] == 16
+
+
+def test_camera_terms_in_f32_order(built, cornell, tmp_path):
+    cam = np.ascontiguousarray(cornell[1].convert_to_taichi_camera().packed(), F).copy()
+
+    def check(c):
+        p = tmp_path / "cam.f32"
+        c.astype(F).tofile(p)
+        rep = _run(built, "camera", p)
+        fast = bool(np.isfinite(c[:20]).all() and not c[19] > 0 and tuple(c[12:16]) == (0, 0, 0, 1))
+        assert rep["fast"] == fast
+        with np.errstate(invalid="ignore"):
+            rows = c[:12].reshape(3, 4)
+            o = ((F(0) * rows[:, 0] + F(0) * rows[:, 1]) + F(0) * rows[:, 2]) + F(1) * rows[:, 3]
+            k = -c[18] * rows[:, 2]
+        assert rep["cam_o"] == o.astype(F).view(np.uint32).tolist()
+        assert rep["cam_k"] == k.astype(F).view(np.uint32).tolist()
+        return fast
+
+    pin = cam.copy()
+    pin[12:16], pin[19] = (0, 0, 0, 1), 0
+    assert check(cam) in (True, False) and check(pin)
+    for i, v in ((19, 0.5), (12, 0.25), (3, np.inf)):   # thin lens, projective row, non-finite
+        c = pin.copy()
+        c[i] = v
+        assert not check(c)
+
+
+# ---------------------------------------------------------------- scene validation and packing
+
+def _scene(built, d, s):
+    os.makedirs(d, exist_ok=True)
+    for name in ARRAYS:
+        if s[name] is not None:
+            np.ascontiguousarray(s[name]).tofile(os.path.join(d, name + (".f32" if s[name].dtype == F else ".i32")))
+    return _run(built, "scene", d, s["n_tri"], s["n_sph"], s["n_mat"], s["n_light"])
+
+
+def _packed(d, name, width):
+    return np.fromfile(os.path.join(d, name + ".f32"), F).reshape(-1, width)
+
+
+@pytest.mark.parametrize("name,args,message", REJECTED, ids=[c[0] for c in REJECTED])
+def test_rejected_scene_reports_its_first_failed_check(built, tmp_path, name, args, message):
+    assert _scene(built, str(tmp_path), args) == {"error": message}
+
+
+def _norm(n):
+    """f3_norm in numpy f32, in its operation order."""
+    n = n.astype(F)
+    l = np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
+    return np.array([n[0] / l, n[1] / l, n[2] / l], F)
+
+
+def _check_packing(d, s, rep):
+    n_tri = s["n_tri"]
+    tri_n, tri_v, tri_mat = s["tri_n"].reshape(-1, 3), s["tri_v"].reshape(-1, 9), s["tri_mat"]
+    nm = _packed(d, "tri_nm", 4)
+    assert nm.shape[0] == n_tri
+    assert np.array_equal(nm[:, :3].view(np.uint32), tri_n.view(np.uint32))
+    assert np.array_equal(nm[:, 3].view(np.int32), tri_mat)
+    fr = _packed(d, "tri_frame", 12).reshape(n_tri, 2, 3, 4)
+    assert not fr[..., 3].any()
+    for i in range(n_tri):
+        for side, n in enumerate((tri_n[i], -tri_n[i])):
+            rows = fr[i, side, :, :3]
+            v = _norm(n)
+            if v[1] in (1, -1):
+                assert np.array_equal(rows, np.array([[1, 0, 0], [0, 0, 1], [0, v[1], 0]], F))
+            else:
+                assert np.array_equal(rows[2].view(np.uint32), v.view(np.uint32))   # rows x, z, v
+                assert np.abs(rows.astype(np.float64) @ rows.astype(np.float64).T - np.eye(3)).max() <= 1e-6
+                assert rows[0, 1] == 0   # x = normalize(v x (0,1,0)) lies in the xz plane
+    n_lt = int(s["light_off"][s["n_light"]])
+    assert rep["n_lt"] == n_lt
+    lv = _packed(d, "light_v", 16)
+    assert lv.shape[0] == n_lt
+    t = s["light_tri"][:n_lt]
+    for k in range(3):
+        assert np.array_equal(lv[:, 4 * k:4 * k + 3], tri_v[t, 3 * k:3 * k + 3]) and not lv[:, 4 * k + 3].any()
+    assert np.array_equal(lv[:, 12:15], tri_n[t]) and np.array_equal(lv[:, 15].view(np.int32), tri_mat[t])
+
+
+def _flat_args(flat):
+    has_sph = flat.sph.shape[0] > 0
+    return dict(tri_v=flat.tri_v, tri_n=flat.tri_n, tri_mat=flat.tri_mat, n_tri=flat.n_tri,
+                sph=flat.sph if has_sph else None, sph_mat=flat.sph_mat if has_sph else None, n_sph=flat.sph.shape[0],
+                mat=flat.mat, n_mat=flat.mat.shape[0], light_tri=flat.light_tri, light_off=flat.light_off,
+                n_light=flat.n_light)
+
+
+def test_cornell_packs_as_the_kernels_read_it(built, cornell, tmp_path):
+    s = _flat_args(cornell[2])
+    rep = _scene(built, str(tmp_path), s)
+    assert rep["error"] is None and rep["plain"] is True and rep["shade_fast"] is True
+    _check_packing(str(tmp_path), s, rep)
+
+
+def _hand_made(**over):
+    """Three triangles: normals +y, -y and a non-unit one; the second emits."""
+    tri_v = np.array([[0, 0, 0, 1, 0, 0, 0, 0, 1], [0, 2, 0, 0, 2, 1, 1, 2, 0], [0, 0, 0, 0, 1, 0, 1, 0, 0]], F)
+    s = scene(tri_v=tri_v, tri_n=np.array([[0, 1, 0], [0, -1, 0], [0.6, 1.2, -0.5]], F), tri_mat=np.array([0, 1, 0], np.int32),
+              n_tri=3, mat=np.array([[0.5, 0.25, 0.75, 0, 0, 0, 1, 0], [1, 1, 1, 5, 0, 0, 1, 0]], F), n_mat=2,
+              light_tri=np.array([1], np.int32), light_off=np.array([0, 1], np.int32), n_light=1)
+    s.update(over)
+    return s
+
+
+def test_hand_made_scene_packs_the_literal_y_frames(built, tmp_path):
+    s = _hand_made()
+    rep = _scene(built, str(tmp_path), s)
+    assert rep["error"] is None and rep["plain"] is True and rep["shade_fast"] is True
+    _check_packing(str(tmp_path), s, rep)
+    fr = _packed(str(tmp_path), "tri_frame", 12).reshape(3, 2, 3, 4)
+    up = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0]], F)
+    down = np.array([[1, 0, 0, 0], [0, 0, 1, 0], [0, -1, 0, 0]], F)
+    assert np.array_equal(fr[0], [up, down]) and np.array_equal(fr[1], [down, up])
+
+
+def _mat(s, row, col, value):
+    m = s["mat"].copy()
+    m[row, col] = value
+    return m
+
+
+@pytest.mark.parametrize("over,plain,shade_fast", [
+    (lambda s: dict(mat=_mat(s, 0, 5, 2)), False, True),                                      # metal
+    (lambda s: dict(mat=_mat(s, 1, 5, 3)), False, True),                                      # dielectric
+    (lambda s: dict(sph=np.array([[0, 0, 0, 1]], F), sph_mat=np.array([0], np.int32), n_sph=1), False, True),
+    (lambda s: dict(mat=_mat(s, 0, 1, 0)), True, False),                                      # albedo 0
+    (lambda s: dict(mat=_mat(s, 0, 2, 1e-20)), True, False),                                  # albedo 1e-20
+    (lambda s: dict(tri_n=np.array([[0, 1, 0], [0, -1, 0], [1, 2, 2]], F)), True, False),     # normal of length 3
+], ids=["metal", "dielectric", "sphere", "albedo_0", "albedo_1e-20", "normal_length_3"])
+def test_plain_and_shade_fast_classification(built, tmp_path, over, plain, shade_fast):
+    s = _hand_made()
+    s.update(over(s))
+    rep = _scene(built, str(tmp_path), s)
+    assert rep["error"] is None and (rep["plain"], rep["shade_fast"]) == (plain, shade_fast)
+
+
+def test_valid_base_scene_is_accepted(built, tmp_path):
+    rep = _scene(built, str(tmp_path), base_scene())
+    assert rep == {"error": None, "n_lt": 1, "plain": True, "shade_fast": True}

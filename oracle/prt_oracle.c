@@ -594,9 +594,14 @@ static Hit hit_all_brute(const OScene* s, v3 ro, v3 rd, float t_min, float t_max
 }
 
 /* Traversal of an external BVH2 (nodes from prt_bvh_export: two child boxes +
- * refs per 64-B node; leaf ref < 0 encodes (first slot, count)).  Boxes only
- * prune, so the result is the brute-force closest (t, index) hit; the slab test
- * is the reference's (bvh_taichi.py:168-190) with t1 = closest so far. */
+ * refs per 64-B node; leaf ref < 0 encodes (first slot, count)).  This backend's
+ * contract is "boxes only prune": the result is the brute-force closest (t, index)
+ * hit.  The slab test is the reference's (bvh_taichi.py:168-190), whose gamma factor
+ * widens the far planes only; with t1 = closest so far as it stands, a flat box whose
+ * near distance rounds an ulp above `best` would be culled together with a lower-index
+ * triangle in it that ties at t == best (seen from origins 100 scene extents away).
+ * So the bound gets the same factor, min(far, best) * gamma as the HIP slab test has
+ * it, and a box entered at t == best up to the slab's own rounding is still visited. */
 static Hit hit_all_bvh(const OScene* s, v3 ro, v3 rd, float t_min, float t_max, int any_hit, uint64_t* cnt) {
     Hit h; memset(&h, 0, sizeof(h));
     float best = t_max;
@@ -612,7 +617,7 @@ static Hit hit_all_bvh(const OScene* s, v3 ro, v3 rd, float t_min, float t_max, 
             for (int side = 1; side >= 0; --side) {
                 const float* b = nd + 6 * side;
                 float lo[3] = {b[0], b[2], b[4]}, hi[3] = {b[1], b[3], b[5]};
-                if (aabb_hit(lo, hi, ro, rd, t_min, best)) {
+                if (aabb_hit(lo, hi, ro, rd, t_min, best * g_gamma_factor)) {
                     int32_t ref;
                     memcpy(&ref, nd + 12 + side, 4);
                     if (sp < 128) stack[sp++] = ref;

@@ -292,6 +292,35 @@ int prt_trace_rays(void* scene, const float* rays, int64_t n, int depth, uint64_
  * the frame (partial edge tiles) are all zeros.  Synchronous. */
 int prt_camera_rays(void* scene, const float* cam, int W, int H, int tw, int th, const int32_t* tile_ids,
                     int n_tiles, int first_sample, int spp, uint64_t seed, float* out8);
+/* The denoiser's first-hit features (the `feat` of the denoise section below) in one kernel: what
+ * prt_camera_rays plus prt_hit_all plus per-pixel sums on the host composed before, without the
+ * per-ray buffers and the copies between them.  Added under ABI 4: purely additive.  For every pixel
+ * of the W x H frame and samples first_sample .. first_sample + samples - 1 in that order: the
+ * render's own primary ray (the stream keyed (seed, pixel, sample), as prt_camera_rays), its closest
+ * hit in PathTracer.trace's primary range (t_min 1e-5f, t_max 99999.9f; core/tracing.py:126-127),
+ * and at a hit prt_hit_all's normal [5:8] and attenuation [9:12].  Eight f32 sums per pixel start
+ * at +0 and take one term per sample in sample order — albedo.rgb, normal.xyz, t, 1 — all 0 at a
+ * miss; then channels 0-5 = sum / (float)samples, 6 = t sum / fmaxf(hits, 1), 7 = hits /
+ * (float)samples, each one IEEE f32 operation: the result is reproducible bit for bit and equals
+ * the host composition (pyrenderer_amd.denoise.features_packed_host).
+ *   out   W x H x 8 f32, [x][y]: albedo.rgb, shading normal.xyz, depth, hit fraction
+ *   flags 0 or PRT_HITS_QUANTIZED (the quantised BVH4, same results)
+ * W and H: 1..65535.  A frame of one row or column has no camera ray the render defines (u = (x + r) /
+ * (W - 1)) and no render entry point takes it; it is accepted here for callers that size buffers by
+ * it, and its pixels hold whatever IEEE arithmetic makes of the quotient.  NULL scene, cam or out, a
+ * size outside that range, samples < 1, first_sample < 0, first_sample + samples > INT32_MAX, other
+ * flags, or a BVH4 deeper than the hit queries take return PRT_ERR_ARG before any device call.
+ * prt_features: host `out`, synchronous; reports a watchdog trip itself (PRT_ERR_INTERNAL). */
+#define PRT_FEATURE_CHANNELS 8
+int prt_features(void* scene, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
+                 uint32_t flags, float* out);
+/* The same on the device: d_out (device, 16-byte aligned) is written by one kernel enqueued on
+ * `stream` (a hipStream_t of the scene's device; NULL = the null stream) with no host
+ * synchronisation, so a frame can go prt_render_tiles_device -> prt_scatter_tiles -> prt_denoise*_device
+ * without leaving the device.  PRT_FLAG_TIME does not apply.  A watchdog trip is reported by
+ * prt_check_faults, as for the device-output renders. */
+int prt_features_device(void* scene, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
+                        uint32_t flags, float* d_out, void* stream);
 /* trace-kernel variant chosen for this scene's large launches when flags select none:
  * out4 = {variant, BVH arity (2 or 4), bit 0 scene LDS-resident | bit 1 quantised nodes,
  *         LDS traversal stack entries per lane: the instantiation set, or for the pooled kernel
@@ -322,8 +351,8 @@ int prt_diag_words(void* scene, uint64_t* out, int n);
  * prt_denoise_last_error, not prt_last_error.
  *   color   W x H x 3 f32   mean radiance, [x][y]
  *   feat    W x H x 8 f32   per pixel: albedo.rgb, shading normal.xyz, depth, hit fraction
- *                           (pyrenderer_amd.denoise.features composes them from prt_camera_rays
- *                           and prt_hit_all)
+ *                           (prt_features / prt_features_device above compute them;
+ *                           pyrenderer_amd.denoise.features is their front end)
  *   iterations 0..8         pass i uses the 5 x 5 B3-spline stencil at step 2^i
  *   params4 4 f32           sigma_c (colour), sigma_z (depth), eps_a (albedo floor of the
  *                           demodulation), eps_z (depth floor); all > 0 and finite

@@ -319,6 +319,36 @@ int enqueue_hits(Scene* s, const float* rays, int64_t n, bool quant, bool any, T
     return PRT_OK;
 }
 
+// prt_features / prt_features_device: the argument checks, before any device call
+int check_features_args(Scene* s, const float* cam, int W, int H, int first_sample, int samples, uint32_t flags,
+                        const float* out) {
+    if (!s) return fail(PRT_ERR_ARG, "scene is NULL");
+    if (!cam) return fail(PRT_ERR_ARG, "cam is NULL");
+    if (!out) return fail(PRT_ERR_ARG, "out is NULL");
+    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, "W and H must be >= 1");
+    if (W > 65535 || H > 65535) return fail(PRT_ERR_ARG, "frame larger than 65535 pixels per side");
+    if (samples < 1) return fail(PRT_ERR_ARG, "samples must be >= 1");
+    if (first_sample < 0 || (int64_t)first_sample + samples > INT32_MAX)
+        return fail(PRT_ERR_ARG, "first_sample must be >= 0 and first_sample + samples < 2^31");
+    if (flags & ~PRT_HITS_QUANTIZED) return fail(PRT_ERR_ARG, "prt_features takes only PRT_HITS_QUANTIZED");
+    if (s->need4 > 64) return fail(PRT_ERR_ARG, "BVH4 too deep for the hit-query kernel");
+    return PRT_OK;
+}
+
+// ... and the one launch: the camera and sample keys as prt_camera_rays sets them (frame_params: one frame
+// of `samples` samples from first_sample), the traversal stack sized to the scene's own bound
+int enqueue_features(Scene* s, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
+                     uint32_t flags, int* fault, float* d_out, hipStream_t stream) {
+    const bool quant = (flags & PRT_HITS_QUANTIZED) != 0;
+    TraceParams P;
+    scene_params(s, P);
+    if (quant) P.nodes = (const float4*)s->nodes4q.p;
+    frame_params(P, cam, W, H, 8, 8, DevBuf(), 0, seed, first_sample, samples, 0);   // no tiles: one lane per pixel
+    P.fault = fault;
+    HIP_TRY(launch_features(P, quant, std::max(s->need4, 4), samples, d_out, stream));
+    return PRT_OK;
+}
+
 // a device-wide self-test kernel's n counters
 int selftest(int device, uint64_t* out, int n, hipError_t (*launch)(unsigned long long*, hipStream_t)) {
     if (!out) return fail(PRT_ERR_ARG, "NULL argument");
@@ -490,6 +520,36 @@ int prt_camera_rays(void* scene, const float* cam, int W, int H, int tw, int th,
         q[7] = 0.0f;
     }
     return PRT_OK;
+}
+
+int prt_features(void* scene, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
+                 uint32_t flags, float* out) {
+    auto* s = (Scene*)scene;
+    if (int rc = check_features_args(s, cam, W, H, first_sample, samples, flags, out)) return rc;
+    DeviceGuard g(s->device);
+    const size_t bytes = sizeof(float) * PRT_FEATURE_CHANNELS * (size_t)W * (size_t)H;
+    DevBuf d_out;
+    HIP_TRY(d_out.ensure(bytes));
+    HIP_TRY(hipMemsetAsync(fault_flag(s->work), 0, sizeof(int), s->stream));
+    if (int rc = enqueue_features(s, cam, W, H, first_sample, samples, seed, flags, fault_flag(s->work), (float*)d_out.p,
+                                  s->stream))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return watchdog_error(take_fault_at(s->work));
+}
+
+int prt_features_device(void* scene, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
+                        uint32_t flags, float* d_out, void* stream) {
+    auto* s = (Scene*)scene;
+    if (int rc = check_features_args(s, cam, W, H, first_sample, samples, flags, d_out)) return rc;
+    if ((uintptr_t)d_out & 15) return fail(PRT_ERR_ARG, "d_out must be 16-byte aligned");
+    DeviceGuard g(s->device);
+    // the watchdog flag of the stream's render context: a trip is reported by prt_check_faults
+    RenderCtx* cx;
+    if (int rc = render_ctx(s, (hipStream_t)stream, &cx)) return rc;
+    return enqueue_features(s, cam, W, H, first_sample, samples, seed, flags, fault_flag(cx->work), d_out,
+                            (hipStream_t)stream);
 }
 
 int prt_render_tiles(void* scene, const float* cam, int W, int H, int tw, int th, const int32_t* tile_ids, int n_tiles,

@@ -103,6 +103,11 @@ hipError_t launch_hits(const TraceParams& P, bool quantized, bool any, int stack
 // World.hit_all's shading at the closest hits of launch_hits (prt_hit_all): n x 16 f32
 hipError_t launch_hit_shade(const TraceParams& P, const float4* rays, int64_t n, const int* hit_id, const float* hit_t,
                             float* out16, hipStream_t stream);
+// prt_features: the first-hit features of samples P.s0 .. P.s0 + samples - 1 of every pixel of the P.W x P.H
+// frame (camera and seed as frame_params sets them, j0 = 0) -> out, W x H x 8 f32 [x][y], 16-byte aligned;
+// `stack` LDS traversal stack entries per lane (>= the BVH4's need)
+hipError_t launch_features(const TraceParams& P, bool quantized, int stack, int samples, float* out,
+                           hipStream_t stream);
 // prt_trace_rays: caller rays (n x 8 f32) -> P.rays (d, rng state keyed (seed, i, 0)) and P.ray_o
 // for n_pad >= n items (the padding repeats ray 0)
 hipError_t launch_rays_prep(const TraceParams& P, const float* in8, int64_t n, int64_t n_pad, float4* rays,

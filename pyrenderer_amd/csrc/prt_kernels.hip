@@ -136,6 +136,55 @@ __global__ __launch_bounds__(kBlock) void hit_shade_kernel(TraceParams P, const 
     o4[3] = make_float4(r[12], r[13], r[14], r[15]);
 }
 
+// The denoiser's first-hit features (prt_features): camera_kernel, hits_kernel, hit_shade_kernel
+// and the host's per-pixel sums in one pass, with no per-ray buffer.  One lane owns one pixel; a wave
+// covers an 8 x 8 pixel block (lane = 8 lx + ly: compact primary rays, and the lanes of one lx store a
+// contiguous 256-B run of the [x][y] output), a block 16 x 16 pixels.  Per sample, in sample order
+// from chunk sample 0 (global sample P.s0): the render's own camera ray, the closest hit in PathTracer.trace's
+// primary range, and hit_surface's normal and albedo added to eight f32 sums that start at +0 (a miss
+// adds zeros); then sums 0-5 / samples, t sum / max(hits, 1), hits / samples.  The sample loop's trip
+// count is wave-uniform (the traversal is wave-cooperative); lanes outside the frame leave before it.
+constexpr float kPrimaryTMin = 1e-5f, kPrimaryTMax = 99999.9f;   // core/tracing.py:126-127
+template <bool QN>
+__global__ __launch_bounds__(kBlock) void features_kernel(TraceParams P, int samples, float* __restrict__ out) {
+    extern __shared__ float4 smem[];
+    LdsStack stk{reinterpret_cast<int*>(smem) + threadIdx.x};
+    const int wv = (int)threadIdx.x >> 6, ln = (int)threadIdx.x & 63;
+    const int x = (int)blockIdx.x * 16 + (wv & 1) * 8 + (ln >> 3);
+    const int y = (int)blockIdx.y * 16 + (wv >> 1) * 8 + (ln & 7);
+    if (x >= P.W || y >= P.H) return;
+    Counters cn = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float sum[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sum[k] = 0.0f;
+    for (int s = 0; s < samples; ++s) {
+        uint32_t st;
+        V3 o, d;
+        camera_ray(P, x, y, (uint32_t)s, st, o, d);
+        int hid = -1;
+        float ht = 0.0f;
+        bool hit = traverse_ww4<false, 1, LdsStack, QN>(P.nodes, P.tris, o, d, kPrimaryTMin, kPrimaryTMax, false, stk,
+                                                        hid, ht, cn, nullptr, 0, P.fault, 0, 0, P.guard_trips);
+        sphere_hits(P, o, d, kPrimaryTMin, kPrimaryTMax, false, hit, hid, ht);
+        float term[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) term[k] = 0.0f;
+        if (hit) {
+            const Surface sf = hit_surface<false>(P, P.tri_nm, P.mats, o, d, ht, hid);
+            term[0] = sf.m[0]; term[1] = sf.m[1]; term[2] = sf.m[2];
+            term[3] = sf.n.x; term[4] = sf.n.y; term[5] = sf.n.z;
+            term[6] = ht;
+            term[7] = 1.0f;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) sum[k] = sum[k] + term[k];
+    }
+    const float n = (float)samples, hits = sum[7];
+    float4* o4 = reinterpret_cast<float4*>(out + ((size_t)x * (size_t)P.H + (size_t)y) * 8);
+    o4[0] = make_float4(sum[0] / n, sum[1] / n, sum[2] / n, sum[3] / n);
+    o4[1] = make_float4(sum[4] / n, sum[5] / n, sum[6] / fmaxf(hits, 1.0f), hits / n);
+}
+
 // prt_trace_rays: the caller's rays (o.xyz, -, d.xyz, -) as the trace kernel's primary rays —
 // (d, rng state keyed (seed, i, 0)) and the origin (o, 0) per item; items past n repeat ray 0
 // (the padding to whole 64-item chunks; their radiance is not returned).
@@ -262,6 +311,16 @@ hipError_t launch_hit_shade(const TraceParams& P, const float4* rays, int64_t n,
                             float* out16, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hit_shade_kernel<<<(unsigned)((n + kBlock - 1) / kBlock), kBlock, 0, stream>>>(P, rays, n, hit_id, hit_t, out16);
+    return hipGetLastError();
+}
+
+hipError_t launch_features(const TraceParams& P, bool quantized, int stack, int samples, float* out,
+                           hipStream_t stream) {
+    if (P.W <= 0 || P.H <= 0 || samples <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((P.W + 15) / 16), (unsigned)((P.H + 15) / 16));
+    const size_t smem = (size_t)stack * kBlock * sizeof(int);
+    if (quantized) features_kernel<true><<<grid, kBlock, smem, stream>>>(P, samples, out);
+    else features_kernel<false><<<grid, kBlock, smem, stream>>>(P, samples, out);
     return hipGetLastError();
 }
 

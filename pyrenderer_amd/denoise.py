@@ -1,8 +1,8 @@
 """First-hit feature buffers and the edge-avoiding a-trous denoiser.
 
-`features()` composes per-pixel albedo / shading normal / depth / hit fraction on the host from
-the render's own primary rays (prt_camera_rays) traced with prt_hit_all; `denoise()` runs the
-HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise).  There is no CPU fallback.
+`features()` computes per-pixel albedo / shading normal / depth / hit fraction of the render's own
+primary rays in one HIP kernel (prt_features; `features_device()` leaves them on the device);
+`denoise()` runs the HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise).  There is no CPU fallback.
 """
 import ctypes
 
@@ -20,7 +20,7 @@ EPS_A = 1e-2
 EPS_Z = 1e-2
 
 FEATURE_CHANNELS = 8
-# rays per prt_camera_rays / prt_hit_all call of features(): 2^20 rays are 32 MiB of rays and
+# rays per prt_camera_rays / prt_hit_all call of features_packed_host(): 2^20 rays are 32 MiB of rays and
 # 64 MiB of hit records on the host, whatever the frame size
 CHUNK_RAYS = 1 << 20
 T_MIN, T_MAX = 1e-5, 99999.9   # the primary ray's range in PathTracer.trace (core/tracing.py:126-127)
@@ -37,8 +37,29 @@ def _slots_in_frame(W, H, tile, ids):
 
 
 def features_packed(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_rays=CHUNK_RAYS):
-    """features() for a DeviceScene and a packed camera record."""
-    W, H, tile, samples = int(W), int(H), int(tile), int(samples)
+    """features() for a DeviceScene and a packed camera record: one features_kernel launch
+    (prt_features).  `tile` and `chunk_rays` are still accepted and no longer affect anything: the
+    kernel owns one pixel per lane, with no tile slots and no per-ray buffers to chunk."""
+    if int(samples) < 1:
+        raise ValueError("samples must be >= 1")
+    return ds.features(cam_packed, int(W), int(H), samples=int(samples), seed=seed)
+
+
+def features_device(ds, cam_packed, W, H, d_out_ptr, *, samples=1, first_sample=0, seed=0, quantized=False,
+                    stream_ptr=None):
+    """prt_features_device: the same features into device memory at `d_out_ptr` (W x H x 8 float32, [x][y],
+    16-byte aligned; e.g. a torch tensor's data_ptr()), enqueued on `stream_ptr` (a hipStream_t; None = the
+    null stream) without a host synchronisation: the `d_feat_ptr` of denoise_device and its kin."""
+    ds.features_device(cam_packed, int(W), int(H), d_out_ptr, samples=int(samples), first_sample=int(first_sample),
+                       seed=seed, quantized=quantized, stream_ptr=stream_ptr)
+
+
+def features_packed_host(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_rays=CHUNK_RAYS, first_sample=0):
+    """The slow path, kept as the restatement the tests compare prt_features against: the same features
+    composed on the host, per chunk of `chunk_rays` rays from prt_camera_rays, prt_hit_all and float32
+    sums in sample order over samples first_sample .. first_sample + samples - 1 (what features_packed
+    did before the kernel; DESIGN.md §11 has both times)."""
+    W, H, tile, samples, first_sample = int(W), int(H), int(tile), int(samples), int(first_sample)
     if samples < 1:
         raise ValueError("samples must be >= 1")
     ids = interleaved_tiles(W, H, tile)
@@ -55,7 +76,7 @@ def features_packed(ds, cam_packed, W, H, *, samples=1, seed=0, tile=64, chunk_r
         step = max(1, chunk_rays // n_slots)
         for s0 in range(0, samples, step):
             k = min(step, samples - s0)
-            o, d, _ = ds.camera_rays(cam_packed, W, H, tile, tile, gid, s0, k, seed)
+            o, d, _ = ds.camera_rays(cam_packed, W, H, tile, tile, gid, first_sample + s0, k, seed)
             # slots of partial edge tiles outside the frame carry all-zero rays: they never reach the traversal
             keep = np.tile(inside, k)
             hits = ds.hit_all(o[keep], d[keep], T_MIN, T_MAX).reshape(k, n_in, 16)

@@ -193,6 +193,26 @@ class DeviceScene:
                                         int(first_sample), int(spp), int(seed), N.ptr(out)))
         return out[:, 0:3].copy(), out[:, 4:7].copy(), out[:, 3].copy().view(np.uint32)
 
+    def features(self, cam, W, H, samples=1, first_sample=0, seed=0, quantized=False):
+        """prt_features: the denoiser's first-hit features of samples first_sample .. first_sample +
+        samples - 1 of every pixel, (W, H, 8) float32 [x][y]: albedo.rgb, shading normal.xyz, depth, hit
+        fraction (include/prt.h)."""
+        cam = np.ascontiguousarray(cam, np.float32)
+        out = np.zeros((int(W), int(H), 8), np.float32)
+        N.check(N.lib().prt_features(self.h, N.ptr(cam), int(W), int(H), int(first_sample), int(samples), int(seed),
+                                     N.PRT_HITS_QUANTIZED if quantized else 0, N.ptr(out)))
+        return out
+
+    def features_device(self, cam, W, H, d_out_ptr, samples=1, first_sample=0, seed=0, quantized=False,
+                        stream_ptr=None):
+        """prt_features_device: the same into device memory at d_out_ptr (W x H x 8 f32, 16-byte aligned),
+        enqueued on `stream_ptr` (None = the null stream) without a host synchronisation."""
+        cam = np.ascontiguousarray(cam, np.float32)
+        N.check(N.lib().prt_features_device(self.h, N.ptr(cam), int(W), int(H), int(first_sample), int(samples),
+                                            int(seed), N.PRT_HITS_QUANTIZED if quantized else 0,
+                                            ctypes.c_void_p(d_out_ptr) if d_out_ptr else None,
+                                            ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+
     def closest_hits(self, o, d, tmin, tmax, any_hit=False, quantized=False):
         """World.hit_all on the GPU for arrays of rays: (hit_id, t); id -1 = miss."""
         rays = pack_rays(o, d, tmin, tmax)

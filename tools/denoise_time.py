@@ -7,6 +7,7 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
     python tools/denoise_time.py --mode given --sizes 512 4096      # ... with a given variance plane (prt_denoise_var_given_device)
     python tools/denoise_time.py --mode moments --sizes 512 4096    # prt_moments_add_device over --frames frames (default 8)
     python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
+    python tools/denoise_time.py --mode features --sizes 512 4096   # prt_features_device (1 and 8 samples); host wall clock of both compositions at 512^2
 """
 import argparse
 import json
@@ -27,7 +28,8 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "batching"), default="fixed")
+    ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "batching", "features"),
+                    default="fixed")
     ap.add_argument("--frames", type=int, default=8, help="--mode moments: n_frames per call")
     a = ap.parse_args()
     import torch
@@ -40,6 +42,8 @@ def main():
     base = 512
     if a.mode == "batching":
         return time_batching(a, scene, cam, world)
+    if a.mode == "features":
+        return time_features(a, cam, world)
     noisy = render(scene, cam, spp=8, depth=8, seed=2, resolution=(base, base), world=world)
     feat = D.features(scene, cam, resolution=(base, base), samples=1, seed=2, world=world)
     dev = torch.device("cuda:0")
@@ -147,6 +151,53 @@ def time_moments(a, size, c, d_f, stream):
                           max_ms=round(ms[-1], 4), reps=a.reps, bytes_total=total,
                           implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
                           hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))), flush=True)
+
+
+def time_features(a, cam, world):
+    """prt_features_device (features_kernel) on Cornell with HIP events, per size and for 1 and 8 samples: the
+    kernel's only compulsory traffic is its 32-B store per pixel, so the implied store bandwidth against
+    the HBM peak tells whether the stores or the traversal set the time.  Then the host wall clock at 512^2,
+    one sample, of features_packed (the kernel, synchronous, with its device-to-host copy) and
+    features_packed_host (the composition it replaced), taken in alternation."""
+    import time
+    import torch
+    from pyrenderer_amd import denoise as D
+    ds, cam_packed = world.device_scene(0), cam.convert_to_taichi_camera().packed()
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(dev)
+    for size in a.sizes:
+        d_f = torch.empty((size, size, D.FEATURE_CHANNELS), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize(dev)
+        for samples in (1, 8):
+            def run():
+                D.features_device(ds, cam_packed, size, size, d_f.data_ptr(), samples=samples, seed=2,
+                                  stream_ptr=stream.cuda_stream)
+
+            ms = _median_ms(run, stream, a.warmup, a.reps)
+            ds.check_faults()
+            med = ms[len(ms) // 2]
+            n = size * size
+            total = n * 4 * D.FEATURE_CHANNELS
+            print(json.dumps(dict(what="features_time", size=size, samples=samples, median_ms=round(med, 4),
+                                  min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4), reps=a.reps, bytes_stored=total,
+                                  implied_store_gbs=round(total / (med * 1e-3) / 1e9, 1),
+                                  hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                  mrays_per_s=round(n * samples / (med * 1e-3) / 1e6, 1))), flush=True)
+        del d_f
+    legs = {"features_packed": lambda: D.features_packed(ds, cam_packed, 512, 512, samples=1, seed=2, tile=64),
+            "features_packed_host": lambda: D.features_packed_host(ds, cam_packed, 512, 512, samples=1, seed=2, tile=64)}
+    t = {k: [] for k in legs}
+    warm, reps = 2, 9
+    for i in range(warm + reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            if i >= warm:
+                t[k].append((time.perf_counter() - t0) * 1e3)
+    out = dict(what="features_host_wall_time", size=512, samples=1, reps=reps)
+    for k, v in t.items():
+        out[k + "_ms"] = dict(median=round(sorted(v)[len(v) // 2], 3), min=round(min(v), 3), max=round(max(v), 3))
+    print(json.dumps(out), flush=True)
 
 
 def time_batching(a, scene, cam, world):

@@ -258,9 +258,17 @@ int prt_check_faults(void* scene);
 /* World.hit_all for a batch of rays (mathematics/intersection_taichi.py:238-291):
  * rays = n x 8 f32 (o.xyz, t_min, d.xyz, t_max); hit_id = original triangle index,
  * n_tri + k for sphere k, -1 for a miss; hit_t = distance (0 on a miss).  Closest hit
- * = minimal (t, id) with the strict t_min < t < t_max test; PRT_HITS_ANY returns
- * some hit in range instead (shadow queries).  PRT_HITS_QUANTIZED traverses the
- * quantised BVH4 of large scenes instead of the f32 one (same results). */
+ * among the triangles = minimal (t, id) with the strict t_min < t < t_max test.  The
+ * spheres follow in index order against the triangles' result, by hit_sphere's rules
+ * (intersection_taichi.py:15-36), which differ: the interval is closed at both ends (a
+ * root equal to t_min or to t_max counts; the near root if it lies in the interval, else
+ * the far one), so a sphere at the closest triangle's t takes the hit from it, and of
+ * spheres with equal roots the highest index wins.  A NaN t_max (the reference's shadow
+ * bound when the light sample shares the point's x) accepts no triangle and every
+ * sphere root >= t_min.  PRT_HITS_ANY returns some hit in range instead (shadow
+ * queries): a triangle if one is in range, else the first sphere in index order.
+ * PRT_HITS_QUANTIZED traverses the quantised BVH4 of large scenes instead of the f32
+ * one (same results). */
 #define PRT_HITS_ANY 0x1u
 #define PRT_HITS_QUANTIZED 0x2u
 int prt_closest_hits(void* scene, const float* rays, int64_t n, uint32_t flags, int32_t* hit_id, float* hit_t);

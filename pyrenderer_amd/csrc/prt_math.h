@@ -169,11 +169,20 @@ __device__ __forceinline__ V3 xyz(float4 f) { return v3(f.x, f.y, f.z); }
 // rule (tracing.py:146-148; ad = att * dz, pdf = |cw| * InvPi).  FAST (round 6):
 // on a scene whose albedos lie in [2^-40, 2^40] and whose face normals have length in [0.5, 2]
 // (TraceParams::shade_fast, checked on the host), cw >= 2^-60 alone puts the quotient in div3's
-// no-scaling domain: cw <= |n| |wi| <= 2 (wi normalised; sphere normals (p - c) / r ~ 1), so pdf =
-// cw / pi is normal in [2^-62, 1], ad_i = att_i cw in [2^-100, 2^41] (normal, biased exponent >= 27 >
-// 23, non-zero), ad_i / pdf ~ pi att_i in [2^-39, 2^42] (normal, exponent difference <= 42 < 96), and
-// no quotient is NaN, so the rule does not fire: one compare instead of div3's range test (a NaN cw
-// fails it).
+// no-scaling domain.  Numerator and denominator both carry cw, so the quotient ad_i / pdf ~ pi att_i lies
+// in [2^-39, 2^42] (normal, exponent difference <= 42 < 96) whatever cw is; cw only has to keep the
+// operands themselves in range: pdf = cw / pi >= 2^-62 and ad_i = att_i cw >= 2^-100 are normal (biased
+// exponent >= 27 > 23, non-zero), and for cw < 2^87 ad_i < 2^127 is finite and 1 / pdf normal.  No
+// quotient is NaN, so the rule does not fire: one compare instead of div3's range test (a NaN cw fails
+// it).  A triangle's cw <= |n| |wi| <= 2 (wi normalised).  A sphere's normal (p - c) / r is NOT near unit
+// length and the host checks nothing about it: p = o + d t is rounded at the size of |o| + |d| t and the
+// root's discriminant cancels, so |p - c| reaches about 2^-11 of the ray's length whatever r is.
+// tests/test_hard_spheres.py records lengths of 0.0064 .. 108 (r = 1e-3 hit from 200 away), 0.49 .. 8658
+// (r = 1e-4 from 2000) and 0.019 .. 9.9 (r = 1e-4 from 2), outside [0.5, 2] on 2200, 1558 and 2072 of
+// some 3000 hits each; the bound cw < 2^87 leaves 73 binades above the largest of them, and
+// tests/test_gpu_hard_spheres.py holds every such path to the oracle's bits in every kernel variant.  (A
+// cw of 2^87 takes a sphere of r < 2^-98 of its hit distance: an infinite cw passes the compare, and
+// there the sequence gives NaN where the rule gives inf.)
 template <bool FAST>
 __device__ __forceinline__ V3 lambert_div(V3 ad, float pdf, float cw, int shade_fast) {
     if constexpr (FAST) {
@@ -182,10 +191,18 @@ __device__ __forceinline__ V3 lambert_div(V3 ad, float pdf, float cw, int shade_
     return div3_nan_guard(ad, pdf);
 }
 // The NEE term's division (em * dot1 * dot2) / |p - p2|^2 (tracing.py:92-108).  FAST (round 6): under
-// shade_fast (above) em_i in [2^-40, 2^40] and dot1, dot2 <= 2 (unit-ish w, normals of length <= 2), so
-// with dot1, dot2 >= 2^-20 and sl in [2^-40, 2^40] the numerators lie in [2^-81, 2^42] (normal, biased
-// exponent >= 46), sl and 1 / sl are normal, the quotients lie in [2^-121, 2^82] and the exponent
-// difference is <= 82 < 96: div3's no-scaling domain with four compares instead of div3's range test.
+// shade_fast (above) em_i in [2^-40, 2^40] and dot2 <= 2 (unit-ish w, the light triangle's normal of length
+// <= 2), and dot1 <= |n| with |n| <= 2 at a triangle, so with dot1, dot2 >= 2^-20 and sl in [2^-40, 2^40]
+// the numerators lie in [2^-81, 2^42] (normal, biased exponent >= 46), sl and 1 / sl are normal, the
+// quotients lie in [2^-121, 2^82] and the exponent difference is <= 82 < 96: div3's no-scaling domain
+// with four compares instead of div3's range test.  At a sphere dot1 <= |n| has no such bound (see
+// lambert_div); every factor of |n| adds to the numerator alone, so the same argument holds for |n| <=
+// 2^13 (numerators below 2^55, quotients below 2^95, exponent difference <= 95) and, with the rows and
+// distances a scene really has, far beyond: the largest numerator is max(em_i) dot1 dot2, and the
+// margin is 96 - log2 of that over sl.  The longest normal tests/test_hard_spheres.py records is 8658 =
+// 2^13.1, on rows of em = 1 at sl > 2^-7 (exponent difference <= 22); tests/test_gpu_hard_spheres.py
+// holds those paths to the oracle's bits.  Beyond the margin the sequence still divides correctly
+// unless an intermediate of it leaves the normal range, which is what v_div_scale exists for.
 template <bool FAST>
 __device__ __forceinline__ V3 nee_div(V3 a, float sl, float dot1, float dot2, int shade_fast) {
     if constexpr (FAST) {

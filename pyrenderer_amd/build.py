@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libprt.so")
 SOURCES = ["prt_kernels.hip", "prt_plan.cpp", "prt_scene.cpp", "prt_capi.cpp", "prt_multi.cpp", "prt_bvh.cpp",
-           "prt_trace_pool.hip"]
+           "prt_bvh4.cpp", "prt_trace_pool.hip"]
 # per-unit extra flags: the pooled-shadow kernel is register-allocated with LLVM's AMDGPU
 # pressure trackers (4 instead of 39 spilled VGPRs at 7 waves/SIMD; prt_trace_pool.hip)
 UNIT_FLAGS = {"prt_trace_pool.hip": ["-mllvm", "--amdgpu-use-amdgpu-trackers"]}
@@ -26,7 +26,7 @@ TRACE_INST = "prt_trace_inst.hip"
 TRACE_SETS = [(s, t) for s in (4, 10, 16, 32) for t in (0, 1)]
 # prt_device.h is the umbrella over the device code's headers by role (math, traversal, shared shading,
 # the two trace kernels, the variant table); prt_host.h / prt_plan.h are the host units' 
-HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_host.h", "prt_plan.h", "prt_device.h", "prt_math.h", "prt_traverse.h", "prt_shade.h",
+HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_bvh_util.h", "prt_host.h", "prt_plan.h", "prt_device.h", "prt_math.h", "prt_traverse.h", "prt_shade.h",
            "prt_trace.h", "prt_pool.h", "prt_variants.h"]
 # the denoiser: units of their own, compiled with the same FLAGS and linked into
 # libprt.so.  They include none of HEADERS and nothing above includes theirs, so they cannot change

@@ -23,6 +23,8 @@ constexpr int kTriF4 = 3;  // (v0, id bits) (e1, 0) (e2, 0)
 inline int32_t leaf_ref(int64_t first, int count) {
     return -(int32_t)(((first << 3) | (int64_t)(count - 1)) + 1);
 }
+inline int64_t leaf_first(int32_t ref) { return (-(int64_t)ref - 1) >> 3; }
+inline int leaf_count(int32_t ref) { return (int)((-(int64_t)ref - 1) & 7) + 1; }
 
 struct BvhHost {
     std::vector<float> nodes;      // n_nodes * 16

@@ -46,6 +46,10 @@ def test_config4_tree_shape(c4_tree):
     n = tv.shape[0]
     assert n == 1_000_044
     assert b.n_tri == order.shape[0] and b.n_nodes == nodes.shape[0] and 1 <= b.depth <= 64   # n_tri: references
+    # the tree itself (tests/test_bvh_pinned.py pins the small ones byte for byte): references, nodes, depth,
+    # leaves and prt_bvh_info's info[5] = SAH cost x 1000, of the default large-scene build
+    assert (b.n_tri, b.n_nodes, b.depth, b.n_leaves) == (1_138_436, 583_318, 27, 583_319)
+    assert round(b.sah_cost * 1000) == 244_325
     # spatial splits duplicate some references (budget 1.3 x): every triangle at least once
     assert np.bincount(order, minlength=n).min() >= 1 and n < order.shape[0] <= 1.3 * n + 1
     # each reference record is its whole triangle: v0 and the f32 edges, id bits in v0.w

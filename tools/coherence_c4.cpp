@@ -4,7 +4,7 @@
 // 27.4 L1 accesses per vector-memory instruction, profiles/r05/final/pmc_mem_c4/): a wave's node load
 // costs one tag lookup per DISTINCT line its active lanes touch.  This model prices a ray-sorting
 // stage on that metric before anything is built: it builds the library's BVH (pyrenderer_amd/csrc/
-// prt_bvh.cpp: SBVH + treelets + 64 bins, BVH4 collapse, 64-B quantised nodes) of the 1,000,044-
+// prt_bvh.cpp: SBVH + treelets + 64 bins; prt_bvh4.cpp: BVH4 collapse, 64-B quantised nodes) of the 1,000,044-
 // triangle scene, walks every ray of tools/c4_rays.py through the BVH4 in the kernel's visiting order
 // (closest hit: nearest hit child first; shadow: farthest first, stop at the first hit; prune by the
 // best t), and then forms waves of 64 rays under several schedules, advancing each lane through its
@@ -18,7 +18,7 @@
 //           the origin in a 2^10-cell grid per axis) — a sorted extension-ray stage over N-ray windows
 //
 //   g++ -O2 -std=c++17 -I pyrenderer_amd/csrc tools/coherence_c4.cpp pyrenderer_amd/csrc/prt_bvh.cpp \
-//       -o build/coherence_c4
+//       pyrenderer_amd/csrc/prt_bvh4.cpp -o build/coherence_c4
 //   build/coherence_c4 /tmp/c4_rays_soup.f32 /tmp/c4_rays.f32  > profiles/r06/coherence_c4/model.json
 #include <algorithm>
 #include <cmath>

@@ -4,13 +4,13 @@
 // The pooled kernel reads a node's octant copy from LDS as seven ds_read_b128 (six f32 plane vectors and
 // the refs).  f16 planes, rounded outward (lo down, hi up) and consumed by v_fma_mix_f32 at no extra
 // VALU, would make it four reads.  That pays only if the looser boxes add few visits.  This tool builds
-// the library's tree for the scene soup (prt_bvh.cpp: build_bvh + collapse_bvh4), walks every ray of
+// the library's tree for the scene soup (prt_bvh.cpp build_bvh + prt_bvh4.cpp collapse_bvh4), walks every ray of
 // tools/c4_rays.py --scene cornell in the kernel's order (closest hit: nearest child first; shadow:
 // first hit ends the query) through the f32 boxes and through the f16-rounded ones, and counts node
 // visits and triangle tests per ray.
 //
 //   g++ -O2 -fopenmp -std=c++17 -I pyrenderer_amd/csrc tools/lds_f16_model.cpp pyrenderer_amd/csrc/prt_bvh.cpp \
-//       -o build/lds_f16_model
+//       pyrenderer_amd/csrc/prt_bvh4.cpp -o build/lds_f16_model
 //   python tools/c4_rays.py --scene cornell --x0 0 --y0 0 --w 512 --h 512 --out /tmp/cb_rays.f32
 //   build/lds_f16_model /tmp/cb_rays_soup.f32 /tmp/cb_rays.f32
 #include <algorithm>

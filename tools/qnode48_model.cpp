@@ -9,12 +9,12 @@
 // node keeps the planes and the origin and has 96 bits for the steps and the refs: refs as two
 // 25-bit bases (inner children, leaf triangles) plus 20 bits of per-slot leaf ends leave 26-30 bits
 // for the steps, i.e. steps rounded up to 8 exponent + m mantissa bits, and possibly origins rounded
-// down to k fewer mantissa bits.  This tool builds the library's config-4 tree (prt_bvh.cpp),
+// down to k fewer mantissa bits.  This tool builds the library's config-4 tree (prt_bvh*.cpp),
 // re-quantises it per candidate encoding and walks every ray of tools/c4_rays.py in the kernel's
 // visiting order, counting node visits and triangle tests per ray.
 //
 //   g++ -O2 -fopenmp -std=c++17 -I pyrenderer_amd/csrc tools/qnode48_model.cpp pyrenderer_amd/csrc/prt_bvh.cpp \
-//       -o build/qnode48_model
+//       pyrenderer_amd/csrc/prt_bvh4.cpp -o build/qnode48_model
 //   build/qnode48_model /tmp/c4_rays_soup.f32 /tmp/c4_rays.f32 > profiles/r06/qnode48/model.json
 #include <algorithm>
 #include <cmath>
@@ -66,7 +66,7 @@ struct Enc { const char* name; int step_mant; int origin_drop; bool fit = false;
 
 struct QNode { float origin[3], step[3]; uint8_t lo[3][4], hi[3][4]; int32_t ref[4]; };
 
-// prt_bvh.cpp quantize_bvh4 with the step / origin rounding of `e`
+// prt_bvh4.cpp quantize_bvh4 with the step / origin rounding of `e`
 std::vector<QNode> quantize(const prt::Bvh4Host& b4, float pad, const Enc& e) {
     std::vector<QNode> out((size_t)b4.n_nodes);
     const double margin = 2.0 * (double)pad;

@@ -1,6 +1,6 @@
 // bvh_check — host driver for the sanitizer build of libprt's BVH builder (VERDICT r05
-// item 4).  pyrenderer_amd/csrc/prt_bvh.cpp is pure C++ (standard library + prt_internal.h), so
-// tools/sanitize/Makefile compiles it with g++ -fsanitize=address,undefined,float-cast-overflow
+// item 4).  pyrenderer_amd/csrc/prt_bvh.cpp and prt_bvh4.cpp are pure C++ (standard library +
+// prt_internal.h + prt_bvh_util.h), so tools/sanitize/Makefile compiles them with g++ -fsanitize=address,undefined,float-cast-overflow
 // next to this driver, which runs the whole host pipeline a scene takes in prt_scene_create —
 // binned-SAH BVH2 with spatial splits and treelet restructuring (build_bvh), the SAH-optimal BVH4
 // collapse (collapse_bvh4) and the 8-bit quantisation (quantize_bvh4) — and checks the results
@@ -17,7 +17,10 @@
 //
 //   bvh_check <soup.f32> [max_leaf]      n x 9 float32 triangle vertices (raw, little endian)
 //   bvh_check --random <n> <seed> [max_leaf]
-// Prints one JSON line; exit status 0 = every check passed.
+// Prints one JSON line; exit status 0 = every check passed.  The line also pins the trees: FNV-1a-64
+// digests of the raw bytes of the five arrays a scene uploads (nodes2, tris, order, nodes4, nodes4q)
+// next to every integer statistic, which tests/test_bvh_pinned.py compares with
+// tests/golden/bvh_trees.json — a valid but different tree passes every check above and fails there.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -59,6 +62,15 @@ struct Box {
         return true;
     }
 };
+
+// FNV-1a, 64 bit (offset basis 0xcbf29ce484222325, prime 0x100000001b3) over raw bytes
+template <class T>
+unsigned long long fnv1a64(const std::vector<T>& v) {
+    unsigned long long h = 0xcbf29ce484222325ull;
+    const unsigned char* p = reinterpret_cast<const unsigned char*>(v.data());
+    for (size_t i = 0; i < v.size() * sizeof(T); ++i) { h ^= p[i]; h *= 0x100000001b3ull; }
+    return h;
+}
 
 int32_t ibits(float f) { int32_t v; std::memcpy(&v, &f, 4); return v; }
 uint32_t ubits(float f) { uint32_t v; std::memcpy(&v, &f, 4); return v; }
@@ -125,6 +137,7 @@ int main(int argc, char** argv) {
     std::vector<int> reached((size_t)n2, 0), slot_seen((size_t)n_ref, 0);
     std::vector<Box> slot_box((size_t)n_ref);
     std::unordered_map<int32_t, Box> leaf_box;   // leaf ref -> its box (BVH4 check)
+    std::vector<int32_t> leaf_at((size_t)n_ref, 0);   // first slot of a leaf -> its ref (< 0)
     reached[0] = 1;
     for (int64_t i = 0; i < n2; ++i) {
         const float* nd = b2.nodes.data() + 16 * i;
@@ -142,11 +155,12 @@ int main(int argc, char** argv) {
                 CHECK(cb.contains(child2(cn, 0)) && cb.contains(child2(cn, 1)), "node %d not nested in %lld", r,
                       (long long)i);
             } else {
-                const int64_t v = -(int64_t)r - 1, first = v >> 3, cnt = (v & 7) + 1;
+                const int64_t first = prt::leaf_first(r), cnt = prt::leaf_count(r);
                 CHECK(cnt <= prt::kMaxLeaf && first >= 0 && first + cnt <= n_ref, "leaf %lld+%lld", (long long)first,
                       (long long)cnt);
                 if (first < 0 || first + cnt > n_ref) continue;
                 leaf_box[r] = cb;
+                leaf_at[(size_t)first] = r;
                 for (int64_t s = first; s < first + cnt; ++s) { slot_seen[(size_t)s]++; slot_box[(size_t)s] = cb; }
             }
         }
@@ -224,10 +238,16 @@ int main(int argc, char** argv) {
                 for (int c = 0; c < 4; ++c)
                     CHECK(cb.contains(child4(r, c)), "BVH4 node %d child %d outside its box", r, c);
             } else {
-                leaf_seen[r]++;
-                auto lb = leaf_box.find(r);
-                CHECK(lb != leaf_box.end(), "BVH4 leaf ref %d is no BVH2 leaf", r);
-                if (lb != leaf_box.end()) CHECK(cb.contains(lb->second), "BVH4 leaf %d box smaller than BVH2's", r);
+                // one BVH2 leaf, or (PRT_DP_LEAF > 0) the consecutive BVH2 leaves of a merged subtree
+                const int64_t end = prt::leaf_first(r) + prt::leaf_count(r);
+                int64_t s = prt::leaf_first(r);
+                while (s >= 0 && s < end && s < n_ref && leaf_at[(size_t)s] != 0) {
+                    const int32_t l = leaf_at[(size_t)s];
+                    leaf_seen[l]++;
+                    CHECK(cb.contains(leaf_box[l]), "BVH4 leaf %d box smaller than BVH2 leaf %d's", r, l);
+                    s += prt::leaf_count(l);
+                }
+                CHECK(s == end, "BVH4 leaf ref %d is no run of BVH2 leaves", r);
             }
         }
     }
@@ -240,6 +260,7 @@ int main(int argc, char** argv) {
     // the traversal stack: the sentinel, the entries every ancestor level may have pushed, and the
     // <= 3 slots a visit writes above the top (collapse_bvh4's bound; the LDS kernels size to it)
     CHECK(b4.stack_need >= 1 + max_anc + 3, "stack_need %d below 1 + %d + 3", b4.stack_need, max_anc);
+    CHECK(b4.depth == max_depth4, "BVH4 depth %d, deepest node at %d", b4.depth, max_depth4);
 
     // ---- quantised BVH4
     std::vector<float> q4;
@@ -264,10 +285,16 @@ int main(int argc, char** argv) {
         }
     }
 
+    uint64_t sah_bits;
+    std::memcpy(&sah_bits, &b2.sah_cost, 8);
     std::printf("{\"triangles\": %lld, \"references\": %lld, \"duplicates\": %lld, \"bvh2_nodes\": %lld, "
-                "\"bvh2_depth\": %d, \"bvh4_nodes\": %lld, \"bvh4_depth\": %d, \"stack_need\": %d, "
-                "\"sah\": %.4f, \"spatial_splits\": %lld, \"failures\": %d}\n",
-                (long long)n_tri, (long long)n_ref, (long long)dup, (long long)n2, b2.depth, (long long)n4,
-                max_depth4, b4.stack_need, b2.sah_cost, (long long)b2.n_spatial, g_fail);
+                "\"bvh2_depth\": %d, \"leaves\": %lld, \"bvh4_nodes\": %lld, \"bvh4_depth\": %d, \"stack_need\": %d, "
+                "\"sah\": %.4f, \"sah_bits\": \"%016llx\", \"pad_bits\": \"%08x\", \"spatial_splits\": %lld, "
+                "\"nodes2\": \"%016llx\", \"tris\": \"%016llx\", \"order\": \"%016llx\", \"nodes4\": \"%016llx\", "
+                "\"nodes4q\": \"%016llx\", \"failures\": %d}\n",
+                (long long)n_tri, (long long)n_ref, (long long)dup, (long long)n2, b2.depth, (long long)b2.n_leaves,
+                (long long)n4, b4.depth, b4.stack_need, b2.sah_cost, (unsigned long long)sah_bits, ubits(b2.pad),
+                (long long)b2.n_spatial, fnv1a64(b2.nodes), fnv1a64(b2.tris), fnv1a64(b2.order), fnv1a64(b4.nodes),
+                fnv1a64(q4), g_fail);
     return g_fail ? 1 : 0;
 }

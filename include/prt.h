@@ -340,16 +340,59 @@ int prt_scene_kernel(void* scene, int32_t* out4);
 int prt_launch_kernel(void* scene, int64_t n_items, uint32_t flags, int32_t* out4);
 /* counters of the last render call made with PRT_FLAG_STATS (synchronises) */
 int prt_last_stats(void* scene, uint64_t* stats4);
-/* diagnostic words of the same call (16 x u64): the 4 counters above, then
- * wave-level shader clocks spent in work refill / traversal / shading, wave
- * loop iterations, and active lanes summed over iterations; [11] [12] lane-level
- * inner / leaf traversal trips, [13] deepest traversal stack, [14] samples whose
- * radiance came out NaN or infinite (failure detection; 0 for a sound scene), [15]
- * wave-level triangle-loop trips (max leaf size over the lanes of each leaf trip) */
+/* Diagnostic words (u64) of the same call, written by the trace kernels' PRT_FLAG_STATS builds.  Words
+ * 17.. and 24.. hold different things depending on which kernel ran: the phase-aligned kernel
+ * (trace_kernel; variants 1-6) or the pooled one (trace_kernel_pool; variants 7, 8). */
+#define PRT_DIAG_NODES 0          /* the four counters of prt_last_stats: BVH node visits, */
+#define PRT_DIAG_TRIS 1           /* triangle tests, */
+#define PRT_DIAG_EXT 2            /* extension queries, */
+#define PRT_DIAG_SHADOW 3         /* shadow queries */
+/* 4..10, trace_kernel only: wave-level shader clocks spent in work refill / traversal / shading, wave loop
+ * iterations, active lanes summed over iterations, wave-level inner / leaf traversal trips */
+#define PRT_DIAG_CLK_REFILL 4
+#define PRT_DIAG_CLK_TRAV 5
+#define PRT_DIAG_CLK_SHADE 6
+#define PRT_DIAG_WAVE_ITERS 7
+#define PRT_DIAG_ACTIVE_LANES 8
+#define PRT_DIAG_WAVE_INNER 9
+#define PRT_DIAG_WAVE_LEAF 10
+#define PRT_DIAG_LANE_INNER 11    /* trace_kernel: lane-level inner traversal trips */
+#define PRT_DIAG_LANE_LEAF 12     /* ... and leaf trips */
+#define PRT_DIAG_MAX_STACK 13     /* deepest traversal stack (both kernels) */
+#define PRT_DIAG_NONFINITE 14     /* samples whose radiance came out NaN or infinite (failure detection; 0 for
+                                   * a sound scene; both kernels) */
+#define PRT_DIAG_WAVE_TRI 15      /* trace_kernel: wave-level triangle-loop trips (max leaf size over the lanes
+                                   * of each leaf trip) */
+#define PRT_DIAG_MAX_QUERY 16     /* most BVH node visits of one query (both kernels) */
+/* 17..21 after trace_kernel's phase-aligned schedule: wave clocks of the extension / shadow iterations,
+ * their counts, and the lanes that queried in the shadow ones */
+#define PRT_DIAG_PHASE 17
+#define PRT_DIAG_PHASE_WORDS 5
+/* 17..20 after trace_kernel_pool: wave E iterations, wave S iterations, lanes of the S iterations, shadow
+ * rays answered by the light-triangle test */
+#define PRT_DIAG_POOL 17
+#define PRT_DIAG_POOL_WORDS 4
+/* trace_kernel: queries with > 1000 node visits, and from PRT_DIAG_OUTLIER_LOG the first 16 of them in
+ * records of 8 words: o.xyz, d.xyz, t_max (f32 bits), query kind << 32 | node visits */
+#define PRT_DIAG_OUTLIERS 23
+#define PRT_DIAG_OUTLIER_LOG 24
+#define PRT_DIAG_OUTLIER_RECORDS 16
+#define PRT_DIAG_OUTLIER_WORDS 8
+/* trace_kernel_pool built with -DPRT_POOL_CLOCKS (tools/pool_clocks.py) instead: wave-level cycles in E's
+ * shading and enqueue, at the barrier, in S, (unused), in the refill, in the extension traversal */
+#define PRT_DIAG_POOL_CLOCKS 24
+#define PRT_DIAG_POOL_CLOCKS_WORDS 6
+/* trace_kernel_pool's lane table (tools/lane_table.py): (wave trips, lane trips) of E inner visits, E
+ * triangle tests, S inner visits, S triangle tests, the shading block, the Lambert block, the loop
+ * iteration and the resolve of shadow answers */
+#define PRT_DIAG_LANE_TABLE 160
+#define PRT_DIAG_LANE_TABLE_WORDS 16
+#define PRT_DIAG_SUSPENDED 176    /* trace_kernel_pool: extension queries suspended, */
+#define PRT_DIAG_RESUMED 177      /* ... and resumed */
+#define PRT_DIAG_WORDS 192        /* words kept per scene; prt_diag_words reads 0 past them */
+/* the first 16 diagnostic words */
 int prt_diag_stats(void* scene, uint64_t* stats16);
-/* the same diagnostic words and any beyond them, n of them (unknown words read 0):
- * [16] most BVH node visits of one query, [23] queries with > 1000 node visits, [24 + 8k ..]
- * the first 16 of them: o.xyz, d.xyz, t_max (f32 bits), query kind << 32 | node visits */
+/* the first n diagnostic words (words past PRT_DIAG_WORDS read 0) */
 int prt_diag_words(void* scene, uint64_t* out, int n);
 
 /* ------------------------------------------------------------ denoise ----

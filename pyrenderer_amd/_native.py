@@ -18,7 +18,7 @@ PRT_FLAG_STATS = 0x1
 PRT_FLAG_TIME = 0x2
 PRT_FLAG_NO_PRIMARY_KERNEL = 0x4   # rejected (PRT_ERR_UNSUP) since round 4: camera rays come from the camera kernel
 PRT_FLAG_MIS_NEE = 0x8
-# trace-kernel variant ids 1..VAR_LAST of the reference estimator (pyrenderer_amd/csrc/prt_kernels.h
+# trace-kernel variant ids 1..VAR_LAST of the reference estimator (pyrenderer_amd/csrc/prt_variant_table.h
 # kVar*); the MIS direct-lighting estimator's variants (PRT_FLAG_MIS_NEE) follow
 VAR_LDS = 1           # LDS-resident scene, phase-aligned schedule, >= 7 waves/SIMD
 VAR_LDS_ANY_OCC = 2   # ... without the occupancy target
@@ -33,6 +33,41 @@ VAR_POOL = (VAR_LDS_POOL, VAR_LDS_POOL6)
 VAR_LAST = 8
 PRT_HITS_ANY = 0x1
 PRT_HITS_QUANTIZED = 0x2
+# the diagnostic words of a PRT_FLAG_STATS launch (DeviceScene.diag_stats / diag_words): include/prt.h
+# PRT_DIAG_*, value for value (tests/test_abi.py compares them); the comments there say which kernel
+# writes the ranges that overlap
+PRT_DIAG_NODES = 0
+PRT_DIAG_TRIS = 1
+PRT_DIAG_EXT = 2
+PRT_DIAG_SHADOW = 3
+PRT_DIAG_CLK_REFILL = 4
+PRT_DIAG_CLK_TRAV = 5
+PRT_DIAG_CLK_SHADE = 6
+PRT_DIAG_WAVE_ITERS = 7
+PRT_DIAG_ACTIVE_LANES = 8
+PRT_DIAG_WAVE_INNER = 9
+PRT_DIAG_WAVE_LEAF = 10
+PRT_DIAG_LANE_INNER = 11
+PRT_DIAG_LANE_LEAF = 12
+PRT_DIAG_MAX_STACK = 13
+PRT_DIAG_NONFINITE = 14
+PRT_DIAG_WAVE_TRI = 15
+PRT_DIAG_MAX_QUERY = 16
+PRT_DIAG_PHASE = 17
+PRT_DIAG_PHASE_WORDS = 5
+PRT_DIAG_POOL = 17
+PRT_DIAG_POOL_WORDS = 4
+PRT_DIAG_OUTLIERS = 23
+PRT_DIAG_OUTLIER_LOG = 24
+PRT_DIAG_OUTLIER_RECORDS = 16
+PRT_DIAG_OUTLIER_WORDS = 8
+PRT_DIAG_POOL_CLOCKS = 24
+PRT_DIAG_POOL_CLOCKS_WORDS = 6
+PRT_DIAG_LANE_TABLE = 160
+PRT_DIAG_LANE_TABLE_WORDS = 16
+PRT_DIAG_SUSPENDED = 176
+PRT_DIAG_RESUMED = 177
+PRT_DIAG_WORDS = 192
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int

@@ -25,9 +25,10 @@ TRACE_INST = "prt_trace_inst.hip"
 # part), 32 (deeper LDS-resident BVHs, PRT_SPILL_LDS=32)
 TRACE_SETS = [(s, t) for s in (4, 10, 16, 32) for t in (0, 1)]
 # prt_device.h is the umbrella over the device code's headers by role (math, traversal, shared shading,
-# the two trace kernels, the variant table); prt_host.h / prt_plan.h are the host units' 
+# the two trace kernels, the variant dispatch); prt_host.h / prt_plan.h are the host units'; prt_lds_layout.h
+# and prt_variant_table.h (no HIP include) are read by both sides
 HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_bvh_util.h", "prt_host.h", "prt_plan.h", "prt_device.h", "prt_math.h", "prt_traverse.h", "prt_shade.h",
-           "prt_trace.h", "prt_pool.h", "prt_variants.h"]
+           "prt_trace.h", "prt_pool.h", "prt_variants.h", "prt_lds_layout.h", "prt_variant_table.h"]
 # the denoiser: units of their own, compiled with the same FLAGS and linked into
 # libprt.so.  They include none of HEADERS and nothing above includes theirs, so they cannot change
 # the trace kernels' code: they are dependencies of the build (_stale) but NOT part of kernel_sha(),

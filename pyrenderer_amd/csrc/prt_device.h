@@ -21,10 +21,10 @@
 // by prt_kernels.hip for the hit-query, camera and reduction kernels):
 //   prt_math.h      math, guards, RNG and sampling
 //   prt_traverse.h  stacks and traversal
-//   prt_shade.h     launch parameters, staging and the shading pieces shared by the kernels
+//   prt_shade.h     launch parameters, staging, the chunk claim and the shading pieces shared by the kernels
 //   prt_trace.h     trace_kernel
 //   prt_pool.h      trace_kernel_pool
-//   prt_variants.h  variant table and dispatch
+//   prt_variants.h  launch / occupancy dispatch over the variant table (prt_variant_table.h)
 #pragma clang fp contract(off)
 
 #include "prt_math.h"

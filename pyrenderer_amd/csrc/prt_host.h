@@ -1,6 +1,6 @@
 // prt_host.h — what the host units of libprt's C ABI (include/prt.h) share: the error text, the device
 // buffer / guard types, a scene's device residency with its per-stream render contexts, and the few
-// functions one unit calls in another.  prt_scene.cpp: BVH handles, scene creation, variant choice;
+// functions one unit calls in another.  prt_scene.cpp: BVH handles, scene creation, a scene's variant;
 // prt_capi.cpp: everything that launches on one device; prt_multi.cpp: the RCCL gather.  The
 // arithmetic that needs no GPU is in prt_plan.h.
 #pragma once
@@ -30,10 +30,8 @@ inline int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(PRT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// stats words: nodes, tris, ext, shadow (public) + diagnostic wave clocks
-// (refill, traversal, shading), wave iterations, active lanes at traversal; words 24..151 the outlier
-// log, 160..175 the pooled kernel's lane table (STATS builds)
-constexpr int kStatWords = 192;
+// stats words of a scene (include/prt.h PRT_DIAG_*: what the STATS builds write where)
+constexpr int kStatWords = PRT_DIAG_WORDS;
 
 // Device buffer owned by its holder: freed by release() or, at the latest, by the destructor (the
 // per-call buffers of prt_trace_rays / prt_closest_hits / prt_hit_all are locals, freed on return

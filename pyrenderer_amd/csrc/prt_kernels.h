@@ -3,11 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/prt.h"   // PRT_DIAG_*: the stats words
+#include "prt_lds_layout.h"
+#include "prt_variant_table.h"
+
 namespace prt {
 
 // Everything one trace launch needs, passed by value as the kernel argument.
 struct TraceParams {
-    const float4* nodes;      // BVH2 (4 float4 per node) or BVH4 (8 float4 per node), prt_internal.h
+    const float4* nodes;      // BVH4 (8 float4 per node) or quantised BVH4 (4 float4 per node), prt_internal.h
     const float4* tris;       // BVH order, 3 float4 per triangle: (v0,id) (e1,0) (e2,0)
     const float4* tri_nm;     // original order: (face normal xyz, material id bits)
     const float4* tri_frame;  // original order: rotate_z_to rows (x, z, n) for the face normal and its negation
@@ -27,7 +31,7 @@ struct TraceParams {
     int leaf_exit;            // ... and leave it when <= this many lanes still hold a leaf
     int resume_min;           // resume variants: leave the traversal loop below this many active lanes
     int* spill;               // spill variants: per-lane stack entries beyond the LDS part (stride = grid threads)
-    const float4* rays;       // primary rays of this launch from camera_kernel, or null (generated in the refill)
+    const float4* rays;       // primary rays of this launch (camera_kernel's, or rays_prep_kernel's caller rays): never null
     const float4* ray_o;      // prt_trace_rays: per-item ray origin (rays_kernel), or null (the camera's cam_o)
     float cam_o[3], cam_k[3];
     int W, H;                 // full frame (u = (x + r) / (W - 1))
@@ -46,7 +50,7 @@ struct TraceParams {
     uint64_t n_items;         // n_slots * samples in this chunk
     uint32_t* work;           // device work counter (zeroed before the launch)
     float* out;               // n_items x 3 radiance, item = (s - s0) * n_slots + slot
-    unsigned long long* stats;  // 4 counters (nodes, tris, ext queries, shadow queries)
+    unsigned long long* stats;  // PRT_DIAG_WORDS diagnostic words (include/prt.h PRT_DIAG_*), written by STATS builds
     int n_node_f4, n_tri_f4;  // scene sizes in float4 (LDS-resident variant)
     int n_mat, n_lt;          // materials (8 floats each), emitter triangles
     int n_tri;                // hit ids >= n_tri are spheres
@@ -65,36 +69,11 @@ struct TraceParams {
     int pool_resume_min;      // pool kernel: leave the extension traversal once at most this many lanes still traverse and
                               // resume the unfinished queries in the next iteration (0: off; env PRT_POOL_RESUME_MIN)
 };
+// the sizes of P's scene that the LDS layouts depend on (prt_lds_layout.h), with `stack` entries per lane
+PRT_HD inline LdsSizes lds_sizes(const TraceParams& P, int stack) {
+    return LdsSizes{P.n_node_f4, P.n_tri_f4, P.n_tri, P.n_mat, P.n_lt, P.n_light, stack};
+}
 
-// trace kernel variants (selectable at run time through PRT_FLAG_VARIANT).  All run the
-// while-while BVH4 traversal (prt_traverse.h traverse_ww4) and give bit-identical images;
-// the measured history of the variants this set replaced is in DESIGN.md §2.
-constexpr int kVarLds = 1;         // LDS-resident scene, phase-aligned ext/shadow iterations, >= 7 waves/SIMD
-                                   // (72 VGPRs: C2 4.40 -> 4.23 ms against the 6-wave build)
-constexpr int kVarLdsAnyOcc = 2;   // ... no occupancy target (LDS scenes too large for 6 blocks per CU)
-constexpr int kVarGlobal = 3;      // global scene: quantised 64-B nodes, LDS stack + global spill area,
-                                   // suspended traversal tails, >= 6 waves/SIMD
-// estimator variants: the reference's unused MIS direct lighting (PRT_FLAG_MIS_NEE)
-constexpr int kVarLdsMis = 4;      // LDS scene, mixed schedule, >= 6 waves/SIMD
-constexpr int kVarGlobalMis = 5;   // kVarGlobal + MIS
-constexpr int kVarLds6 = 6;        // kVarLds built for >= 6 waves/SIMD (80 VGPRs): LDS scenes whose copy
-                                   // fits six blocks per CU but not seven
-constexpr int kVarLdsPool = 7;     // LDS-resident scene, block-pooled shadow queries (trace_kernel_pool),
-                                   // >= 7 waves/SIMD; the LDS stack size is P.lds_stack
-constexpr int kVarLdsPool6 = 8;    // kVarLdsPool built for >= 6 waves/SIMD (80 VGPRs)
-constexpr int kVarFirst = 1;
-constexpr int kVarLast = 8;
-// ids 9-14 were the round-5 schedules of trace_kernel_pool that did not become the default (fused,
-// packed leaf trips, split arrival; DESIGN.md §9, logs in profiles/r05/{fused,pack,split}/): removed
-// in round 6, the C-ABI rejects them as unknown variants
-bool variant_pool(int var);
-bool variant_mis(int var);
-bool variant_uses_lds(int var);
-bool variant_spills(int var);
-bool variant_quantized(int var);
-
-int stack_variant(int bvh_depth);
-size_t trace_smem_bytes(int stack, int var, const TraceParams& P);
 // camera rays of a launch: rays = (d, rng state); ray_o = per-ray origins (cameras other than the affine
 // pinhole; null otherwise)
 hipError_t launch_camera(const TraceParams& P, float4* rays, float4* ray_o, hipStream_t stream);
@@ -112,7 +91,6 @@ hipError_t launch_features(const TraceParams& P, bool quantized, int stack, int 
 // for n_pad >= n items (the padding repeats ray 0)
 hipError_t launch_rays_prep(const TraceParams& P, const float* in8, int64_t n, int64_t n_pad, float4* rays,
                             float4* ray_o, hipStream_t stream);
-size_t lds_scene_bytes(const TraceParams& P);  // LDS-resident scene + shading data
 hipError_t launch_trace(const TraceParams& P, int stack, int var, int grid, bool stats, hipStream_t stream);
 // per-frame sample-order sums of one chunk of launch samples [j0, j0 + n): frames f0 .. f0 + n_frames - 1
 // (frame f = launch samples [f spp, (f + 1) spp)) into acc + f pitch (floats, >= 3 n_slots), in one launch

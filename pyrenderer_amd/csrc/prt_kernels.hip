@@ -17,6 +17,7 @@
 #pragma clang fp contract(off)
 
 #include "prt_device.h"
+#include "prt_plan.h"
 
 namespace prt {
 
@@ -255,34 +256,8 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(const float* __restrict_
 
 }  // namespace
 
-// LDS stack entries of the trace kernel for a BVH4 needing need = depth + 1 entries
-// (collapse_bvh4's bound; scenes needing more than 32 take the spill-stack global variant)
-int stack_variant(int depth) { return depth + 1 <= 10 ? 10 : depth + 1 <= 16 ? 16 : 32; }
-
-// LDS-resident scene (prt_trace.h trace_kernel): the BVH4 as 8 octant copies of 7 float4 per
-// node (n_node_f4 counts the 8 float4 of a global BVH4 node), triangles, shading data
-size_t lds_scene_bytes(const TraceParams& P) {
-    return 16 * (7 * (size_t)P.n_node_f4 + P.n_tri_f4 + 7 * (size_t)P.n_tri + 2 * (size_t)P.n_mat + 4 * (size_t)P.n_lt) +
-           4 * ((size_t)P.n_light + 1);
-}
-
-size_t trace_smem_bytes(int stack, int var, const TraceParams& P) {
-    if (variant_pool(var)) {
-        // trace_kernel_pool: 16-bit stacks of P.lds_stack entries, the shadow pool, queue and control
-        // words, then the BVH4 octant copies, triangles and light records (no shading data)
-        return (size_t)P.lds_stack * kBlock * sizeof(short) +
-               16 * (size_t)(kPoolF4 + kQueueF4 + kCtlF4) +
-               16 * (7 * (size_t)P.n_node_f4 + P.n_tri_f4 + 4 * (size_t)P.n_lt + ((size_t)P.n_light + 4) / 4 +
-                     2 * (size_t)P.n_mat);
-    }
-    // traversal stack entries: 16-bit for LDS-resident scenes, 32-bit otherwise
-    size_t b = (size_t)stack * kBlock * (variant_uses_lds(var) ? sizeof(short) : sizeof(int));
-    if (variant_uses_lds(var)) b += lds_scene_bytes(P);
-    return b;
-}
-
 hipError_t launch_trace(const TraceParams& P, int stack, int var, int grid, bool stats, hipStream_t stream) {
-    size_t smem = trace_smem_bytes(stack, var, P);
+    size_t smem = trace_smem_bytes(stack, var, lds_sizes(P, P.lds_stack));
     switch (stack) {
         case 4: return stats ? launch_trace_4_1(P, var, grid, smem, stream) : launch_trace_4_0(P, var, grid, smem, stream);
         case 10: return stats ? launch_trace_10_1(P, var, grid, smem, stream) : launch_trace_10_0(P, var, grid, smem, stream);
@@ -296,7 +271,7 @@ hipError_t launch_hits(const TraceParams& P, bool quantized, bool any, int stack
                        int* hit_id, float* hit_t, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    size_t smem = (size_t)stack * kBlock * sizeof(int);
+    size_t smem = stack32_bytes(stack);
     if (quantized) {
         if (any) hits_kernel<true, true><<<grid, kBlock, smem, stream>>>(P, rays, n, hit_id, hit_t);
         else hits_kernel<true, false><<<grid, kBlock, smem, stream>>>(P, rays, n, hit_id, hit_t);
@@ -318,7 +293,7 @@ hipError_t launch_features(const TraceParams& P, bool quantized, int stack, int 
                            hipStream_t stream) {
     if (P.W <= 0 || P.H <= 0 || samples <= 0) return hipSuccess;
     const dim3 grid((unsigned)((P.W + 15) / 16), (unsigned)((P.H + 15) / 16));
-    const size_t smem = (size_t)stack * kBlock * sizeof(int);
+    const size_t smem = stack32_bytes(stack);
     if (quantized) features_kernel<true><<<grid, kBlock, smem, stream>>>(P, samples, out);
     else features_kernel<false><<<grid, kBlock, smem, stream>>>(P, samples, out);
     return hipGetLastError();
@@ -432,14 +407,6 @@ hipError_t launch_reduce(const float* buf, float* acc, int n_slots, int64_t j0, 
     reduce_kernel<<<grid, kBlock, 0, stream>>>(buf, acc, n_slots, j0, n, spp, f0, pitch, accumulate ? 1 : 0);
     return hipGetLastError();
 }
-
-// look-ups in the variant table (prt_variants.h kVariants); unknown ids answer false
-bool variant_pool(int var) { const Variant* v = find_variant(var); return v && v->pool; }
-bool variant_mis(int var) { const Variant* v = find_variant(var); return v && v->mis; }
-bool variant_uses_lds(int var) { const Variant* v = find_variant(var); return v && v->lds; }
-// the global-scene trace kernels traverse quantised nodes with a spill stack
-bool variant_spills(int var) { const Variant* v = find_variant(var); return v && !v->lds; }
-bool variant_quantized(int var) { return variant_spills(var); }
 
 int trace_blocks_per_cu(int stack, int var, bool stats, size_t smem) {
     switch (stack) {

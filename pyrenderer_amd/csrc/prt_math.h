@@ -16,8 +16,7 @@ constexpr float kPiOver4 = 0.78539816339744830961f;
 constexpr float kTMin = 0.00001f;    // core/tracing.py:127
 constexpr float kTMax = 99999.9f;    // core/tracing.py:127
 constexpr float kGamma = 0x1.000006p+0f;  // f32(1 + 2*GAMMA2_3), bvh_taichi.py:179
-constexpr int kBlock = 256;
-constexpr int kChunk = 64;           // work items per queue refill (one atomic)
+constexpr int kChunk = 64;          // work items per queue refill (one atomic)
 
 struct V3 { float x, y, z; };
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }

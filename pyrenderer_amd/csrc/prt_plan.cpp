@@ -161,6 +161,56 @@ FrameSpan launch_frames(int64_t s0, int64_t n, int64_t spp, int64_t n_frames) {
     return FrameSpan{s0 / spp, std::min<int64_t>(n_frames, (s0 + n + spp - 1) / spp)};
 }
 
+bool variant_pool(int var) { const Variant* v = find_variant(var); return v && v->pool; }
+bool variant_mis(int var) { const Variant* v = find_variant(var); return v && v->mis; }
+bool variant_uses_lds(int var) { const Variant* v = find_variant(var); return v && v->lds; }
+bool variant_spills(int var) { const Variant* v = find_variant(var); return v && !v->lds; }
+bool variant_quantized(int var) { return variant_spills(var); }
+
+int stack_variant(int depth) { return depth + 1 <= 10 ? 10 : depth + 1 <= 16 ? 16 : 32; }
+
+size_t lds_scene_bytes(const LdsSizes& z) {
+    LdsSizes scene = z;
+    scene.stack = 0;
+    return trace_lds(scene).bytes;
+}
+
+size_t trace_smem_bytes(int stack, int var, const LdsSizes& z) {
+    if (variant_pool(var)) return pool_lds(z).bytes;
+    if (!variant_uses_lds(var)) return stack32_bytes(stack);
+    LdsSizes own = z;
+    own.stack = stack;
+    return trace_lds(own).bytes;
+}
+
+// LDS-resident scene: BVH + triangles small enough to sit beside the stack
+constexpr int64_t kLdsSceneBytes = 24 * 1024;
+// ... and whose node indices and leaf references fit the LDS kernels' 16-bit stack entries
+// (inner nodes < 0x7FFF, the sentinel; leaf refs >= -32768)
+bool lds_fits(const LdsSizes& z) {
+    const int64_t n_refs = z.n_tri_f4 / 3;
+    return (int64_t)lds_scene_bytes(z) <= kLdsSceneBytes && z.n_node_f4 / 8 < 0x7FFF && n_refs * 8 <= 32768;
+}
+
+// LDS-resident scene when it fits; the >= 7 (>= 6) waves/SIMD build when seven (six) blocks'
+// LDS still fit one CU (160 KiB), so the occupancy target is not defeated by LDS.
+// Everything else (and BVH4s deeper than the 64-entry LDS stack) takes the global-scene
+// kernel: 64-B quantised nodes, 16-entry LDS stack + spill, suspended traversal tails,
+// >= 6 waves/SIMD (C4: 28.6 ms at 5 waves, 27.2 at 6, 28.6 at 7 with spills).
+// An LDS-resident scene whose pooled-shadow kernel still fits seven blocks per CU takes that kernel
+// (C2 4.06 vs 4.28 ms, C3 73.6 vs 77.5 ms, profiles/r03/pool/) at every launch size: since round 6
+// it also wins the small launches that round 3 left to the phase-aligned kernel (config 1 0.080 vs
+// 0.094 ms per launch; DESIGN.md §2, profiles/r06/kernarg/variants/).
+// The MIS estimator (PRT_FLAG_MIS_NEE) has one variant per scene placement.
+int choose_variant(const LdsSizes& z, int need4, int stack4, bool mis) {
+    const bool lds = lds_fits(z) && stack4;
+    if (mis) return lds ? kVarLdsMis : kVarGlobalMis;
+    if (!lds) return kVarGlobal;
+    if (need4 <= 32 && trace_smem_bytes(16, kVarLdsPool, z) * 7 <= 160 * 1024) return kVarLdsPool;
+    const size_t smem = trace_smem_bytes(stack4, kVarLds, z);
+    return smem * 7 <= 160 * 1024 ? kVarLds : smem * 6 <= 160 * 1024 ? kVarLds6 : kVarLdsAnyOcc;
+}
+
 bool camera_is_fast(const float* cam) {
     bool fin = true;
     for (int i = 0; i < 20; ++i) fin = fin && std::isfinite(cam[i]);

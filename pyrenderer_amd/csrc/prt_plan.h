@@ -1,7 +1,9 @@
 // prt_plan.h — the host arithmetic of libprt that needs no GPU: scene argument checks and packing,
 // environment knobs, tile and window arithmetic, the launch-chunk plan and the camera's host-evaluated
-// terms.  Standard library + prt_internal.h only (no HIP include), plain arrays and small structs in
-// and out, so tools/sanitize/host_check.cpp runs all of it on the CPU under ASan + UBSan.
+// terms, and the launch decisions that depend on a scene's sizes alone (LDS footprints, the variant
+// choice).  Standard library + prt_internal.h, prt_lds_layout.h and prt_variant_table.h only (no HIP
+// include), plain arrays and small structs in and out, so tools/sanitize/host_check.cpp runs all of it
+// on the CPU under ASan + UBSan.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -9,6 +11,8 @@
 #include <vector>
 
 #include "prt_internal.h"
+#include "prt_lds_layout.h"
+#include "prt_variant_table.h"
 
 namespace prt {
 
@@ -57,6 +61,28 @@ ChunkPlan plan_chunks(int64_t T, int64_t n_slots, int64_t bytes_per_sample, size
 // the frames [f0, f1) that the launch samples [s0, s0 + n) overlap (frame f = samples [f spp, (f + 1) spp))
 struct FrameSpan { int64_t f0, f1; };
 FrameSpan launch_frames(int64_t s0, int64_t n, int64_t spp, int64_t n_frames);
+
+// ---- launch decisions that follow from the scene's sizes alone (prt_lds_layout.h, prt_variant_table.h)
+// look-ups in the variant table; unknown ids answer false
+bool variant_pool(int var);
+bool variant_mis(int var);
+bool variant_uses_lds(int var);
+bool variant_spills(int var);      // the global-scene trace kernels traverse quantised nodes with a spill stack
+bool variant_quantized(int var);
+// LDS stack entries of the trace kernel for a BVH4 needing need = depth + 1 entries
+// (collapse_bvh4's bound; scenes needing more than 32 take the spill-stack global variant)
+int stack_variant(int depth);
+// bytes of the LDS-resident scene copy with its shading data (trace_kernel's, without the stacks)
+size_t lds_scene_bytes(const LdsSizes& z);
+// dynamic LDS of a launch of variant `var`: `stack` is the instantiation set's entries per lane, z.stack
+// the pooled kernel's own (TraceParams::lds_stack), which that kernel takes instead
+size_t trace_smem_bytes(int stack, int var, const LdsSizes& z);
+// LDS-resident scene: the copy is small enough to sit beside the stacks, and node indices and leaf
+// references fit the LDS kernels' 16-bit stack entries
+bool lds_fits(const LdsSizes& z);
+// the variant of a launch whose flags name none: need4 = the BVH4's worst-case stack entries (z.stack too),
+// stack4 = its LDS stack instantiation set (0: too deep for one)
+int choose_variant(const LdsSizes& z, int need4, int stack4, bool mis);
 
 // Pinhole camera with an affine matrix (no aperture, last row (0,0,0,1), all finite):
 // the kernels may use the exact gen_ray shortcut (TraceParams::cam_fast) ...

@@ -35,9 +35,7 @@ namespace {
 // two parity-alternating control words pairs (queue length, "alive"), then the scene copy:
 // octant BVH4 nodes, triangles, light triangles and offsets.  Shading data (normals, frames,
 // materials) are read from global memory (L1-resident) to keep seven blocks per CU.
-constexpr int kPoolF4 = 7 * kBlock / 4;        // pool SoA: 7 x 256 f32
-constexpr int kQueueF4 = 2 * kBlock / 16;      // queue: 2 x 256 u8, by iteration parity
-constexpr int kCtlF4 = 3;                      // ctl: 12 words
+// (prt_lds_layout.h pool_lds: the regions' offsets, and kPoolF4, kQueueF4, kCtlF4)
 constexpr int kPoolSPrio = 2;                  // issue priority of the S-phase waves (s_setprio)
 
 // One block barrier per iteration (round 4; round 3's kernel had two: after E and after S, with
@@ -63,28 +61,26 @@ constexpr int kPoolSPrio = 2;                  // issue priority of the S-phase 
 template <bool STATS, int WPE, bool PLAIN>
 __global__ __attribute__((amdgpu_flat_work_group_size(kBlock, kBlock), amdgpu_waves_per_eu(WPE)))
 void trace_kernel_pool(TraceParams P) {
-    constexpr int ctl_f4 = kCtlF4;
     extern __shared__ float4 smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int stack_f4 = P.lds_stack * kBlock * 2 / 16;
+    const PoolLds lay = pool_lds(lds_sizes(P, P.lds_stack));   // prt_lds_layout.h
     LdsStack16A stk = LdsStack16A::at(smem, tid);
     using Stk = decltype(stk);
-    float* pool = reinterpret_cast<float*>(smem + stack_f4);   // [7][256]
-    uint8_t* queue = reinterpret_cast<uint8_t*>(smem + stack_f4 + kPoolF4);
-    uint32_t* ctl = reinterpret_cast<uint32_t*>(smem + stack_f4 + kPoolF4 + kQueueF4);
-    float4* sn = smem + stack_f4 + kPoolF4 + kQueueF4 + ctl_f4;
-    const int n_node4 = P.n_node_f4 / 8;
-    float4* st4 = sn + 56 * n_node4;
-    float4* slv = st4 + P.n_tri_f4;
-    int* slo = reinterpret_cast<int*>(slv + 4 * P.n_lt);
-    float4* smt = slv + 4 * P.n_lt + (P.n_light + 4) / 4;   // materials, after the light offsets
-    copy_octant_nodes(sn, P.nodes, n_node4);
+    float* pool = reinterpret_cast<float*>(smem + lay.pool);   // [7][256]
+    uint8_t* queue = reinterpret_cast<uint8_t*>(smem + lay.queue);
+    uint32_t* ctl = reinterpret_cast<uint32_t*>(smem + lay.ctl);
+    float4* sn = smem + lay.nodes;
+    float4* st4 = smem + lay.tris;
+    float4* slv = smem + lay.light_v;
+    int* slo = reinterpret_cast<int*>(smem + lay.light_off);
+    float4* smt = smem + lay.mats;   // materials, after the light offsets
+    copy_octant_nodes(sn, P.nodes, P.n_node_f4 / 8);
     for (int i = tid; i < P.n_tri_f4; i += kBlock) st4[i] = P.tris[i];
     for (int i = tid; i < 4 * P.n_lt; i += kBlock) slv[i] = P.light_v[i];
     for (int i = tid; i <= P.n_light; i += kBlock) slo[i] = P.light_off[i];
     for (int i = tid; i < 2 * P.n_mat; i += kBlock) smt[i] = reinterpret_cast<const float4*>(P.mats)[i];
-    if (tid < 4 * ctl_f4) ctl[tid] = 0u;
+    if (tid < 4 * kCtlF4) ctl[tid] = 0u;
     __syncthreads();
     const float4* g_nodes = sn;
     const float4* g_tris = st4;
@@ -108,11 +104,11 @@ void trace_kernel_pool(TraceParams P) {
     V3 beta = v3(1, 1, 1), L = v3(0, 0, 0), pend = v3(0, 0, 0);
     Counters cn = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t n_e = 0, n_s = 0, lanes_s = 0, pre_hits = 0;
-    uint64_t n_susp = 0, n_res = 0;   // STATS (diag words 176, 177): queries suspended, queries resumed
-    // STATS lane table (diag words 160..175, tools/lane_table.py): (wave trips, lane trips) of E inner
+    uint64_t n_susp = 0, n_res = 0;   // STATS (PRT_DIAG_SUSPENDED, PRT_DIAG_RESUMED): queries suspended, resumed
+    // STATS lane table (PRT_DIAG_LANE_TABLE, tools/lane_table.py): (wave trips, lane trips) of E inner
     // visits, E triangle tests, S inner visits, S triangle tests, the shading block, the Lambert
     // block, the loop iteration (lanes busy after the refill) and the resolve of shadow answers
-    uint64_t lt[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t lt[PRT_DIAG_LANE_TABLE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     // books a traversal's trip counters into lane-table entries k, k + 1 (inner) and k + 2, k + 3 (leaf)
     auto book_trav = [&](int k) {
         lt[k] += cn.wi; lt[k + 1] += cn.li; lt[k + 2] += cn.wl; lt[k + 3] += cn.ll;
@@ -133,31 +129,21 @@ void trace_kernel_pool(TraceParams P) {
     uint32_t qpar = 0;
 #ifdef PRT_POOL_CLOCKS
     // diagnostic build (tools/pool_clocks.py): wave-level cycles in E, at barrier 1, in S, at barrier 2
-    uint64_t ck[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t ck[PRT_DIAG_POOL_CLOCKS_WORDS] = {0, 0, 0, 0, 0, 0};
     uint64_t t_c = __builtin_amdgcn_s_memtime();
 #define PRT_CLOCK(k) do { const uint64_t t_n = __builtin_amdgcn_s_memtime(); ck[k] += t_n - t_c; t_c = t_n; } while (0)
 #else
 #define PRT_CLOCK(k) do {} while (0)
 #endif
-    // work-queue refill of the wave's idle lanes (path regeneration, trace_kernel's refill)
+    // work-queue refill of the wave's idle lanes (path regeneration; the chunk claim is prt_shade.h
+    // claim_chunk; the start of an item is written out as in trace_kernel, see there)
     auto refill = [&](KParams& Q) {
             bool me_idle = item < 0;
             uint64_t idle = __ballot(me_idle);
             for (int round = 0; round < 2 && idle; ++round) {
                 uint32_t avail = q_end - q_next;
                 if (avail == 0 && !exhausted) {
-                    uint32_t base = 0;
-                    if (lane == 0) base = atomicAdd(Q.work, (uint32_t)kChunk);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    if ((uint64_t)base >= Q.n_items) {
-                        exhausted = true;
-                    } else {
-                        q_next = base;
-                        q_end = (uint32_t)min((uint64_t)base + kChunk, Q.n_items);
-                        chunk_s = __builtin_amdgcn_readfirstlane(base / (uint32_t)Q.n_slots);
-                        uint32_t tk = (base - chunk_s * (uint32_t)Q.n_slots) >> Q.log_tpx;
-                        chunk_xy0 = ((const __attribute__((address_space(4))) uint32_t*)(uintptr_t)Q.tile_xy)[tk];
-                    }
+                    exhausted = !claim_chunk<false, false>(Q, lane, q_next, q_end, chunk_s, chunk_xy0);
                     avail = q_end - q_next;
                 }
                 if (avail == 0) break;
@@ -473,33 +459,34 @@ void trace_kernel_pool(TraceParams P) {
     }
 #ifdef PRT_POOL_CLOCKS
     if (lane == 0)
-        for (int k = 0; k < 6; ++k) atomicAdd(P.stats + 24 + k, (unsigned long long)ck[k]);
+        for (int k = 0; k < PRT_DIAG_POOL_CLOCKS_WORDS; ++k)
+            atomicAdd(P.stats + PRT_DIAG_POOL_CLOCKS + k, (unsigned long long)ck[k]);
 #endif
 #undef PRT_CLOCK
     if (STATS) {
-        // diag 0..3: node visits, triangle tests, extension and shadow queries; 17..20 (pool kernel): wave
-        // E iterations, wave S iterations, lanes of the S iterations, shadow rays answered by the
-        // light-triangle test
-        const uint64_t sums[8] = {cn.nodes, cn.tris, cn.ext, cn.shadow, n_e, n_s, lanes_s, pre_hits};
-        for (int k = 0; k < 8; ++k) {
+        // the four counters (PRT_DIAG_NODES ..), then the pooled kernel's PRT_DIAG_POOL words
+        const uint64_t sums[4 + PRT_DIAG_POOL_WORDS] = {cn.nodes, cn.tris, cn.ext,  cn.shadow,
+                                                        n_e,      n_s,     lanes_s, pre_hits};
+        for (int k = 0; k < 4 + PRT_DIAG_POOL_WORDS; ++k) {
             const uint64_t v = wave_sum(sums[k]);
-            if (lane == 0) atomicAdd(P.stats + (k < 4 ? k : k + 13), (unsigned long long)v);
+            const int word = k < 4 ? PRT_DIAG_NODES + k : PRT_DIAG_POOL + k - 4;
+            if (lane == 0) atomicAdd(P.stats + word, (unsigned long long)v);
         }
-        for (int k = 0; k < 16; ++k) {
+        for (int k = 0; k < PRT_DIAG_LANE_TABLE_WORDS; ++k) {
             const uint64_t v = wave_sum(lt[k]);
-            if (lane == 0 && v) atomicAdd(P.stats + 160 + k, (unsigned long long)v);
+            if (lane == 0 && v) atomicAdd(P.stats + PRT_DIAG_LANE_TABLE + k, (unsigned long long)v);
         }
         n_susp = wave_sum(n_susp);
         n_res = wave_sum(n_res);
         if (lane == 0 && n_susp) {
-            atomicAdd(P.stats + 176, (unsigned long long)n_susp);
-            atomicAdd(P.stats + 177, (unsigned long long)n_res);
+            atomicAdd(P.stats + PRT_DIAG_SUSPENDED, (unsigned long long)n_susp);
+            atomicAdd(P.stats + PRT_DIAG_RESUMED, (unsigned long long)n_res);
         }
         const uint32_t msp = wave_max(cn.max_sp), nf = wave_sum(cn.nonfinite), mq = wave_max(cn.max_q);
         if (lane == 0) {
-            atomicMax(P.stats + 13, (unsigned long long)msp);
-            if (nf) atomicAdd(P.stats + 14, (unsigned long long)nf);
-            atomicMax(P.stats + 16, (unsigned long long)mq);
+            atomicMax(P.stats + PRT_DIAG_MAX_STACK, (unsigned long long)msp);
+            if (nf) atomicAdd(P.stats + PRT_DIAG_NONFINITE, (unsigned long long)nf);
+            atomicMax(P.stats + PRT_DIAG_MAX_QUERY, (unsigned long long)mq);
         }
     }
 }

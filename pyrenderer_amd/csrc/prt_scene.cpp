@@ -1,6 +1,6 @@
 // prt_scene.cpp — the library's identity calls, host BVH handles, and a scene's life: validate, build
-// the BVH, pack, upload, query the device, read the environment knobs; plus the choice of trace-kernel
-// variant that follows from the scene's sizes (prt_host.h).
+// the BVH, pack, upload, query the device, read the environment knobs; plus the calls of the size-only
+// launch decisions (prt_plan.h: LDS footprints, the trace-kernel variant) for a scene (prt_host.h).
 #include <cstdlib>
 #include <new>
 
@@ -31,44 +31,15 @@ void destroy_scene(Scene* s) {
     delete s;
 }
 
-// LDS-resident scene: BVH + triangles small enough to sit beside the stack
-constexpr int64_t kLdsSceneBytes = 24 * 1024;
-// the scene's sizes alone (all that the LDS footprints depend on), with the pooled kernel's stack
-TraceParams size_params(const Scene* s) {
-    TraceParams P;
-    std::memset(&P, 0, sizeof(P));
-    P.n_node_f4 = (int)s->n_node4_f4; P.n_tri_f4 = (int)s->n_tri_f4; P.n_tri = (int)s->n_tri;
-    P.n_mat = s->n_mat; P.n_lt = s->n_lt; P.n_light = s->n_light;
-    P.lds_stack = s->need4;
-    return P;
-}
-
-// LDS-resident scene when it fits; the >= 7 (>= 6) waves/SIMD build when seven (six) blocks'
-// LDS still fit one CU (160 KiB), so the occupancy target is not defeated by LDS.
-// Everything else (and BVH4s deeper than the 64-entry LDS stack) takes the global-scene
-// kernel: 64-B quantised nodes, 16-entry LDS stack + spill, suspended traversal tails,
-// >= 6 waves/SIMD (C4: 28.6 ms at 5 waves, 27.2 at 6, 28.6 at 7 with spills).
-// An LDS-resident scene whose pooled-shadow kernel still fits seven blocks per CU takes that kernel
-// (C2 4.06 vs 4.28 ms, C3 73.6 vs 77.5 ms, profiles/r03/pool/) at every launch size: since round 6
-// it also wins the small launches that round 3 left to the phase-aligned kernel (config 1 0.080 vs
-// 0.094 ms per launch; DESIGN.md §2, profiles/r06/kernarg/variants/).
-int default_variant(const Scene* s) {
-    if (!lds_fits4(s) || !s->stack4) return kVarGlobal;
-    const TraceParams P = size_params(s);
-    if (s->need4 <= 32 && trace_smem_bytes(16, kVarLdsPool, P) * 7 <= 160 * 1024) return kVarLdsPool;
-    size_t smem = trace_smem_bytes(s->stack4, kVarLds, P);
-    return smem * 7 <= 160 * 1024 ? kVarLds : smem * 6 <= 160 * 1024 ? kVarLds6 : kVarLdsAnyOcc;
+// the scene's sizes alone (all that the LDS footprints and the variant choice depend on, prt_plan.h), with
+// the pooled kernel's stack
+LdsSizes scene_sizes(const Scene* s) {
+    return LdsSizes{(int)s->n_node4_f4, (int)s->n_tri_f4, (int)s->n_tri, s->n_mat, s->n_lt, s->n_light, s->need4};
 }
 
 }  // namespace
 
-// ... and whose node indices and leaf references fit the LDS kernels' 16-bit stack entries
-// (inner nodes < 0x7FFF, the sentinel; leaf refs >= -32768)
-bool lds_fits4(const Scene* s) {
-    const int64_t n_refs = s->n_tri_f4 / 3;
-    return (int64_t)lds_scene_bytes(size_params(s)) <= kLdsSceneBytes && s->n_node4_f4 / 8 < 0x7FFF &&
-           n_refs * 8 <= 32768;
-}
+bool lds_fits4(const Scene* s) { return lds_fits(scene_sizes(s)); }
 
 // the traversal stack entries of variant `var` (LDS part for the spill variants; the pool kernel's
 // instantiation set, its LDS stack being the launch parameter P.lds_stack)
@@ -78,24 +49,23 @@ int variant_stack(const Scene* s, int var) {
 
 // the variant a launch takes: the one the flags name, else the scene's default
 int launch_variant(const Scene* s, uint32_t flags) {
-    int var = (int)((flags >> PRT_FLAG_VARIANT_SHIFT) & 0xFFu);
-    const bool mis = (flags & PRT_FLAG_MIS_NEE) != 0;
-    if (var == 0) var = !mis ? default_variant(s) : (lds_fits4(s) && s->stack4) ? kVarLdsMis : kVarGlobalMis;
-    return var;
+    const int var = (int)((flags >> PRT_FLAG_VARIANT_SHIFT) & 0xFFu);
+    return var ? var : choose_variant(scene_sizes(s), s->need4, s->stack4, (flags & PRT_FLAG_MIS_NEE) != 0);
 }
 
 // blocks per CU of variant `var`'s persistent grid (>= 1), queried once per (variant, stats)
 int variant_occ(Scene* s, int var, bool stats) {
     int& occ = s->occ[2 * var + (stats ? 1 : 0)];
     const int stack = variant_stack(s, var);
-    if (occ == 0) occ = std::max(1, trace_blocks_per_cu(stack, var, stats, trace_smem_bytes(stack, var, size_params(s))));
+    if (occ == 0) occ = std::max(1, trace_blocks_per_cu(stack, var, stats, trace_smem_bytes(stack, var, scene_sizes(s))));
     return occ;
 }
 
 // Scene part of a trace launch's parameters (everything but the work description).
 void scene_params(Scene* s, TraceParams& P) {
-    P = size_params(s);
-    P.lds_stack = 0;   // set per launch (trace_setup)
+    std::memset(&P, 0, sizeof(P));   // lds_stack is set per launch (trace_setup)
+    P.n_node_f4 = (int)s->n_node4_f4; P.n_tri_f4 = (int)s->n_tri_f4; P.n_tri = (int)s->n_tri;
+    P.n_mat = s->n_mat; P.n_lt = s->n_lt; P.n_light = s->n_light;
     P.nodes = (const float4*)s->nodes4.p; P.tris = (const float4*)s->tris.p;
     P.tri_nm = (const float4*)s->tri_nm.p; P.tri_frame = (const float4*)s->tri_frame.p;
     P.mats = (const float*)s->mats.p;
@@ -155,7 +125,7 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
     s->resume_min = (int)env_int("PRT_RESUME_MIN", 1, 64, s->resume_min);
     s->pool_resume_min = (int)env_int("PRT_POOL_RESUME_MIN", 0, 64, s->pool_resume_min);
     s->spill_lds = spill_lds_entries(env_int("PRT_SPILL_LDS", INT32_MIN, INT32_MAX, s->spill_lds));
-    s->blocks_per_cu = variant_occ(s, default_variant(s), false);
+    s->blocks_per_cu = variant_occ(s, launch_variant(s, 0), false);
     if (const long long cb = env_int("PRT_CHUNK_BYTES", 1LL << 20, INT64_MAX, 0)) {
         s->chunk_bytes = (size_t)cb;
     } else {

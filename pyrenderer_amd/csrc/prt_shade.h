@@ -99,6 +99,55 @@ __device__ __forceinline__ void camera_ray(const TraceParams& P, int x, int y, u
 }
 
 // ------------------------------------------------------------------------------------------------
+// The work-queue refill of a wave's idle lanes (path regeneration): the chunk claim trace_kernel and
+// trace_kernel_pool share.  Each kernel keeps the ballot / rank hand-out around it and the start of an
+// item written out (pixel decode, out-of-frame zero write, ray and origin fetch): through a shared
+// function the pooled kernel's non-STATS builds spilled 6 to 14 VGPRs where they spill 0 to 2, and the
+// global-scene kernel's scratch grew from 28 to 40 bytes (profiles/r12/trace_plumbing/README.md).
+// PT: TraceParams or KParams.
+
+// Claims the wave's next chunk [q_next, q_end) of kChunk items from the launch's work counter and
+// decodes its sample index and tile origin (both wave-uniform); false: the queue is exhausted.
+// PIXEL_MAJOR: the global scenes' chunk order; WAVE_CLOCK: books the items into P.wave_clock
+// (trace_kernel's diagnostic).
+template <bool PIXEL_MAJOR, bool WAVE_CLOCK, class PT>
+__device__ __forceinline__ bool claim_chunk(const PT& Q, int lane, uint32_t& q_next, uint32_t& q_end,
+                                            uint32_t& chunk_s, uint32_t& chunk_xy0) {
+    uint32_t base = 0;
+    if (lane == 0) base = atomicAdd(Q.work, (uint32_t)kChunk);
+    base = __builtin_amdgcn_readfirstlane(base);
+    if ((uint64_t)base >= Q.n_items) return false;
+    if constexpr (PIXEL_MAJOR) {
+        // global scenes: queue chunk c -> (sample c % n, 64-pixel group c / n), so
+        // the chunks in flight hold every sample of a few pixel groups instead of
+        // one sample of the whole frame: their paths start (and first bounce) in a
+        // small part of the scene, and its nodes and triangles stay in L2 (C4
+        // 18.12 -> 17.51 ms).  LDS scenes keep sample-major chunks, whose staged
+        // rays and radiance are read and written in address order (pixel-major
+        // there strides 4 MB per chunk: C2 4.23 -> 4.32 ms; profiles/r02/s5/ab_pm/)
+        const uint32_t n_samp = (uint32_t)(Q.n_items / (uint64_t)Q.n_slots);
+        const uint32_t c = base >> 6;
+        const uint32_t g = c / n_samp;
+        base = (c - g * n_samp) * (uint32_t)Q.n_slots + (g << 6);
+        base = __builtin_amdgcn_readfirstlane(base);
+    }
+    q_next = base;
+    q_end = (uint32_t)min((uint64_t)base + kChunk, Q.n_items);
+    if constexpr (WAVE_CLOCK) {
+        if (Q.wave_clock && lane == 0)
+            Q.wave_clock[3 * ((size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) + 2] += q_end - q_next;
+    }
+    // n_slots is a multiple of 64 (tile sizes are powers of two >= 64 px),
+    // so a chunk never straddles two samples: one scalar division per chunk
+    chunk_s = __builtin_amdgcn_readfirstlane(base / (uint32_t)Q.n_slots);
+    // tiles hold >= 64 pixels (powers of two), so the chunk lies in one tile
+    uint32_t tk = (base - chunk_s * (uint32_t)Q.n_slots) >> Q.log_tpx;
+    // uniform index: a scalar load through the constant address space
+    chunk_xy0 = ((const __attribute__((address_space(4))) uint32_t*)(uintptr_t)Q.tile_xy)[tk];
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Shading and staging pieces shared by trace_kernel, trace_kernel_pool and the hit-query kernels: one
 // copy of each, in the reference's expression order (the arithmetic contract).  PT is the launch
 // parameters as the caller holds them (TraceParams by value, or KParams through the kernarg pointer);

@@ -53,7 +53,6 @@ void trace_kernel(TraceParams P) {
     extern __shared__ float4 smem[];
     // LDS: the traversal stacks (16-bit entries for LDS-resident scenes), then the scene copy
     using StackT = typename std::conditional<SCENE_LDS, LdsStack16A, SpillStack<STACK>>::type;
-    constexpr int kStackF4 = STACK * kBlock * (SCENE_LDS ? 2 : 4) / 16;
     StackT stk;
     if constexpr (SCENE_LDS) {
         stk = LdsStack16A::at(smem, threadIdx.x);
@@ -71,16 +70,16 @@ void trace_kernel(TraceParams P) {
     const int* s_loff = P.light_off;
     if (SCENE_LDS) {
         // small scene: copy BVH + triangles, and the shading data (normals, frames,
-        // materials, emitters), into LDS once per persistent block
-        float4* sn = smem + kStackF4;
-        const int n_node4 = P.n_node_f4 / 8;
-        float4* st4 = sn + 56 * n_node4;
-        float4* snm = st4 + P.n_tri_f4;
-        float4* sfr = snm + P.n_tri;
-        float4* smt = sfr + 6 * P.n_tri;
-        float4* slv = smt + 2 * P.n_mat;
-        int* slo = reinterpret_cast<int*>(slv + 4 * P.n_lt);
-        copy_octant_nodes(sn, P.nodes, n_node4);
+        // materials, emitters), into LDS once per persistent block (layout: prt_lds_layout.h)
+        const TraceLds lay = trace_lds(lds_sizes(P, STACK));
+        float4* sn = smem + lay.nodes;
+        float4* st4 = smem + lay.tris;
+        float4* snm = smem + lay.normals;
+        float4* sfr = smem + lay.frames;
+        float4* smt = smem + lay.mats;
+        float4* slv = smem + lay.light_v;
+        int* slo = reinterpret_cast<int*>(smem + lay.light_off);
+        copy_octant_nodes(sn, P.nodes, P.n_node_f4 / 8);
         for (int i = threadIdx.x; i < P.n_tri_f4; i += kBlock) st4[i] = P.tris[i];
         for (int i = threadIdx.x; i < P.n_tri; i += kBlock) snm[i] = P.tri_nm[i];
         for (int i = threadIdx.x; i < 6 * P.n_tri; i += kBlock) sfr[i] = P.tri_frame[i];
@@ -127,7 +126,7 @@ void trace_kernel(TraceParams P) {
     // diagnostic (STATS) wave-level clocks: refill / traversal / shading, iterations, active lanes
     uint64_t c_refill = 0, c_trav = 0, c_shade = 0, n_iter = 0, n_active = 0;
     // STATS, phase-aligned schedule: wave clocks and counts of extension / shadow iterations and the
-    // lanes that queried in the shadow ones (diag words 17..21)
+    // lanes that queried in the shadow ones (PRT_DIAG_PHASE)
     uint64_t c_it_ext = 0, c_it_sh = 0, n_it_ext = 0, n_it_sh = 0, lanes_sh = 0, t_it = 0;
     uint64_t t_a = 0, t_b = 0;
     // PHASE: the wave alternates extension and shadow iterations, so the costly
@@ -152,38 +151,8 @@ void trace_kernel(TraceParams P) {
         for (int round = 0; round < 2 && idle; ++round) {
             uint32_t avail = q_end - q_next;
             if (avail == 0 && !exhausted) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(Q.work, (uint32_t)kChunk);
-                base = __builtin_amdgcn_readfirstlane(base);
-                if ((uint64_t)base >= Q.n_items) {
-                    exhausted = true;
-                } else {
-                    if constexpr (!SCENE_LDS) {
-                        // global scenes: queue chunk c -> (sample c % n, 64-pixel group c / n), so
-                        // the chunks in flight hold every sample of a few pixel groups instead of
-                        // one sample of the whole frame: their paths start (and first bounce) in a
-                        // small part of the scene, and its nodes and triangles stay in L2 (C4
-                        // 18.12 -> 17.51 ms).  LDS scenes keep sample-major chunks, whose staged
-                        // rays and radiance are read and written in address order (pixel-major
-                        // there strides 4 MB per chunk: C2 4.23 -> 4.32 ms; profiles/r02/s5/ab_pm/)
-                        const uint32_t n_samp = (uint32_t)(Q.n_items / (uint64_t)Q.n_slots);
-                        const uint32_t c = base >> 6;
-                        const uint32_t g = c / n_samp;
-                        base = (c - g * n_samp) * (uint32_t)Q.n_slots + (g << 6);
-                        base = __builtin_amdgcn_readfirstlane(base);
-                    }
-                    q_next = base;
-                    q_end = (uint32_t)min((uint64_t)base + kChunk, Q.n_items);
-                    if (Q.wave_clock && lane == 0)
-                        Q.wave_clock[3 * ((size_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) + 2] += q_end - q_next;
-                    // n_slots is a multiple of 64 (tile sizes are powers of two >= 64 px),
-                    // so a chunk never straddles two samples: one scalar division per chunk
-                    chunk_s = __builtin_amdgcn_readfirstlane(base / (uint32_t)Q.n_slots);
-                    // tiles hold >= 64 pixels (powers of two), so the chunk lies in one tile
-                    uint32_t tk = (base - chunk_s * (uint32_t)Q.n_slots) >> Q.log_tpx;
-                    // uniform index: a scalar load through the constant address space
-                    chunk_xy0 = ((const __attribute__((address_space(4))) uint32_t*)(uintptr_t)Q.tile_xy)[tk];
-                }
+                // global scenes take pixel-major chunks (claim_chunk)
+                exhausted = !claim_chunk<!SCENE_LDS, true>(Q, lane, q_next, q_end, chunk_s, chunk_xy0);
                 avail = q_end - q_next;
             }
             if (avail == 0) break;
@@ -192,7 +161,9 @@ void trace_kernel(TraceParams P) {
             uint32_t take = need < avail ? need : avail;
             if (me_idle && rank < take) {
                 item = (int)(q_next + rank);
-                // start a new sample: main_taichi.py:89-95
+                // start a new sample (main_taichi.py:89-95).  Written out here and in trace_kernel_pool:
+                // as a function shared by both, the pooled, global-scene and MIS kernels spilled more
+                // (prt_shade.h at claim_chunk; profiles/r12/trace_plumbing/README.md)
                 L = v3(0, 0, 0);
                 int x, y;
                 pixel_of(Q, (uint32_t)item, chunk_s, chunk_xy0, x, y);
@@ -293,11 +264,11 @@ void trace_kernel(TraceParams P) {
         if (STATS) {
             const uint32_t qn = cn.nodes - cn.q0;
             cn.max_q = max(cn.max_q, qn);   // most node visits of one query
-            // outlier log (diag words 24..151): the first 16 queries with > 1000 node visits
+            // outlier log (PRT_DIAG_OUTLIER_LOG): the first 16 queries with > 1000 node visits
             if (qn > 1000) {
-                const unsigned long long k = atomicAdd(Q.stats + 23, 1ull);
-                if (k < 16) {
-                    unsigned long long* r = Q.stats + 24 + 8 * k;
+                const unsigned long long k = atomicAdd(Q.stats + PRT_DIAG_OUTLIERS, 1ull);
+                if (k < PRT_DIAG_OUTLIER_RECORDS) {
+                    unsigned long long* r = Q.stats + PRT_DIAG_OUTLIER_LOG + PRT_DIAG_OUTLIER_WORDS * k;
                     r[0] = __float_as_uint(o.x); r[1] = __float_as_uint(o.y); r[2] = __float_as_uint(o.z);
                     r[3] = __float_as_uint(d.x); r[4] = __float_as_uint(d.y); r[5] = __float_as_uint(d.z);
                     r[6] = __float_as_uint(tmax); r[7] = ((unsigned long long)qtype << 32) | qn;
@@ -491,28 +462,30 @@ void trace_kernel(TraceParams P) {
         uint64_t wv[7] = {c_refill, c_trav, c_shade, n_iter, n_active, w_inner, w_leaf};
         for (int k = 0; k < 7; ++k) wv[k] = wave_sum(wv[k]);
         if (lane == 0) {
-            atomicAdd(P.stats + 0, (unsigned long long)a);
-            atomicAdd(P.stats + 1, (unsigned long long)b);
-            atomicAdd(P.stats + 2, (unsigned long long)c);
-            atomicAdd(P.stats + 3, (unsigned long long)e);
-            for (int k = 0; k < 7; ++k) atomicAdd(P.stats + 4 + k, (unsigned long long)wv[k]);
+            atomicAdd(P.stats + PRT_DIAG_NODES, (unsigned long long)a);
+            atomicAdd(P.stats + PRT_DIAG_TRIS, (unsigned long long)b);
+            atomicAdd(P.stats + PRT_DIAG_EXT, (unsigned long long)c);
+            atomicAdd(P.stats + PRT_DIAG_SHADOW, (unsigned long long)e);
+            // PRT_DIAG_CLK_REFILL .. PRT_DIAG_WAVE_LEAF, in wv's order
+            for (int k = 0; k < 7; ++k) atomicAdd(P.stats + PRT_DIAG_CLK_REFILL + k, (unsigned long long)wv[k]);
         }
-        uint64_t ph[5] = {c_it_ext, c_it_sh, n_it_ext, n_it_sh, lanes_sh};
-        for (int k = 0; k < 5; ++k) ph[k] = wave_sum(ph[k]);
+        uint64_t ph[PRT_DIAG_PHASE_WORDS] = {c_it_ext, c_it_sh, n_it_ext, n_it_sh, lanes_sh};
+        for (int k = 0; k < PRT_DIAG_PHASE_WORDS; ++k) ph[k] = wave_sum(ph[k]);
         if (lane == 0)
-            for (int k = 0; k < 5; ++k) atomicAdd(P.stats + 17 + k, (unsigned long long)ph[k]);
+            for (int k = 0; k < PRT_DIAG_PHASE_WORDS; ++k)
+                atomicAdd(P.stats + PRT_DIAG_PHASE + k, (unsigned long long)ph[k]);
         const uint32_t m = wave_max(cn.max_sp);
-        if (lane == 0) atomicMax(P.stats + 13, (unsigned long long)m);
+        if (lane == 0) atomicMax(P.stats + PRT_DIAG_MAX_STACK, (unsigned long long)m);
         const uint32_t nf = wave_sum(cn.nonfinite);
-        if (lane == 0 && nf) atomicAdd(P.stats + 14, (unsigned long long)nf);
+        if (lane == 0 && nf) atomicAdd(P.stats + PRT_DIAG_NONFINITE, (unsigned long long)nf);
         const uint32_t mq = wave_max(cn.max_q);
-        if (lane == 0) atomicMax(P.stats + 16, (unsigned long long)mq);
+        if (lane == 0) atomicMax(P.stats + PRT_DIAG_MAX_QUERY, (unsigned long long)mq);
         const uint32_t wt = wave_sum(cn.w_tri);
-        if (lane == 0 && wt) atomicAdd(P.stats + 15, (unsigned long long)wt);
+        if (lane == 0 && wt) atomicAdd(P.stats + PRT_DIAG_WAVE_TRI, (unsigned long long)wt);
         const uint64_t a2 = wave_sum(l_inner), b2 = wave_sum(l_leaf);
         if (lane == 0) {
-            atomicAdd(P.stats + 11, (unsigned long long)a2);
-            atomicAdd(P.stats + 12, (unsigned long long)b2);
+            atomicAdd(P.stats + PRT_DIAG_LANE_INNER, (unsigned long long)a2);
+            atomicAdd(P.stats + PRT_DIAG_LANE_LEAF, (unsigned long long)b2);
         }
     }
 }

@@ -1,5 +1,5 @@
 // prt_trace_inst.hip — one instantiation set of the persistent trace kernel
-// (prt_trace.h): every variant of the table in prt_variants.h for traversal stack PRT_STACK and
+// (prt_trace.h): every variant of the table in prt_variant_table.h for traversal stack PRT_STACK and
 // stats flag PRT_STATS.  pyrenderer_amd/build.py compiles this file once per
 // (stack, stats) pair, in parallel, and links the objects into libprt.so.
 #pragma clang fp contract(off)

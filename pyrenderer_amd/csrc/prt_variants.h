@@ -1,5 +1,6 @@
 #pragma once
-// prt_variants.h — the table of trace-kernel variants and the launch / occupancy dispatch derived from it.
+// prt_variants.h — the launch / occupancy dispatch derived from the table of trace-kernel variants
+// (prt_variant_table.h kVariants).
 #pragma clang fp contract(off)
 
 #include <type_traits>
@@ -9,22 +10,6 @@
 
 namespace prt {
 
-// The trace-kernel variants that exist (ids in prt_kernels.h): scene placement, estimator, kernel and
-// the occupancy target (min waves per SIMD) each is built for.
-struct Variant { int id; bool lds, mis, pool; int wpe; };
-constexpr Variant kVariants[] = {
-    {kVarLds, true, false, false, 7},      {kVarLdsAnyOcc, true, false, false, 1},
-    {kVarGlobal, false, false, false, 6},  {kVarLdsMis, true, true, false, 6},
-    {kVarGlobalMis, false, true, false, 6}, {kVarLds6, true, false, false, 6},
-    {kVarLdsPool, true, false, true, 7},   {kVarLdsPool6, true, false, true, 6},
-};
-constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
-// the row of variant `var`, or null
-constexpr const Variant* find_variant(int var) {
-    for (int i = 0; i < kNumVariants; ++i)
-        if (kVariants[i].id == var) return &kVariants[i];
-    return nullptr;
-}
 // Which STACK instantiations a variant has.  The pool kernel's LDS stack size is a launch parameter
 // (P.lds_stack): one instantiation, compiled in its own unit (prt_trace_pool.hip, other
 // register-allocation flags) and reached through the 16-entry set.  Global scenes (LDS part of the spill

@@ -25,6 +25,16 @@ def test_library_exports_header_symbols():
     assert L.prt_abi_version() == N.ABI_VERSION == 4
 
 
+def test_diag_word_names_match_the_header():
+    """Every PRT_DIAG_* of include/prt.h has the same value in _native.py, and the reverse."""
+    from pyrenderer_amd import _native as N
+    src = open(os.path.join(ROOT, "include", "prt.h")).read()
+    header = {k: int(v, 0) for k, v in re.findall(r"^#define\s+(PRT_DIAG_[A-Z0-9_]+)\s+(\w+)", src, re.M)}
+    mirror = {k: v for k, v in vars(N).items() if k.startswith("PRT_DIAG_")}
+    assert len(header) >= 30 and header == mirror, set(header.items()) ^ set(mirror.items())
+    assert header["PRT_DIAG_NONFINITE"] == 14 and header["PRT_DIAG_MAX_STACK"] == 13   # bench.py's literal [14]
+
+
 def test_device_count_without_gpu_is_ok():
     from pyrenderer_amd import _native as N
     assert N.device_count() >= 0

@@ -95,8 +95,8 @@ def test_config4_full_frame_matches_oracle(cubes):
     ids = np.arange(16, dtype=np.int32)
     ds.render_tiles(cam, W, H, 32, 32, ids, 4, 8, 0, N.PRT_FLAG_STATS)
     diag = ds.diag_stats()
-    assert diag[14] == 0                       # no NaN / inf sample radiance
-    assert diag[0] > 0 and diag[1] > 0
+    assert diag[N.PRT_DIAG_NONFINITE] == 0                     # no NaN / inf sample radiance
+    assert diag[N.PRT_DIAG_NODES] > 0 and diag[N.PRT_DIAG_TRIS] > 0
 
 
 def test_config4_sharded_frame_is_identical(cubes):

@@ -197,5 +197,5 @@ def test_stack_depth_within_the_collapse_bound(world, cornell, name):
         info = ds.kernel_info(n_items=W * H * 4, flags=flags)
         assert info["variant"] == var
         ds.render_tiles(packed, W, H, 64, 64, tiles, 4, 8, seed=1, flags=flags)
-        deepest = int(ds.diag_stats()[13])
+        deepest = int(ds.diag_stats()[N.PRT_DIAG_MAX_STACK])
         assert 1 <= deepest <= info["stack"], (name, var, deepest, info)

@@ -250,7 +250,7 @@ def test_zoo_render_and_counters_match_the_oracle(world, cornell, kernel):
         np.testing.assert_array_equal(got, ref)
         if fl & N.PRT_FLAG_STATS:
             assert st[2] == oc[2] and st[3] == oc[3] and st[0] > 0 and st[1] > 0, (st, oc)
-            assert ds.diag_stats()[14] == 0
+            assert ds.diag_stats()[N.PRT_DIAG_NONFINITE] == 0
 
 
 # ------------------------------------------------------------------ features

@@ -195,6 +195,52 @@ def test_lds_soup_deep_stack_matches_oracle(cornell):
     ds.close()
 
 
+def test_largest_lds_scene_matches_oracle_in_every_lds_variant(cornell):
+    """The far end of the LDS layouts (prt_lds_layout.h), where a wrong region offset would show: the
+    soup with the most extra triangles that is still LDS-resident (one more is not), through every
+    LDS variant — phase-aligned (1, 2, 6), pooled (7, 8) and MIS (4) — bit for bit against the oracle,
+    with no non-finite sample and no watchdog trip."""
+    from pyrenderer_amd import _native as N
+    from pyrenderer_amd.device_scene import DeviceScene
+
+    def resident(n):
+        ds = DeviceScene(_soup_scene(cornell, n, 11), 0)
+        try:
+            return ds.kernel_info()["lds_scene"]
+        finally:
+            ds.close()
+
+    lo, hi = 0, 256   # the Cornell box alone is resident (test_default_variant_reaches_its_occupancy)
+    assert not resident(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if resident(mid) else (lo, mid)
+    assert lo >= 1 and resident(lo) and not resident(lo + 1), lo
+    flat = _soup_scene(cornell, lo, 11)
+    ds = DeviceScene(flat, 0)
+    osc = O.OracleScene.from_flat(flat)
+    cam = cornell[1].convert_to_taichi_camera().packed()
+    ids = np.arange(1, dtype=np.int32)
+    want = {}
+    for mis in (False, True):
+        O.set_nee_mode(mis)
+        try:
+            want[mis] = osc.render_tiles(cam, 64, 64, 64, 64, ids, 4, 4, seed=3)
+        finally:
+            O.set_nee_mode(False)
+    for var in (N.VAR_LDS, N.VAR_LDS_ANY_OCC, N.VAR_LDS6, N.VAR_LDS_POOL, N.VAR_LDS_POOL6, N.VAR_MIS[0]):
+        mis = var == N.VAR_MIS[0]
+        flags = (var << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
+        assert ds.kernel_info(n_items=64 * 64 * 4, flags=flags)["variant"] == var
+        g, _ = ds.render_tiles(cam, 64, 64, 64, 64, ids, 4, 4, 3, flags)
+        np.testing.assert_array_equal(g, want[mis], err_msg="variant %d" % var)
+        gs, _ = ds.render_tiles(cam, 64, 64, 64, 64, ids, 4, 4, 3, flags | N.PRT_FLAG_STATS)
+        np.testing.assert_array_equal(gs, want[mis], err_msg="variant %d, STATS build" % var)
+        assert ds.diag_stats()[N.PRT_DIAG_NONFINITE] == 0, var
+        ds.check_faults()
+    ds.close()
+
+
 def test_full_size_config2_matches_oracle(gpu_scene, oracle_scene, cornell):
     """BASELINE config 2 at full size (512^2 x 64 spp, depth 8), the WHOLE frame
     against the oracle (brute-force closest hits, all host threads).  At this size
@@ -487,7 +533,7 @@ def test_nonfinite_sample_counter(gpu_scene, cornell):
     cam = cornell[1].convert_to_taichi_camera().packed()
     ids = np.arange(4, dtype=np.int32)
     gpu_scene.render_tiles(cam, 64, 64, 32, 32, ids, 2, 8, 1, N.PRT_FLAG_STATS)
-    assert gpu_scene.diag_stats()[14] == 0
+    assert gpu_scene.diag_stats()[N.PRT_DIAG_NONFINITE] == 0
     f = cornell[2]
     mat = f.mat.copy()
     mat[f.tri_mat[0], 0] = np.nan                  # the floor's red albedo
@@ -495,7 +541,7 @@ def test_nonfinite_sample_counter(gpu_scene, cornell):
                     f.direct_rgb)
     ds = DeviceScene(bad, 0)
     s, _ = ds.render_tiles(cam, 64, 64, 32, 32, ids, 2, 8, 1, N.PRT_FLAG_STATS)
-    n_bad = int(ds.diag_stats()[14])
+    n_bad = int(ds.diag_stats()[N.PRT_DIAG_NONFINITE])
     px_bad = int((~np.isfinite(s)).any(axis=1).sum())
     assert n_bad > 0 and n_bad >= px_bad > 0, (n_bad, px_bad)
     ds.close()

@@ -11,7 +11,6 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-SUSPENDED, RESUMED, NONFINITE = 176, 177, 14
 
 
 @pytest.fixture(scope="module")
@@ -45,9 +44,9 @@ def _render(ds, cam, W, H, tile, ids, spp, depth, seed, variant=0):
     ds.check_faults()
     simg, st = ds.render_tiles(cam, W, H, tile, tile, ids, spp, depth, seed, N.PRT_FLAG_STATS | (variant << 8))
     ds.check_faults()
-    w = ds.diag_words(192)
-    assert int(w[NONFINITE]) == 0
-    return img, simg, (int(st[2]), int(st[3])), int(w[SUSPENDED]), int(w[RESUMED])
+    w = ds.diag_words(N.PRT_DIAG_WORDS)
+    assert int(w[N.PRT_DIAG_NONFINITE]) == 0
+    return img, simg, (int(st[2]), int(st[3])), int(w[N.PRT_DIAG_SUSPENDED]), int(w[N.PRT_DIAG_RESUMED])
 
 
 def _tiles(W, H, tile):

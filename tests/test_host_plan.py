@@ -139,6 +139,179 @@ def test_frame_windows_of_a_launch(built, chunk):
         assert got == [[0, T, 0, n_frames]]
 
 
+# ---------------------------------------------------------------- LDS layouts and the variant choice
+# The layouts of prt_lds_layout.h and the size-only launch decisions of prt_plan.cpp against the four
+# statements they replaced, restated here from their text: trace_kernel's and trace_kernel_pool's pointer
+# chains, lds_scene_bytes() and trace_smem_bytes(), and the rules of lds_fits4 / default_variant /
+# launch_variant.  Sizes are (n_node_f4, n_tri_f4, n_tri, n_mat, n_lt, n_light, stack) as int64.
+
+KB = 256                      # kBlock
+POOL_F4, QUEUE_F4, CTL_F4 = 7 * KB // 4, 2 * KB // 16, 3
+LDS_VARS, POOL_VARS = (1, 2, 4, 6, 7, 8), (7, 8)
+
+
+def _sizes(n_node4=1, n_refs=1, n_tri=1, n_mat=1, n_lt=1, n_light=1, stack=1):
+    """A size tuple from counts: whole BVH4 nodes of 8 float4 (the layouts' precondition n_node_f4 % 8 == 0)
+    and triangle records of 3 float4."""
+    return np.array([8 * n_node4, 3 * n_refs, n_tri, n_mat, n_lt, n_light, stack], np.int64)
+
+
+def _old_scene_bytes(z):
+    nn, tf4, nt, nm, nlt, nl, _ = z
+    return 16 * (7 * nn + tf4 + 7 * nt + 2 * nm + 4 * nlt) + 4 * (nl + 1)
+
+
+def _old_smem(stack, var, z):
+    nn, tf4, nt, nm, nlt, nl, lds_stack = z
+    if var in POOL_VARS:
+        return (lds_stack * KB * 2 + 16 * (POOL_F4 + QUEUE_F4 + CTL_F4) +
+                16 * (7 * nn + tf4 + 4 * nlt + (nl + 4) // 4 + 2 * nm))
+    b = stack * KB * (2 if var in LDS_VARS else 4)
+    return b + _old_scene_bytes(z) if var in LDS_VARS else b
+
+
+def _old_trace_regions(z):
+    """trace_kernel's pointer chain: (float4 offset, bytes its copy loop fills) per region, in order."""
+    nn, tf4, nt, nm, nlt, nl, stack = z
+    sn = stack * KB * 2 // 16
+    st4 = sn + 56 * (nn // 8)
+    snm = st4 + tf4
+    sfr = snm + nt
+    smt = sfr + 6 * nt
+    slv = smt + 2 * nm
+    slo = slv + 4 * nlt
+    return [(0, stack * KB * 2), (sn, 16 * 56 * (nn // 8)), (st4, 16 * tf4), (snm, 16 * nt), (sfr, 16 * 6 * nt),
+            (smt, 16 * 2 * nm), (slv, 16 * 4 * nlt), (slo, 4 * (nl + 1))]
+
+
+def _old_pool_regions(z):
+    """trace_kernel_pool's pointer chain, likewise."""
+    nn, tf4, nt, nm, nlt, nl, stack = z
+    pool = stack * KB * 2 // 16
+    queue = pool + POOL_F4
+    ctl = pool + POOL_F4 + QUEUE_F4
+    sn = pool + POOL_F4 + QUEUE_F4 + CTL_F4
+    st4 = sn + 56 * (nn // 8)
+    slv = st4 + tf4
+    slo = slv + 4 * nlt
+    smt = slv + 4 * nlt + (nl + 4) // 4
+    return [(0, stack * KB * 2), (pool, 4 * 7 * KB), (queue, 2 * KB), (ctl, 4 * 12), (sn, 16 * 56 * (nn // 8)),
+            (st4, 16 * tf4), (slv, 16 * 4 * nlt), (slo, 4 * (nl + 1)), (smt, 16 * 2 * nm)]
+
+
+def _old_fits(z):
+    return bool(_old_scene_bytes(z) <= 24 * 1024 and z[0] // 8 < 0x7FFF and (z[1] // 3) * 8 <= 32768)
+
+
+def _old_variant(z, need4, stack4, mis):
+    z = z.copy()
+    z[6] = need4   # size_params: P.lds_stack = need4
+    lds = _old_fits(z) and stack4 != 0
+    if mis:
+        return 4 if lds else 5
+    if not lds:
+        return 3
+    if need4 <= 32 and _old_smem(16, 7, z) * 7 <= 160 * 1024:
+        return 7
+    smem = _old_smem(stack4, 1, z)
+    return 1 if smem * 7 <= 160 * 1024 else 6 if smem * 6 <= 160 * 1024 else 2
+
+
+def _with_total(total, fn, **counts):
+    """The size tuple of `counts` with n_refs, n_mat and n_lt chosen so that fn(sizes) == total."""
+    for n_mat in range(1, 8):
+        for n_lt in range(1, 5):
+            z0 = _sizes(n_refs=0, n_mat=n_mat, n_lt=n_lt, **counts)
+            rest = total - fn(z0)
+            if rest >= 48 * counts["n_tri"] and rest % 48 == 0:
+                z = _sizes(n_refs=int(rest // 48), n_mat=n_mat, n_lt=n_lt, **counts)
+                assert fn(z) == total
+                return z
+    raise AssertionError("no tuple with total %d" % total)
+
+
+def _size_tuples():
+    t = {"ones": _sizes()}
+    for nl in (1, 3, 4, 5):
+        t["n_light_%d" % nl] = _sizes(n_node4=3, n_refs=9, n_tri=7, n_mat=2, n_lt=nl + 1, n_light=nl, stack=10)
+    t["cornell_sized"] = _sizes(n_node4=11, n_refs=36, n_tri=36, n_mat=8, n_lt=2, n_light=1, stack=10)
+    # lds_fits' 24 KiB: the last copy that fits and one float4 more (n_light = 3: a 16-byte offsets tail)
+    for total in (24576, 24592):
+        t["scene_%d" % total] = _with_total(total, _old_scene_bytes, n_node4=10, n_tri=40, n_light=3, stack=10)
+    for n4 in (0x7FFE, 0x7FFF):
+        t["n_node4_%#x" % n4] = _sizes(n_node4=n4, n_refs=8, n_tri=8, stack=10)
+    for refs in (4096, 4097):
+        t["n_refs_%d" % refs] = _sizes(n_node4=2, n_refs=refs, n_tri=8, stack=10)
+    # default_variant's 160 KiB steps: the largest total (whole float4: n_light = 3) that passes, and
+    # the next.  The pooled kernel at seven blocks; then, with few enough normals and frames that the pooled
+    # kernel is already out, the phase-aligned one at seven and at six.
+    for total in (23392, 23408):
+        assert (total * 7 <= 160 * 1024) == (total == 23392)
+        t["pool7_%d" % total] = _with_total(total, lambda z: _old_smem(16, 7, z), n_node4=6, n_tri=60, n_light=3,
+                                            stack=10)
+        t["lds7_%d" % total] = _with_total(total, lambda z: _old_smem(10, 1, z), n_node4=6, n_tri=20, n_light=3,
+                                           stack=10)
+    for total in (27296, 27312):
+        assert (total * 6 <= 160 * 1024) == (total == 27296)
+        t["lds6_%d" % total] = _with_total(total, lambda z: _old_smem(10, 1, z), n_node4=6, n_tri=20, n_light=3,
+                                           stack=10)
+    return t
+
+
+SIZE_TUPLES = _size_tuples()
+
+
+def test_size_tuples_sit_on_the_thresholds_they_name():
+    t = SIZE_TUPLES
+    assert _old_fits(t["scene_24576"]) and not _old_fits(t["scene_24592"])
+    assert [_old_variant(t[k], 10, 10, False) for k in ("pool7_23392", "pool7_23408")] == [7, 1]
+    assert [_old_variant(t[k], 10, 10, False) for k in ("lds7_23392", "lds7_23408", "lds6_27296", "lds6_27312")] == \
+        [1, 6, 6, 2]
+
+
+def test_lds_layouts_match_the_four_statements_they_replaced(built):
+    names = list(SIZE_TUPLES)
+    reps = _run(built, "layout", *[int(v) for k in names for v in SIZE_TUPLES[k]])
+    assert len(reps) == len(names)
+    for name, rep in zip(names, reps):
+        z = SIZE_TUPLES[name]
+        stack = int(z[6])
+        for key, regions, total in (("trace", _old_trace_regions(z), _old_smem(stack, 1, z)),
+                                    ("pool", _old_pool_regions(z), _old_smem(16, 7, z))):
+            off = rep[key]
+            assert off == [int(o) for o, _ in regions], (name, key)
+            ends = [16 * int(o) + int(b) for o, b in regions]
+            # in order and disjoint: a region starts at or after the end of the one before it
+            assert all(16 * off[i + 1] >= ends[i] for i in range(len(off) - 1)), (name, key)
+            assert off == sorted(off) and off[0] == 0
+            # float4-aligned: the offsets are whole float4 by construction; the region before must not
+            # reach into the next one's first float4
+            assert all(16 * off[i + 1] - ends[i] < 16 for i in range(len(off) - 1)), (name, key)
+            assert ends[-1] == rep[key + "_bytes"] == int(total), (name, key)
+        assert rep["scene_bytes"] == int(_old_scene_bytes(z)), name
+        assert rep["smem"] == [int(_old_smem(stack, var, z)) for var in range(0, 10)], name
+
+
+def test_variant_choice_matches_the_parent_rule(built):
+    cases = []
+    for name, z in SIZE_TUPLES.items():
+        need4 = int(z[6])
+        stack4 = 10 if need4 <= 10 else 16 if need4 <= 16 else 32
+        for n4, s4 in ((need4, stack4), (need4, 0), (32, 32), (33, 32)):
+            cases.append((name, z, n4, s4))
+    reps = _run(built, "variant", *[int(v) for _, z, n4, s4 in cases for v in list(z[:6]) + [n4, s4]])
+    assert len(reps) == len(cases)
+    seen = set()
+    for (name, z, n4, s4), rep in zip(cases, reps):
+        zz = z.copy()
+        zz[6] = n4
+        assert rep["fits"] == _old_fits(zz), (name, n4, s4)
+        assert rep["nee"] == _old_variant(z, n4, s4, False), (name, n4, s4)
+        assert rep["mis"] == _old_variant(z, n4, s4, True), (name, n4, s4)
+        seen.update((rep["nee"], rep["mis"]))
+    assert seen == {1, 2, 3, 4, 5, 6, 7}   # every variant a default can be (8 is only ever forced)
+
+
 # ---------------------------------------------------------------- knobs and camera
 
 def test_env_int_clamps_and_falls_back(built):

@@ -68,38 +68,40 @@ def main():
             if r > 0:  # round 0 = warm-up
                 res[v].append((ms, wall * 1e3, same))
     samples = W * H * a.spp
+    from pyrenderer_amd import _native as N
     from pyrenderer_amd._native import PRT_FLAG_STATS
+    PH, PL = N.PRT_DIAG_PHASE, N.PRT_DIAG_POOL   # the same words, by the kernel that ran
     for v in a.variants:
         ds.render_tiles(c, W, H, 64, 64, ids, a.spp, a.depth, 0, PRT_FLAG_STATS | vflags(v))
-        dg = ds.diag_words(22).astype(np.float64)   # 17..21: ext / shadow iteration clocks, counts, lanes
-        tot = dg[4] + dg[5] + dg[6]
+        dg = ds.diag_words(PH + N.PRT_DIAG_PHASE_WORDS).astype(np.float64)
+        tot = dg[N.PRT_DIAG_CLK_REFILL] + dg[N.PRT_DIAG_CLK_TRAV] + dg[N.PRT_DIAG_CLK_SHADE]
         if v.rstrip("np") in ("7", "8", "9", "10"):
-            # trace_kernel_pool's diag words 17..20: wave E iterations, wave S iterations, lanes of the
+            # trace_kernel_pool's PRT_DIAG_POOL words: wave E iterations, wave S iterations, lanes of the
             # S iterations, shadow rays answered by the light-triangle test
             print(json.dumps({"variant": v, "pool": {
-                "e_wave_iters": int(dg[17]), "s_wave_iters": int(dg[18]),
-                "lanes_per_s_iter": round(dg[19] / max(dg[18], 1), 2),
-                "s_iters_per_e_iter": round(dg[18] / max(dg[17], 1), 3),
-                "shadow_queries": int(dg[3]), "answered_by_light_test": int(dg[20]),
-                "nodes_per_sample": round(dg[0] / samples, 2), "tris_per_sample": round(dg[1] / samples, 2),
-                "max_stack": int(dg[13])}}), flush=True)
+                "e_wave_iters": int(dg[PL]), "s_wave_iters": int(dg[PL + 1]),
+                "lanes_per_s_iter": round(dg[PL + 2] / max(dg[PL + 1], 1), 2),
+                "s_iters_per_e_iter": round(dg[PL + 1] / max(dg[PL], 1), 3),
+                "shadow_queries": int(dg[N.PRT_DIAG_SHADOW]), "answered_by_light_test": int(dg[PL + 3]),
+                "nodes_per_sample": round(dg[N.PRT_DIAG_NODES] / samples, 2), "tris_per_sample": round(dg[N.PRT_DIAG_TRIS] / samples, 2),
+                "max_stack": int(dg[N.PRT_DIAG_MAX_STACK])}}), flush=True)
             continue
-        print(json.dumps({"variant": v, "diag": {"refill_frac": round(dg[4] / tot, 3), "trav_frac": round(dg[5] / tot, 3),
-                                                 "shade_frac": round(dg[6] / tot, 3), "wave_iters": int(dg[7]),
-                                                 "lanes_per_iter": round(dg[8] / max(dg[7], 1), 2),
-                                                 "nodes_per_sample": round(dg[0] / samples, 2),
-                                                 "tris_per_sample": round(dg[1] / samples, 2),
-                                                 "inner_simd_eff": round(dg[11] / max(dg[9] * 64, 1), 3),
-                                                 "leaf_simd_eff": round(dg[12] / max(dg[10] * 64, 1), 3),
-                                                 "wave_inner_trips_per_iter": round(dg[9] / max(dg[7], 1), 2),
-                                                 "wave_leaf_trips_per_iter": round(dg[10] / max(dg[7], 1), 2),
-                                                 "wave_tri_trips_per_iter": round(dg[15] / max(dg[7], 1), 2),
-                                                 "max_stack": int(dg[13]),
-                                                 "max_nodes_one_query": int(dg[16]),
-                                                 "shadow_iter_time_frac": round(dg[18] / max(dg[17] + dg[18], 1), 3),
-                                                 "ext_iters": int(dg[19]), "shadow_iters": int(dg[20]),
-                                                 "lanes_per_shadow_iter": round(dg[21] / max(dg[20], 1), 2),
-                                                 "lanes_per_ext_iter": round((dg[8] - dg[21]) / max(dg[19], 1), 2)}}),
+        print(json.dumps({"variant": v, "diag": {"refill_frac": round(dg[N.PRT_DIAG_CLK_REFILL] / tot, 3), "trav_frac": round(dg[N.PRT_DIAG_CLK_TRAV] / tot, 3),
+                                                 "shade_frac": round(dg[N.PRT_DIAG_CLK_SHADE] / tot, 3), "wave_iters": int(dg[N.PRT_DIAG_WAVE_ITERS]),
+                                                 "lanes_per_iter": round(dg[N.PRT_DIAG_ACTIVE_LANES] / max(dg[N.PRT_DIAG_WAVE_ITERS], 1), 2),
+                                                 "nodes_per_sample": round(dg[N.PRT_DIAG_NODES] / samples, 2),
+                                                 "tris_per_sample": round(dg[N.PRT_DIAG_TRIS] / samples, 2),
+                                                 "inner_simd_eff": round(dg[N.PRT_DIAG_LANE_INNER] / max(dg[N.PRT_DIAG_WAVE_INNER] * 64, 1), 3),
+                                                 "leaf_simd_eff": round(dg[N.PRT_DIAG_LANE_LEAF] / max(dg[N.PRT_DIAG_WAVE_LEAF] * 64, 1), 3),
+                                                 "wave_inner_trips_per_iter": round(dg[N.PRT_DIAG_WAVE_INNER] / max(dg[N.PRT_DIAG_WAVE_ITERS], 1), 2),
+                                                 "wave_leaf_trips_per_iter": round(dg[N.PRT_DIAG_WAVE_LEAF] / max(dg[N.PRT_DIAG_WAVE_ITERS], 1), 2),
+                                                 "wave_tri_trips_per_iter": round(dg[N.PRT_DIAG_WAVE_TRI] / max(dg[N.PRT_DIAG_WAVE_ITERS], 1), 2),
+                                                 "max_stack": int(dg[N.PRT_DIAG_MAX_STACK]),
+                                                 "max_nodes_one_query": int(dg[N.PRT_DIAG_MAX_QUERY]),
+                                                 "shadow_iter_time_frac": round(dg[PH + 1] / max(dg[PH] + dg[PH + 1], 1), 3),
+                                                 "ext_iters": int(dg[PH + 2]), "shadow_iters": int(dg[PH + 3]),
+                                                 "lanes_per_shadow_iter": round(dg[PH + 4] / max(dg[PH + 3], 1), 2),
+                                                 "lanes_per_ext_iter": round((dg[N.PRT_DIAG_ACTIVE_LANES] - dg[PH + 4]) / max(dg[PH + 2], 1), 2)}}),
               flush=True)
     for v, rows in res.items():
         ms = np.array([x[0] for x in rows])

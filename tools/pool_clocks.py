@@ -1,7 +1,7 @@
 """Where the block-pooled kernel's waves spend their time (diagnostic): a library copy built with
 -DPRT_POOL_CLOCKS accumulates wave-level s_memtime cycles per phase — E (refill / extension query /
 shading + enqueue), waiting at barrier 1, S (pooled shadow queries, or the refill of waves without an S
-chunk), waiting at barrier 2 — into diag words 24..29.  One process, config 2, variant 7.
+chunk), waiting at barrier 2 — into the diag words PRT_DIAG_POOL_CLOCKS (24..29).  One process, config 2, variant 7.
 
     python -m pyrenderer_amd.build --out abtmp/libprt_clk.so -D PRT_POOL_CLOCKS
     python tools/pool_clocks.py --lib abtmp/libprt_clk.so
@@ -45,12 +45,13 @@ def main():
     ids = np.ascontiguousarray(interleaved_tiles(W, H, 64), np.int32)
     out = np.zeros((len(ids) * 64 * 64, 3), np.float32)
     st = np.zeros(4, np.uint64)
-    for flags in (N.PRT_FLAG_STATS, 0):   # the STATS render zeroes the diag words, the clock build adds to 24..27
+    for flags in (N.PRT_FLAG_STATS, 0):   # the STATS render zeroes the diag words, the clock build adds to its own words
         N.check(L.prt_render_tiles(h, N.ptr(cam), W, H, 64, 64, N.ptr(ids), len(ids), cfg["spp"], cfg["depth"], 0,
                                    flags | (a.variant << 8), N.ptr(out), N.ptr(st)))
-    w = np.zeros(30, np.uint64)
-    N.check(L.prt_diag_words(h, N.ptr(w), 30))
-    ck = w[24:30].astype(np.float64)
+    c0, c1 = N.PRT_DIAG_POOL_CLOCKS, N.PRT_DIAG_POOL_CLOCKS + N.PRT_DIAG_POOL_CLOCKS_WORDS
+    w = np.zeros(c1, np.uint64)
+    N.check(L.prt_diag_words(h, N.ptr(w), c1))
+    ck = w[c0:c1].astype(np.float64)
     tot = ck.sum()
     names = ("E_shade_enqueue", "barrier1", "S", "barrier2", "E_refill", "E_traversal")
     print(json.dumps({"variant": a.variant, "config": a.config, "wave_cycles": float(tot),

@@ -1,6 +1,6 @@
 // host_check — host driver for the sanitizer build of libprt's GPU-free host arithmetic
-// (pyrenderer_amd/csrc/prt_plan.cpp: standard library + prt_internal.h only).  tools/sanitize/Makefile
-// compiles both with g++ -fsanitize=address,undefined,float-cast-overflow, every finding fatal;
+// (pyrenderer_amd/csrc/prt_plan.cpp: standard library + prt_internal.h, prt_lds_layout.h and
+// prt_variant_table.h only).  tools/sanitize/Makefile compiles both with g++ -fsanitize=address,undefined,float-cast-overflow, every finding fatal;
 // tests/test_host_plan.py runs the modes below and checks the printed values against numpy.
 //
 //   host_check origins <tiles_x> <tw> <th> <id>...          packed origins of tile ids
@@ -12,6 +12,11 @@
 //   host_check frames <spp> <n_frames> <chunk>              [s0, n, f0, f1] of every launch of chunk samples
 //   host_check camera <cam.f32>                             cam_fast and the bits of cam_o / cam_k
 //   host_check env <NAME> <lo> <hi> <fallback>              env_int, and spill_lds_entries of it
+//   host_check layout (<n_node_f4> <n_tri_f4> <n_tri> <n_mat> <n_lt> <n_light> <stack>)...
+//       per size tuple: the float4 offsets of trace_lds and pool_lds in region order, their totals in
+//       bytes, lds_scene_bytes, and trace_smem_bytes(stack, var, sizes) for var = 0 .. kVarLast + 1
+//   host_check variant (<n_node_f4> <n_tri_f4> <n_tri> <n_mat> <n_lt> <n_light> <need4> <stack4>)...
+//       per tuple: lds_fits, and choose_variant without and with the MIS estimator
 //   host_check scene <dir> <n_tri> <n_sph> <n_mat> <n_light>
 //       reads <dir>/{tri_v,tri_n,sph,mat}.f32 and {tri_mat,sph_mat,light_tri,light_off}.i32 (raw, as
 //       numpy.tofile writes them; a missing file is a NULL argument), validates, and when valid packs
@@ -158,6 +163,38 @@ int main(int argc, char** argv) {
     } else if (mode == "env" && argc == 6) {
         const long long v = prt::env_int(argv[2], num(3), num(4), num(5));
         std::printf("{\"value\": %lld, \"spill_lds\": %d}\n", v, prt::spill_lds_entries(v));
+    } else if (mode == "layout" && argc >= 9 && (argc - 2) % 7 == 0) {
+        std::printf("[");
+        for (int i = 2; i < argc; i += 7) {
+            const prt::LdsSizes z{(int)num(i), (int)num(i + 1), (int)num(i + 2), (int)num(i + 3), (int)num(i + 4),
+                                  (int)num(i + 5), (int)num(i + 6)};
+            const prt::TraceLds t = prt::trace_lds(z);
+            const prt::PoolLds p = prt::pool_lds(z);
+            std::printf("%s{\"trace\": ", i > 2 ? ", " : "");
+            print_list(std::vector<int64_t>{t.stacks, t.nodes, t.tris, t.normals, t.frames, t.mats, t.light_v,
+                                            t.light_off});
+            std::printf(", \"trace_bytes\": %zu, \"pool\": ", t.bytes);
+            print_list(std::vector<int64_t>{p.stacks, p.pool, p.queue, p.ctl, p.nodes, p.tris, p.light_v, p.light_off,
+                                            p.mats});
+            std::printf(", \"pool_bytes\": %zu, \"scene_bytes\": %zu, \"smem\": ", p.bytes, prt::lds_scene_bytes(z));
+            // trace_smem_bytes of every variant id (and the unknown 0 and 9) at the instantiation set z.stack
+            std::vector<size_t> smem;
+            for (int var = 0; var <= prt::kVarLast + 1; ++var) smem.push_back(prt::trace_smem_bytes(z.stack, var, z));
+            print_list(smem);
+            std::printf("}");
+        }
+        std::printf("]\n");
+    } else if (mode == "variant" && argc >= 10 && (argc - 2) % 8 == 0) {
+        std::printf("[");
+        for (int i = 2; i < argc; i += 8) {
+            const int need4 = (int)num(i + 6), stack4 = (int)num(i + 7);
+            const prt::LdsSizes z{(int)num(i), (int)num(i + 1), (int)num(i + 2), (int)num(i + 3), (int)num(i + 4),
+                                  (int)num(i + 5), need4};
+            std::printf("%s{\"fits\": %s, \"nee\": %d, \"mis\": %d}", i > 2 ? ", " : "",
+                        prt::lds_fits(z) ? "true" : "false", prt::choose_variant(z, need4, stack4, false),
+                        prt::choose_variant(z, need4, stack4, true));
+        }
+        std::printf("]\n");
     } else if (mode == "scene" && argc == 7) {
         return scene_mode(argv[2], num(3), num(4), (int)num(5), (int)num(6));
     } else {

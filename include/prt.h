@@ -106,6 +106,13 @@ int prt_bvh_build(const float* tri_v, int64_t n_tri, int32_t max_leaf, void** ou
 int prt_bvh_info(void* bvh, int64_t* info6);
 /* nodes: n_nodes x 16 f32; tris: n_tri x 12 f32 (BVH order); order: n_tri (BVH slot -> triangle) */
 int prt_bvh_export(void* bvh, float* nodes, float* tris, int32_t* order);
+/* The wide tree a scene's kernels traverse, collapsed from this BVH2 (same triangle order and leaf
+ * references): width 4 (every scene) or 8 (scenes the trace kernels keep in LDS).  info4 = n_nodes,
+ * depth (root-to-leaf node count - 1), worst-case traversal stack entries, floats per node (32 / 56).
+ * nodes (NULL: sizes only): n_nodes x floats per node; children in groups of four, group g at 24 g floats:
+ * lo.x[4] hi.x[4] lo.y[4] hi.y[4] lo.z[4] hi.z[4], then the child refs (int bits) after the last group;
+ * empty slots: lo = +inf, hi = -inf, ref = 0x7FFFFFFF. */
+int prt_bvh_collapse(void* bvh, int32_t width, int64_t* info4, float* nodes);
 void prt_bvh_destroy(void* bvh);
 
 /* -------------------------------------------------------------- scene ----
@@ -330,9 +337,10 @@ int prt_features(void* scene, const float* cam, int W, int H, int first_sample, 
 int prt_features_device(void* scene, const float* cam, int W, int H, int first_sample, int samples, uint64_t seed,
                         uint32_t flags, float* d_out, void* stream);
 /* trace-kernel variant chosen for this scene's large launches when flags select none:
- * out4 = {variant, BVH arity (2 or 4), bit 0 scene LDS-resident | bit 1 quantised nodes,
+ * out4 = {variant, BVH arity (4, or 8: an LDS reference kernel over the scene's eight-wide tree, env
+ *         PRT_LDS_WIDTH), bit 0 scene LDS-resident | bit 1 quantised nodes,
  *         LDS traversal stack entries per lane: the instantiation set, or for the pooled kernel
- *         (7 / 8) the exact BVH4 bound its stack is sized to} */
+ *         (7 / 8) the exact bound of its tree that its stack is sized to} */
 int prt_scene_kernel(void* scene, int32_t* out4);
 /* the same for one trace launch of n_items (pixel, sample) work items with these render flags: an
  * LDS-resident scene whose pool fits seven blocks per CU takes the block-pooled shadow kernel (7) at

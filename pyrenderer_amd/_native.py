@@ -92,6 +92,7 @@ EXPORTS = {
     "prt_bvh_build": (_i, [_vp, _i64, _i32, _vp]),
     "prt_bvh_info": (_i, [_vp, _vp]),
     "prt_bvh_export": (_i, [_vp, _vp, _vp, _vp]),
+    "prt_bvh_collapse": (_i, [_vp, _i32, _vp, _vp]),
     "prt_bvh_destroy": (None, [_vp]),
     "prt_scene_create": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "prt_scene_info": (_i, [_vp, _vp]),
@@ -202,6 +203,15 @@ class Bvh:
         order = np.zeros(self.n_tri, np.int32)
         check(lib().prt_bvh_export(self.h, ptr(nodes), ptr(tris), ptr(order)))
         return nodes, tris, order
+
+    def collapse(self, width=4):
+        """prt_bvh_collapse: the wide tree of `width` (4 or 8) children per node as (nodes, depth,
+        stack_need): nodes (n, 32) or (n, 56) float32 in the layout include/prt.h describes."""
+        info = np.zeros(4, np.int64)
+        check(lib().prt_bvh_collapse(self.h, width, ptr(info), None))
+        nodes = np.zeros((int(info[0]), int(info[3])), np.float32)
+        check(lib().prt_bvh_collapse(self.h, width, ptr(info), ptr(nodes)))
+        return nodes, int(info[1]), int(info[2])
 
     def __del__(self):
         if getattr(self, "h", None):

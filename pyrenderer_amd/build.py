@@ -18,6 +18,10 @@ SOURCES = ["prt_kernels.hip", "prt_plan.cpp", "prt_scene.cpp", "prt_capi.cpp", "
 # per-unit extra flags: the pooled-shadow kernel is register-allocated with LLVM's AMDGPU
 # pressure trackers (4 instead of 39 spilled VGPRs at 7 waves/SIMD; prt_trace_pool.hip)
 UNIT_FLAGS = {"prt_trace_pool.hip": ["-mllvm", "--amdgpu-use-amdgpu-trackers"]}
+# ... and compiled a second time for the eight-wide tree of LDS-resident scenes (SOURCES holds the
+# four-wide unit)
+POOL_UNIT = "prt_trace_pool.hip"
+POOL_WIDE = [(8, "prt_trace_pool8.o")]
 # the persistent trace kernel's instantiation sets: prt_trace_inst.hip compiled once
 # per (traversal stack entries, stats) pair — the objects build in parallel
 TRACE_INST = "prt_trace_inst.hip"
@@ -67,6 +71,7 @@ def kernel_sha():
             h.update(fh.read())
     h.update(" ".join(FLAGS).encode())
     h.update(repr(sorted(UNIT_FLAGS.items())).encode())
+    h.update(repr(POOL_WIDE).encode())
     return h.hexdigest()[:16]
 
 
@@ -92,6 +97,8 @@ def build(force=False, verbose=False, out=None, defs=()):
              for f in SOURCES + AUX_SOURCES]
     units += [(os.path.join(CSRC, TRACE_INST), os.path.join(obj_dir, f"prt_trace_{st}_{tt}.o"),
                [f"-DPRT_STACK={st}", f"-DPRT_STATS={tt}"]) for st, tt in TRACE_SETS]
+    units += [(os.path.join(CSRC, POOL_UNIT), os.path.join(obj_dir, obj), UNIT_FLAGS[POOL_UNIT] + [f"-DPRT_POOL_WIDTH={w}"])
+              for w, obj in POOL_WIDE]
     cmds = [[hipcc] + FLAGS + extra + d + ["-c", src, "-o", obj] for src, obj, d in units]
     if verbose:
         print(f"compiling {len(cmds)} units with {_jobs()} jobs", flush=True)

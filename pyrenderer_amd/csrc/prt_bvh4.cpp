@@ -1,5 +1,6 @@
 // prt_bvh4.cpp — what consumes the flat BVH2 (BvhHost, prt_bvh.cpp): its collapse into four-wide
-// nodes, SAH-optimal (DpCollapse) or greedy, and the 8-bit quantisation of those nodes.
+// nodes (and eight-wide ones for LDS-resident scenes), SAH-optimal (DpCollapse) or greedy, and the 8-bit
+// quantisation of the four-wide nodes.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -12,8 +13,11 @@
 namespace prt {
 namespace {
 
-constexpr int kWidth = 4;             // children of one collapsed node
-constexpr int kNode4 = kNode4F4 * 4;  // floats of one collapsed node
+constexpr int kNode4 = kNode4F4 * 4;  // floats of one four-wide node
+// Cost of one visit of a `width`-wide node in the DP, in four-wide visits (ct is relative to those): the
+// eight-wide visit tests two groups of four boxes and pushes up to seven children, 159 (closest-hit) and
+// 129 (any-hit) VALU instructions against 77 and 69 in the pooled kernel's listing
+constexpr double visit_cost(int width) { return width == 4 ? 1.0 : 2.0; }
 constexpr int32_t kEmptyRef = 0x7FFFFFFF;   // ref of an empty slot: the traversal sentinel
 
 // The collapse's knobs, read once per collapse: the env variable through atoi / atof, then the clamp.
@@ -45,15 +49,16 @@ inline Child child_of(const float* n2, int side) {
     return c;
 }
 
-// SAH-optimal collapse of the BVH2 into BVH4 nodes (Ylitie et al. 2017's dynamic program, for
-// four-wide nodes).  Expected cost of a tree = sum over BVH4 nodes of area x 1 (one visit) + sum
-// over leaf entries of area x ct x triangles.  cost[i][k] (k = 2..kWidth) = least cost of representing
-// inner BVH2 node i's subtree by exactly k entries of one BVH4 node, the subtrees below those
-// entries included; cost[i][1] = least cost of i as one entry: its own BVH4 node, or (subtrees of
+// SAH-optimal collapse of the BVH2 into `width`-wide nodes (Ylitie et al. 2017's dynamic program).
+// Expected cost of a tree = sum over wide nodes of area x visit_cost(width) (one visit) + sum
+// over leaf entries of area x ct x triangles.  cost[i][k] (k = 2..width) = least cost of representing
+// inner BVH2 node i's subtree by exactly k entries of one wide node, the subtrees below those
+// entries included; cost[i][1] = least cost of i as one entry: its own wide node, or (subtrees of
 // <= leaf_cap triangles) one leaf of its whole triangle range.  split[i][k] = entries taken from
 // the left child.
 struct DpCollapse {
-    static constexpr int kStride = kWidth + 1;   // table row of one node: k = 0..kWidth
+    const int kWidth;             // children of one collapsed node
+    const int kStride;            // table row of one node: k = 0..kWidth
     std::vector<double> cost;     // n2 * kStride
     std::vector<int8_t> split;    // n2 * kStride
     std::vector<double> area;     // n2: surface area of inner node i
@@ -63,7 +68,8 @@ struct DpCollapse {
     const BvhHost& b2;
     double ct;
     int leaf_cap;
-    DpCollapse(const BvhHost& b, double ct_, int leaf_cap_) : b2(b), ct(ct_), leaf_cap(leaf_cap_) {
+    DpCollapse(const BvhHost& b, double ct_, int leaf_cap_, int width)
+        : kWidth(width), kStride(width + 1), b2(b), ct(ct_), leaf_cap(leaf_cap_) {
         const int64_t n2 = b2.n_nodes;
         cost.assign((size_t)n2 * kStride, INFINITY);
         split.assign((size_t)n2 * kStride, 0);
@@ -103,7 +109,7 @@ struct DpCollapse {
             // a single-leaf scene (one empty child) still gets a node of its one entry
             double best = c[1].empty ? side(c[0], 1) : INFINITY;
             for (int k = 2; k <= kWidth; ++k) best = std::min(best, ci[k]);
-            ci[1] = area[(size_t)i] + best;
+            ci[1] = area[(size_t)i] * visit_cost(kWidth) + best;
             int64_t f[2];
             int32_t m[2];
             for (int s = 0; s < 2; ++s) range(c[s], &f[s], &m[s]);
@@ -143,7 +149,7 @@ struct DpCollapse {
             else expand(c[s].ref, parts[s], outc);
         }
     }
-    // children of the BVH4 node made from inner node i: its cheapest cut
+    // children of the wide node made from inner node i: its cheapest cut
     void children(int32_t i, std::vector<Child>* outc) const {
         const double* ci = &cost[(size_t)i * kStride];
         if (child_of(node(i), 1).empty) {
@@ -158,14 +164,14 @@ struct DpCollapse {
     }
 };
 
-// greedy children of the BVH4 node made from inner node i: its two children, the inner one with the
-// largest surface area opened again and again until the node is full
-void greedy_children(const BvhHost& b2, int32_t i, std::vector<Child>* ch) {
+// greedy children of the `width`-wide node made from inner node i: its two children, the inner one with
+// the largest surface area opened again and again until the node is full
+void greedy_children(const BvhHost& b2, int32_t i, int width, std::vector<Child>* ch) {
     for (int side = 0; side < 2; ++side) {
         Child c = child_of(b2.nodes.data() + (size_t)i * 16, side);
         if (!c.empty) ch->push_back(c);
     }
-    while ((int)ch->size() < kWidth) {
+    while ((int)ch->size() < width) {
         int best = -1;
         double ba = -1.0;
         for (size_t k = 0; k < ch->size(); ++k)
@@ -179,17 +185,20 @@ void greedy_children(const BvhHost& b2, int32_t i, std::vector<Child>* ch) {
     }
 }
 
-// Writes the BVH4 top-down from the root: `children(i, &ch)` names the entries of the node made from
-// inner BVH2 node i, each inner entry gets the next node slot.
+// Writes the wide BVH (Bvh4Host: kWidth 4, Bvh8Host: kWidth 8) top-down from the root: `children(i, &ch)`
+// names the entries of the node made from inner BVH2 node i, each inner entry gets the next node slot.
+// Children go in groups of four: plane p (lo.x, hi.x, lo.y, hi.y, lo.z, hi.z) of child k at float
+// (k / 4) * 24 + 4 p + k % 4, the refs after the last group.
 // anc = entries the traversal can hold for the node's strict ancestors: a visit continues
 // with one hit child and pushes the others (<= children - 1), and LIFO order means the
 // stack below a node holds only siblings of its ancestors (traverse_ww4)
-template <class Chooser>
-void emit_bvh4(const Chooser& children, Bvh4Host* out) {
+template <int kWidth, class Host, class Chooser>
+void emit_wide(const Chooser& children, Host* out) {
+    constexpr int kNode = kWidth == 4 ? kNode4 : kNode8F4 * 4;   // floats of one node
     struct Item { int32_t b2node; int32_t slot; int32_t depth; int32_t anc; };
     std::vector<Item> work;
     out->nodes.clear();
-    out->nodes.resize(kNode4, 0.0f);
+    out->nodes.resize(kNode, 0.0f);
     out->n_nodes = 1;
     out->depth = 0;
     int32_t max_anc = 0;
@@ -200,14 +209,15 @@ void emit_bvh4(const Chooser& children, Bvh4Host* out) {
         work.pop_back();
         ch.clear();
         children(it.b2node, &ch);
-        float* f = out->nodes.data() + (size_t)it.slot * kNode4;
+        float* f = out->nodes.data() + (size_t)it.slot * kNode;
         for (int k = 0; k < kWidth; ++k) {
             bool ok = k < (int)ch.size();
+            const int at = (k / 4) * 24 + k % 4;
             for (int a = 0; a < 3; ++a) {
                 // empty slot: inverted box (lo = +inf, hi = -inf) is missed by every ray
                 // whose direction has one finite 1/d, whatever t_max (even NaN / inf)
-                f[(2 * a) * kWidth + k] = ok ? ch[k].lo[a] : INFINITY;
-                f[(2 * a + 1) * kWidth + k] = ok ? ch[k].hi[a] : -INFINITY;
+                f[at + (2 * a) * 4] = ok ? ch[k].lo[a] : INFINITY;
+                f[at + (2 * a + 1) * 4] = ok ? ch[k].hi[a] : -INFINITY;
             }
             // empty slot ref = the traversal sentinel: if a NaN ray ever "hits" it, the lane's
             // traversal ends instead of restarting at the root (a NaN ray hits nothing anyway)
@@ -215,8 +225,8 @@ void emit_bvh4(const Chooser& children, Bvh4Host* out) {
             if (ok) {
                 if (ch[k].ref >= 0) {
                     ref = (int32_t)out->n_nodes++;
-                    out->nodes.resize((size_t)out->n_nodes * kNode4, 0.0f);
-                    f = out->nodes.data() + (size_t)it.slot * kNode4;   // storage may have moved
+                    out->nodes.resize((size_t)out->n_nodes * kNode, 0.0f);
+                    f = out->nodes.data() + (size_t)it.slot * kNode;   // storage may have moved
                     work.push_back({ch[k].ref, ref, it.depth + 1, it.anc + (int32_t)ch.size() - 1});
                 } else {
                     ref = ch[k].ref;
@@ -227,22 +237,27 @@ void emit_bvh4(const Chooser& children, Bvh4Host* out) {
         out->depth = std::max(out->depth, it.depth);
         max_anc = std::max(max_anc, it.anc);
     }
-    // the sentinel, the deepest node's ancestor entries, and the <= 3 slots a visit writes
-    // above the top unconditionally (visit_node4); <= 3 (depth + 1) + 1, the per-level bound
+    // the sentinel, the deepest node's ancestor entries, and the <= kWidth - 1 slots a visit writes
+    // above the top unconditionally (visit_node4, visit_node8); <= (kWidth - 1) (depth + 1) + 1, the
+    // per-level bound
     out->stack_need = 1 + max_anc + (kWidth - 1);
+}
+
+template <int kWidth, class Host>
+void collapse_wide(const BvhHost& b2, Host* out) {
+    const CollapseKnobs knobs;
+    if (knobs.dp) {
+        const DpCollapse dp(b2, knobs.ct, knobs.leaf_cap, kWidth);
+        emit_wide<kWidth>([&](int32_t i, std::vector<Child>* ch) { dp.children(i, ch); }, out);
+    } else {
+        emit_wide<kWidth>([&](int32_t i, std::vector<Child>* ch) { greedy_children(b2, i, kWidth, ch); }, out);
+    }
 }
 
 }  // namespace
 
-void collapse_bvh4(const BvhHost& b2, Bvh4Host* out) {
-    const CollapseKnobs knobs;
-    if (knobs.dp) {
-        const DpCollapse dp(b2, knobs.ct, knobs.leaf_cap);
-        emit_bvh4([&](int32_t i, std::vector<Child>* ch) { dp.children(i, ch); }, out);
-    } else {
-        emit_bvh4([&](int32_t i, std::vector<Child>* ch) { greedy_children(b2, i, ch); }, out);
-    }
-}
+void collapse_bvh4(const BvhHost& b2, Bvh4Host* out) { collapse_wide<4>(b2, out); }
+void collapse_bvh8(const BvhHost& b2, Bvh8Host* out) { collapse_wide<8>(b2, out); }
 
 void quantize_bvh4(const Bvh4Host& b4, float pad, std::vector<float>* out) {
     out->assign((size_t)b4.n_nodes * 16, 0.0f);

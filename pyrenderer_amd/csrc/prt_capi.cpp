@@ -117,14 +117,20 @@ int trace_setup(Scene* s, RenderCtx* cx, uint32_t flags, int64_t n_items, TraceP
     if (variant_mis(var) != mis)
         return fail(PRT_ERR_ARG, "PRT_FLAG_MIS_NEE must be set exactly for the MIS estimator variants");
     const bool spill = variant_spills(var);
-    if (s->stack4 == 0 && !spill) return fail(PRT_ERR_ARG, "BVH4 too deep for the LDS traversal stack variants");
+    // the LDS reference kernels traverse the scene's tree of lds_width children (prt_plan.h), all others the BVH4
+    const int width = variant_width(s, var), need = variant_need(s, var);
+    if (variant_stack(s, var) == 0 && !spill) return fail(PRT_ERR_ARG, "BVH4 too deep for the LDS traversal stack variants");
     if (variant_quantized(var)) {
         P.nodes = (const float4*)s->nodes4q.p;
         P.n_node_f4 = (int)s->n_node4q_f4;
+    } else if (width == 8) {
+        P.nodes = (const float4*)s->nodes8.p;
+        P.n_node_f4 = (int)s->n_node8_f4;
     }
+    P.lds_width = width;
     const bool lds_var = variant_uses_lds(var);
-    if (lds_var && !lds_fits4(s)) return fail(PRT_ERR_ARG, "scene too large for the LDS variant");
-    if (variant_pool(var) && (s->need4 > 32 || s->need4 < 1))
+    if (lds_var && !lds_fits4(s, var)) return fail(PRT_ERR_ARG, "scene too large for the LDS variant");
+    if (variant_pool(var) && (need > 32 || need < 1))
         return fail(PRT_ERR_ARG, "BVH4 too deep for the pooled-shadow variant's LDS stack");
     // while-while leaf-phase entry: LDS scenes wait for every descending lane's leaf (their
     // leaves are cheap and traversals short); global scenes enter the leaf phase once at
@@ -133,8 +139,10 @@ int trace_setup(Scene* s, RenderCtx* cx, uint32_t flags, int64_t n_items, TraceP
     // Leaf-phase exit: back to descending once at most 8 (LDS) / 24 (global) lanes still
     // hold a leaf (C2 5.25 -> 5.04 ms in round 1, flat for 8-16 now; C4 with pixel-major
     // chunks 17.37-17.46 ms at 24 against 17.50-17.64 at 12 in three interleaved rounds,
-    // profiles/r03/s1_baseline/leafexit/)
-    P.lds_stack = s->need4;
+    // profiles/r03/s1_baseline/leafexit/).  The eight-wide tree keeps 8: C2 3.506 / 3.377 / 3.376 / 3.385 /
+    // 3.412 / 3.446 ms per launch at 0 / 4 / 6 / 8 / 10 / 12, and 3.504 at the 16 that the trip model
+    // preferred (profiles/r13/lds_bvh8/)
+    P.lds_stack = need;
     P.leaf_break = s->leaf_break >= 0 ? s->leaf_break : (lds_var ? 0 : 16);
     P.leaf_exit = s->leaf_exit >= 0 ? s->leaf_exit : (lds_var ? 8 : 24);
     const int occ = variant_occ(s, var, stats);

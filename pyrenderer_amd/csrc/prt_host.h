@@ -91,6 +91,13 @@ struct Scene {
     int64_t n_node4_f4 = 0;
     int stack4 = 0;                  // stack variant for the BVH4 (0 = BVH4 unusable)
     int need4 = 0;                   // worst-case BVH4 traversal stack entries
+    // the BVH8 of an LDS-resident scene (prt_internal.h Bvh8Host; n_node8_f4 = 0: none), its worst-case stack
+    // entries and stack variant, and the width the LDS reference kernels traverse (prt_plan.h lds_width; env
+    // PRT_LDS_WIDTH read at scene creation)
+    DevBuf nodes8;
+    int64_t n_node8_f4 = 0;
+    int need8 = 0, stack8 = 0;
+    int lds_width = 4;
     int leaf_break = -1;             // env PRT_LEAF_BREAK (0..64); -1: per variant (trace launch)
     int leaf_exit = -1;              // env PRT_LEAF_EXIT (0..64); -1: per variant (trace launch)
     int resume_min = 32;             // resume variants (env PRT_RESUME_MIN; C4 after the r02 BVH fixes: 16 / 24 / 32 / 40 / 48 -> 19.4 / 19.1 / 19.0 / 19.4 / 19.8 ms)
@@ -127,7 +134,10 @@ struct Scene {
 
 // ---- prt_scene.cpp: the scene part of a launch's parameters, and the variant choice
 void scene_params(Scene* s, TraceParams& P);
-bool lds_fits4(const Scene* s);
+int variant_width(const Scene* s, int var);           // children per node of the tree variant `var` traverses
+int variant_need(const Scene* s, int var);            // ... and that tree's worst-case stack entries
+LdsSizes scene_sizes(const Scene* s, int var);        // the scene's sizes as variant `var` lays them out in LDS
+bool lds_fits4(const Scene* s, int var);
 int launch_variant(const Scene* s, uint32_t flags);   // the flags' variant, or the scene's default
 int variant_stack(const Scene* s, int var);
 int variant_occ(Scene* s, int var, bool stats);       // blocks per CU (>= 1)

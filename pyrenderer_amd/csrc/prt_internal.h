@@ -54,6 +54,19 @@ struct Bvh4Host {
 };
 void collapse_bvh4(const BvhHost& b2, Bvh4Host* out);
 
+// BVH8 collapsed from the same BVH2, for the scenes the trace kernels keep in LDS (prt_plan.h lds_fits).
+// One node = 14 x float4 = 224 B, the child boxes in SoA as two groups of four: f[0..5] = lo.x, hi.x,
+// lo.y, hi.y, lo.z, hi.z of children 0-3, f[6..11] the same of children 4-7, f[12..13] the eight child
+// refs (int bits).  Empty slots as in Bvh4Host.
+constexpr int kNode8F4 = 14;
+struct Bvh8Host {
+    std::vector<float> nodes;      // n_nodes * 56
+    int64_t n_nodes = 0;
+    int32_t depth = 0;             // max root-to-leaf node count - 1
+    int32_t stack_need = 0;        // worst-case traversal stack entries: a visit pushes up to 7 children
+};
+void collapse_bvh8(const BvhHost& b2, Bvh8Host* out);
+
 // Quantised BVH4 for scenes read from HBM: one node = 4 x float4 = 64 B (two per
 // 128-B cache line, half the BVH4 footprint):
 //   f[0] = (origin.x, origin.y, origin.z, s.x)    s = grid step per axis (range / 254, rounded up)

@@ -68,10 +68,13 @@ struct TraceParams {
                               // [0.5, 2] (host-checked): the shading quotients' cheap guards (prt_math.h)
     int pool_resume_min;      // pool kernel: leave the extension traversal once at most this many lanes still traverse and
                               // resume the unfinished queries in the next iteration (0: off; env PRT_POOL_RESUME_MIN)
+    int lds_width;            // LDS reference kernels: children per node of the tree at `nodes` (4: BVH4, 8: BVH8,
+                              // prt_internal.h); picks the kernel instantiation and the LDS layout
 };
 // the sizes of P's scene that the LDS layouts depend on (prt_lds_layout.h), with `stack` entries per lane
-PRT_HD inline LdsSizes lds_sizes(const TraceParams& P, int stack) {
-    return LdsSizes{P.n_node_f4, P.n_tri_f4, P.n_tri, P.n_mat, P.n_lt, P.n_light, stack};
+// and the tree of `width` children per node: the kernels pass their instantiation's, the host P.lds_width
+PRT_HD inline LdsSizes lds_sizes(const TraceParams& P, int stack, int width) {
+    return LdsSizes{P.n_node_f4, P.n_tri_f4, P.n_tri, P.n_mat, P.n_lt, P.n_light, stack, width == 8 ? 8 : 4};
 }
 
 // camera rays of a launch: rays = (d, rng state); ray_o = per-ray origins (cameras other than the affine
@@ -104,15 +107,26 @@ hipError_t launch_scatter(const float* packed, const uint32_t* tile_xy, int n_sl
 hipError_t launch_scatter_frames(const float* packed, const uint32_t* tile_xy, int n_slots, int group_slots,
                                  int64_t group_pitch, int n_frames, int64_t src_fpitch, int64_t dst_fpitch, int log_tw,
                                  int log_tpx, int x0, int y0, int w, int h, float* out, hipStream_t stream);
-int trace_blocks_per_cu(int stack, int var, bool stats, size_t smem);
+int trace_blocks_per_cu(int stack, int var, bool stats, int width, size_t smem);
 // mismatches of the fast reciprocal sequence against 1 / b over all 2^32 floats, by class of |b|
 // (8 counters: zero, denormal, < 2^-40, [2^-40, 2^40], (2^40, 2^126], > 2^126, inf, NaN)
 hipError_t launch_rcp_selftest(unsigned long long* d_out, hipStream_t stream);
 // the fast sequences' guards over all 2^32 floats (10 counters, prt_kernels.hip guard_selftest_kernel)
 hipError_t launch_guard_selftest(unsigned long long* d_out, hipStream_t stream);
-// the block-pooled shadow-query kernel (prt_trace_pool.hip): launch / blocks per CU by (stats, waves per EU)
-// the pooled kernel's lean instantiation (no sphere or specular code) runs when P.plain is set
-hipError_t launch_trace_pool(const TraceParams& P, bool stats, int wpe, int grid, size_t smem, hipStream_t stream);
-int trace_occ_pool(bool stats, int wpe, size_t smem);
+// the block-pooled shadow-query kernel (prt_trace_pool.hip, one unit per tree width): launch / blocks per CU
+// by (stats, waves per EU); the pooled kernel's lean instantiation (no sphere or specular code) runs when
+// P.plain is set.  launch_trace_pool / trace_occ_pool pick the unit of P.lds_width / `width`.
+hipError_t launch_trace_pool4(const TraceParams& P, bool stats, int wpe, int grid, size_t smem, hipStream_t stream);
+hipError_t launch_trace_pool8(const TraceParams& P, bool stats, int wpe, int grid, size_t smem, hipStream_t stream);
+int trace_occ_pool4(bool stats, int wpe, size_t smem);
+int trace_occ_pool8(bool stats, int wpe, size_t smem);
+inline hipError_t launch_trace_pool(const TraceParams& P, bool stats, int wpe, int grid, size_t smem,
+                                    hipStream_t stream) {
+    return P.lds_width == 8 ? launch_trace_pool8(P, stats, wpe, grid, smem, stream)
+                            : launch_trace_pool4(P, stats, wpe, grid, smem, stream);
+}
+inline int trace_occ_pool(bool stats, int wpe, int width, size_t smem) {
+    return width == 8 ? trace_occ_pool8(stats, wpe, smem) : trace_occ_pool4(stats, wpe, smem);
+}
 
 }  // namespace prt

@@ -26,7 +26,7 @@ namespace prt {
 #define PRT_INST_LIST(X) X(4, 0) X(4, 1) X(10, 0) X(10, 1) X(16, 0) X(16, 1) X(32, 0) X(32, 1)
 #define PRT_DECL_INST(S, T)                                                                              \
     hipError_t launch_trace_##S##_##T(const TraceParams& P, int var, int grid, size_t smem, hipStream_t stream); \
-    int trace_occ_##S##_##T(int var, size_t smem);
+    int trace_occ_##S##_##T(int var, int width, size_t smem);
 PRT_INST_LIST(PRT_DECL_INST)
 #undef PRT_DECL_INST
 
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(const float* __restrict_
 }  // namespace
 
 hipError_t launch_trace(const TraceParams& P, int stack, int var, int grid, bool stats, hipStream_t stream) {
-    size_t smem = trace_smem_bytes(stack, var, lds_sizes(P, P.lds_stack));
+    size_t smem = trace_smem_bytes(stack, var, lds_sizes(P, P.lds_stack, P.lds_width));
     switch (stack) {
         case 4: return stats ? launch_trace_4_1(P, var, grid, smem, stream) : launch_trace_4_0(P, var, grid, smem, stream);
         case 10: return stats ? launch_trace_10_1(P, var, grid, smem, stream) : launch_trace_10_0(P, var, grid, smem, stream);
@@ -408,12 +408,12 @@ hipError_t launch_reduce(const float* buf, float* acc, int n_slots, int64_t j0, 
     return hipGetLastError();
 }
 
-int trace_blocks_per_cu(int stack, int var, bool stats, size_t smem) {
+int trace_blocks_per_cu(int stack, int var, bool stats, int width, size_t smem) {
     switch (stack) {
-        case 4: return stats ? trace_occ_4_1(var, smem) : trace_occ_4_0(var, smem);
-        case 10: return stats ? trace_occ_10_1(var, smem) : trace_occ_10_0(var, smem);
-        case 16: return stats ? trace_occ_16_1(var, smem) : trace_occ_16_0(var, smem);
-        case 32: return stats ? trace_occ_32_1(var, smem) : trace_occ_32_0(var, smem);
+        case 4: return stats ? trace_occ_4_1(var, width, smem) : trace_occ_4_0(var, width, smem);
+        case 10: return stats ? trace_occ_10_1(var, width, smem) : trace_occ_10_0(var, width, smem);
+        case 16: return stats ? trace_occ_16_1(var, width, smem) : trace_occ_16_0(var, width, smem);
+        case 32: return stats ? trace_occ_32_1(var, width, smem) : trace_occ_32_0(var, width, smem);
         default: return 0;
     }
 }

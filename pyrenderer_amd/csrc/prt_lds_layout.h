@@ -19,13 +19,18 @@ constexpr int kPoolF4 = 7 * kBlock / 4;        // pool SoA: 7 x 256 f32
 constexpr int kQueueF4 = 2 * kBlock / 16;      // queue: 2 x 256 u8, by iteration parity
 constexpr int kCtlF4 = 3;                      // ctl: 12 words
 
-// The sizes the layouts depend on.  n_node_f4 counts the 8 float4 of a global BVH4 node and is a
-// multiple of 8 (collapse_bvh4 writes whole nodes): the LDS copy holds 8 octant copies of 7 float4 per
-// node, 56 * (n_node_f4 / 8) float4, which the layouts write as 7 * n_node_f4 — equal under that
-// precondition only.  n_tri_f4: 3 float4 per triangle record in BVH order; n_mat: materials of 8 floats;
-// n_lt: emitter triangles of 4 float4; n_light: lights (n_light + 1 prefix offsets); stack: traversal
-// stack entries per lane.
-struct LdsSizes { int n_node_f4, n_tri_f4, n_tri, n_mat, n_lt, n_light, stack; };
+// The sizes the layouts depend on.  width: children per node of the tree the kernel traverses in LDS (4:
+// the BVH4; 8: the BVH8 of prt_internal.h).  n_node_f4 counts the float4 of that tree's global nodes — 8
+// per BVH4 node, 14 per BVH8 node — and is a multiple of that (the collapse writes whole nodes): the LDS
+// copy holds 8 octant copies of 7 (14) float4 per node, 56 * (n_node_f4 / 8) or 112 * (n_node_f4 / 14)
+// float4, which node_copy_f4 writes as 7 * n_node_f4 or 8 * n_node_f4 — equal under that precondition only.
+// n_tri_f4: 3 float4 per triangle record in BVH order; n_mat: materials of 8 floats; n_lt: emitter
+// triangles of 4 float4; n_light: lights (n_light + 1 prefix offsets); stack: traversal stack entries per
+// lane.
+struct LdsSizes { int n_node_f4, n_tri_f4, n_tri, n_mat, n_lt, n_light, stack, width = 4; };
+PRT_HD constexpr int64_t node_copy_f4(const LdsSizes& z) { return (z.width == 8 ? 8 : 7) * (int64_t)z.n_node_f4; }
+// nodes of the tree (lds_fits: node indices fit the 16-bit stack entries)
+PRT_HD constexpr int64_t node_count(const LdsSizes& z) { return z.n_node_f4 / (z.width == 8 ? 14 : 8); }
 
 // float4 of a block's traversal stacks with 16-bit entries (LDS-resident scenes) ...
 PRT_HD constexpr int64_t stack16_f4(int stack) { return (int64_t)stack * kBlock * 2 / 16; }
@@ -43,7 +48,7 @@ PRT_HD constexpr TraceLds trace_lds(const LdsSizes& z) {
     TraceLds l{};
     l.stacks = 0;
     l.nodes = l.stacks + stack16_f4(z.stack);
-    l.tris = l.nodes + 7 * (int64_t)z.n_node_f4;
+    l.tris = l.nodes + node_copy_f4(z);
     l.normals = l.tris + z.n_tri_f4;                 // one float4 per triangle
     l.frames = l.normals + z.n_tri;                  // 2 x 3 float4 per triangle
     l.mats = l.frames + 6 * (int64_t)z.n_tri;
@@ -67,7 +72,7 @@ PRT_HD constexpr PoolLds pool_lds(const LdsSizes& z) {
     l.queue = l.pool + kPoolF4;
     l.ctl = l.queue + kQueueF4;
     l.nodes = l.ctl + kCtlF4;
-    l.tris = l.nodes + 7 * (int64_t)z.n_node_f4;
+    l.tris = l.nodes + node_copy_f4(z);
     l.light_v = l.tris + z.n_tri_f4;
     l.light_off = l.light_v + 4 * (int64_t)z.n_lt;
     l.mats = l.light_off + ((int64_t)z.n_light + 4) / 4;

@@ -189,7 +189,22 @@ constexpr int64_t kLdsSceneBytes = 24 * 1024;
 // (inner nodes < 0x7FFF, the sentinel; leaf refs >= -32768)
 bool lds_fits(const LdsSizes& z) {
     const int64_t n_refs = z.n_tri_f4 / 3;
-    return (int64_t)lds_scene_bytes(z) <= kLdsSceneBytes && z.n_node_f4 / 8 < 0x7FFF && n_refs * 8 <= 32768;
+    return (int64_t)lds_scene_bytes(z) <= kLdsSceneBytes && node_count(z) < 0x7FFF && n_refs * 8 <= 32768;
+}
+
+bool variant_takes_width(int var) { const Variant* v = find_variant(var); return v && v->lds && !v->mis; }
+
+// The eight-wide tree: Cornell's 7 BVH4 nodes become 3, a query makes 1.4 visits instead of 3.4, and a
+// visit costs two four-wide ones (C2 3.580 -> 3.385 ms per launch, C3 66.5 -> 63.1 ms against the BVH4
+// of the same scenes, images identical; DESIGN.md §2, profiles/r13/lds_bvh8/)
+constexpr int kLdsWidthDefault = 8;
+int lds_width(const LdsSizes& z8, int need8, int knob) {
+    const bool can8 = z8.width == 8 && z8.n_node_f4 > 0 && need8 >= 1 && need8 <= 32 && lds_fits(z8);
+    if (!can8 || knob == 4) return 4;
+    if (knob == 8) return 8;
+    LdsSizes own = z8;
+    own.stack = need8;
+    return pool_lds(own).bytes * 7 <= 160 * 1024 ? kLdsWidthDefault : 4;
 }
 
 // LDS-resident scene when it fits; the >= 7 (>= 6) waves/SIMD build when seven (six) blocks'

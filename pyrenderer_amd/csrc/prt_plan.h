@@ -80,6 +80,15 @@ size_t trace_smem_bytes(int stack, int var, const LdsSizes& z);
 // LDS-resident scene: the copy is small enough to sit beside the stacks, and node indices and leaf
 // references fit the LDS kernels' 16-bit stack entries
 bool lds_fits(const LdsSizes& z);
+// the variants that traverse the scene's wide tree of lds_width() children: the LDS-resident reference
+// kernels (pooled and phase-aligned); the MIS, global-scene, hit-query and feature kernels keep the BVH4
+bool variant_takes_width(int var);
+// The width rule: children per node of the tree the LDS-resident kernels traverse.  z8: the scene's sizes
+// with its BVH8 (width 8; n_node_f4 = 0: the scene has none), need8 that tree's worst-case stack entries,
+// knob PRT_LDS_WIDTH (4 or 8 force the width where the BVH8 can run at all; anything else: the default).
+// 8 needs a BVH8 whose stack fits the pooled kernel's 32 entries and whose copy is LDS-resident; the
+// default also asks that the pooled kernel's LDS still gives seven blocks per CU.
+int lds_width(const LdsSizes& z8, int need8, int knob);
 // the variant of a launch whose flags name none: need4 = the BVH4's worst-case stack entries (z.stack too),
 // stack4 = its LDS stack instantiation set (0: too deep for one)
 int choose_variant(const LdsSizes& z, int need4, int stack4, bool mis);

@@ -33,7 +33,7 @@ namespace {
 // LDS (per 256-thread block): the 16-bit traversal stacks (P.lds_stack entries), the pool (7
 // f32 arrays of 256: o.xyz, d.xyz, t_max; t_max carries the result back), the queue (256 u8),
 // two parity-alternating control words pairs (queue length, "alive"), then the scene copy:
-// octant BVH4 nodes, triangles, light triangles and offsets.  Shading data (normals, frames,
+// octant nodes of the BVH4 or BVH8 (BW), triangles, light triangles and offsets.  Shading data (normals, frames,
 // materials) are read from global memory (L1-resident) to keep seven blocks per CU.
 // (prt_lds_layout.h pool_lds: the regions' offsets, and kPoolF4, kQueueF4, kCtlF4)
 constexpr int kPoolSPrio = 2;                  // issue priority of the S-phase waves (s_setprio)
@@ -58,13 +58,14 @@ constexpr int kPoolSPrio = 2;                  // issue priority of the S-phase 
 // PLAIN: the lean build for scenes without spheres and metal / dielectric materials (P.plain; C1, C2,
 // C5): without that code the kernel's loop keeps 17 fewer uniform values in spilled SGPRs and is a
 // third shorter
-template <bool STATS, int WPE, bool PLAIN>
+// BW: children per node of the scene's LDS-resident tree (4: the BVH4; 8: the BVH8, visit_node8)
+template <bool STATS, int WPE, bool PLAIN, int BW>
 __global__ __attribute__((amdgpu_flat_work_group_size(kBlock, kBlock), amdgpu_waves_per_eu(WPE)))
 void trace_kernel_pool(TraceParams P) {
     extern __shared__ float4 smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const PoolLds lay = pool_lds(lds_sizes(P, P.lds_stack));   // prt_lds_layout.h
+    const PoolLds lay = pool_lds(lds_sizes(P, P.lds_stack, BW));   // prt_lds_layout.h
     LdsStack16A stk = LdsStack16A::at(smem, tid);
     using Stk = decltype(stk);
     float* pool = reinterpret_cast<float*>(smem + lay.pool);   // [7][256]
@@ -75,7 +76,7 @@ void trace_kernel_pool(TraceParams P) {
     float4* slv = smem + lay.light_v;
     int* slo = reinterpret_cast<int*>(smem + lay.light_off);
     float4* smt = smem + lay.mats;   // materials, after the light offsets
-    copy_octant_nodes(sn, P.nodes, P.n_node_f4 / 8);
+    copy_octant_tree<BW>(sn, P.nodes, P.n_node_f4);
     for (int i = tid; i < P.n_tri_f4; i += kBlock) st4[i] = P.tris[i];
     for (int i = tid; i < 4 * P.n_lt; i += kBlock) slv[i] = P.light_v[i];
     for (int i = tid; i <= P.n_light; i += kBlock) slo[i] = P.light_off[i];
@@ -223,7 +224,7 @@ void trace_kernel_pool(TraceParams P) {
                     tstate_init(ts, stk, kTMax);
                     if (STATS) { cn.ext++; cn.q0 = cn.nodes; }
                 }
-                done = traverse_ww4<STATS, 1, Stk, false, true, true>(
+                done = traverse_ww4<STATS, 1, Stk, false, true, true, BW>(
                     g_nodes, g_tris, o, d, kTMin, kTMax, false, stk, hid, ht, cn, &ts, exhausted ? 0 : Q.pool_resume_min + 1,
                     Q.fault, exhausted ? 0 : Q.leaf_break, exhausted ? 0 : Q.leaf_exit, Q.guard_trips);
                 hit = done && hid >= 0;
@@ -432,7 +433,7 @@ void trace_kernel_pool(TraceParams P) {
                 int hid = -1;
                 float ht = 0.0f;
                 if (STATS) cn.q0 = cn.nodes;
-                bool hit = traverse_ww4<STATS, 2, Stk, false, false, true>(
+                bool hit = traverse_ww4<STATS, 2, Stk, false, false, true, BW>(
                     g_nodes, g_tris, so, sd, kTMin, stm, true, stk, hid, ht, cn, nullptr, 0, Q.fault,
                     exhausted ? 0 : Q.leaf_break, exhausted ? 0 : Q.leaf_exit, Q.guard_trips);
                 if (STATS) { cn.max_q = max(cn.max_q, cn.nodes - cn.q0); book_trav(4); }

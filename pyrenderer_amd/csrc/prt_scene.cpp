@@ -31,33 +31,45 @@ void destroy_scene(Scene* s) {
     delete s;
 }
 
-// the scene's sizes alone (all that the LDS footprints and the variant choice depend on, prt_plan.h), with
-// the pooled kernel's stack
-LdsSizes scene_sizes(const Scene* s) {
-    return LdsSizes{(int)s->n_node4_f4, (int)s->n_tri_f4, (int)s->n_tri, s->n_mat, s->n_lt, s->n_light, s->need4};
+// the scene's sizes alone (all that the LDS footprints and the variant choice depend on, prt_plan.h) with
+// the tree of `width` children per node, and the pooled kernel's stack for it
+LdsSizes sizes_of(const Scene* s, int width) {
+    const bool w8 = width == 8;
+    return LdsSizes{(int)(w8 ? s->n_node8_f4 : s->n_node4_f4), (int)s->n_tri_f4, (int)s->n_tri, s->n_mat, s->n_lt,
+                    s->n_light, w8 ? s->need8 : s->need4, w8 ? 8 : 4};
 }
 
 }  // namespace
 
-bool lds_fits4(const Scene* s) { return lds_fits(scene_sizes(s)); }
+int variant_width(const Scene* s, int var) { return variant_takes_width(var) ? s->lds_width : 4; }
+int variant_need(const Scene* s, int var) { return variant_width(s, var) == 8 ? s->need8 : s->need4; }
+LdsSizes scene_sizes(const Scene* s, int var) { return sizes_of(s, variant_width(s, var)); }
+
+bool lds_fits4(const Scene* s, int var) { return lds_fits(scene_sizes(s, var)); }
 
 // the traversal stack entries of variant `var` (LDS part for the spill variants; the pool kernel's
 // instantiation set, its LDS stack being the launch parameter P.lds_stack)
 int variant_stack(const Scene* s, int var) {
-    return variant_pool(var) ? 16 : variant_spills(var) ? s->spill_lds : s->stack4;
+    return variant_pool(var) ? 16 : variant_spills(var) ? s->spill_lds : variant_width(s, var) == 8 ? s->stack8 : s->stack4;
 }
 
-// the variant a launch takes: the one the flags name, else the scene's default
+// the variant a launch takes: the one the flags name, else the scene's default (the reference estimator's
+// from the sizes of the tree its LDS kernels traverse, the MIS estimator's from the BVH4's)
 int launch_variant(const Scene* s, uint32_t flags) {
     const int var = (int)((flags >> PRT_FLAG_VARIANT_SHIFT) & 0xFFu);
-    return var ? var : choose_variant(scene_sizes(s), s->need4, s->stack4, (flags & PRT_FLAG_MIS_NEE) != 0);
+    if (var) return var;
+    if (flags & PRT_FLAG_MIS_NEE) return choose_variant(sizes_of(s, 4), s->need4, s->stack4, true);
+    const bool w8 = s->lds_width == 8;
+    return choose_variant(sizes_of(s, s->lds_width), w8 ? s->need8 : s->need4, w8 ? s->stack8 : s->stack4, false);
 }
 
 // blocks per CU of variant `var`'s persistent grid (>= 1), queried once per (variant, stats)
 int variant_occ(Scene* s, int var, bool stats) {
     int& occ = s->occ[2 * var + (stats ? 1 : 0)];
     const int stack = variant_stack(s, var);
-    if (occ == 0) occ = std::max(1, trace_blocks_per_cu(stack, var, stats, trace_smem_bytes(stack, var, scene_sizes(s))));
+    if (occ == 0)
+        occ = std::max(1, trace_blocks_per_cu(stack, var, stats, variant_width(s, var),
+                                              trace_smem_bytes(stack, var, scene_sizes(s, var))));
     return occ;
 }
 
@@ -77,6 +89,7 @@ void scene_params(Scene* s, TraceParams& P) {
     P.n_sph = (int)s->n_sph; P.sph = (const float4*)s->sph.p; P.sph_mat = (const int*)s->sph_mat.p;
     P.plain = s->plain ? 1 : 0; P.shade_fast = s->shade_fast ? 1 : 0;
     P.frame_spp = 0xFFFFFFFFu;   // one frame: global sample = s0 + j0 + the chunk's sample
+    P.lds_width = 4;             // the BVH4; trace_setup switches the LDS reference kernels to the scene's width
 }
 
 namespace {
@@ -99,6 +112,18 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
         if (int rc = upload(s->nodes4q, q4.data(), sizeof(float) * q4.size(), total)) return rc;
     }
     s->n_lt = pk.n_lt;
+    s->n_tri_f4 = (int64_t)bvh.tris.size() / 4;
+    // LDS-resident scenes also get the eight-wide tree; the width rule (prt_plan.h lds_width) says which of
+    // the two their LDS reference kernels traverse
+    if (lds_fits(sizes_of(s, 4))) {
+        Bvh8Host b8;
+        collapse_bvh8(bvh, &b8);
+        s->n_node8_f4 = (int64_t)b8.nodes.size() / 4;
+        s->need8 = b8.stack_need;
+        s->stack8 = b8.stack_need <= 32 ? stack_variant(b8.stack_need - 1) : 0;
+        if (int rc = upload(s->nodes8, b8.nodes.data(), sizeof(float) * b8.nodes.size(), total)) return rc;
+        s->lds_width = lds_width(sizes_of(s, 8), s->need8, (int)env_int("PRT_LDS_WIDTH", 0, 8, 0));
+    }
     s->n_sph = a.n_sph;
     s->plain = pk.plain;
     s->shade_fast = pk.shade_fast;
@@ -117,7 +142,6 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
     hipDeviceProp_t prop;
     if ((e = hipGetDeviceProperties(&prop, s->device)) != hipSuccess) return fail(PRT_ERR_HIP, hipGetErrorString(e));
     s->cus = prop.multiProcessorCount;
-    s->n_tri_f4 = (int64_t)bvh.tris.size() / 4;
     s->leaf_exit = (int)env_int("PRT_LEAF_EXIT", 0, 64, s->leaf_exit);
     s->leaf_break = (int)env_int("PRT_LEAF_BREAK", 0, 64, s->leaf_break);
     if (const char* wc = std::getenv("PRT_WAVE_CLOCK")) s->wave_clock_path = wc;
@@ -192,6 +216,27 @@ int prt_bvh_export(void* bvh, float* nodes, float* tris, int32_t* order) {
     return PRT_OK;
 }
 
+int prt_bvh_collapse(void* bvh, int32_t width, int64_t* info4, float* nodes) {
+    auto* b = (BvhHost*)bvh;
+    if (!b || !info4) return fail(PRT_ERR_ARG, "NULL argument");
+    if (width != 4 && width != 8) return fail(PRT_ERR_ARG, "width must be 4 or 8");
+    try {
+        Bvh4Host b4;
+        Bvh8Host b8;
+        if (width == 4) collapse_bvh4(*b, &b4);
+        else collapse_bvh8(*b, &b8);
+        const std::vector<float>& f = width == 4 ? b4.nodes : b8.nodes;
+        info4[0] = width == 4 ? b4.n_nodes : b8.n_nodes;
+        info4[1] = width == 4 ? b4.depth : b8.depth;
+        info4[2] = width == 4 ? b4.stack_need : b8.stack_need;
+        info4[3] = 4 * (width == 4 ? kNode4F4 : kNode8F4);
+        if (nodes) std::memcpy(nodes, f.data(), sizeof(float) * f.size());
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_ERR_OOM, "host allocation failed during the collapse");
+    }
+    return PRT_OK;
+}
+
 void prt_bvh_destroy(void* bvh) { delete (BvhHost*)bvh; }
 
 int prt_scene_create(int device, const float* tri_v, const float* tri_n, const int32_t* tri_mat, int64_t n_tri,
@@ -249,10 +294,10 @@ int prt_launch_kernel(void* scene, int64_t n_items, uint32_t flags, int32_t* out
     if (n_items < 0) return fail(PRT_ERR_ARG, "n_items < 0");
     int var = launch_variant(s, flags);
     out4[0] = var;
-    out4[1] = 4;
+    out4[1] = variant_width(s, var);
     out4[2] = (variant_uses_lds(var) ? 1 : 0) | (variant_quantized(var) ? 2 : 0);
-    // the pooled kernel's LDS stack is sized to the BVH4's exact bound (P.lds_stack = need4)
-    out4[3] = variant_pool(var) ? s->need4 : variant_stack(s, var);
+    // the pooled kernel's LDS stack is sized to its tree's exact bound (P.lds_stack)
+    out4[3] = variant_pool(var) ? variant_need(s, var) : variant_stack(s, var);
     return PRT_OK;
 }
 

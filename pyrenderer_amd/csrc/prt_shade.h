@@ -381,5 +381,70 @@ __device__ __forceinline__ void copy_octant_nodes(float4* __restrict__ sn, const
     }
 }
 
+// The same for an LDS-resident scene's BVH8 (prt_internal.h Bvh8Host; visit_node8): copy k of node n is
+// 14 float4 — the near / far planes of each axis for children 0-3 of k's front-to-back order, the same six
+// for children 4-7, then the eight refs as two quads; node stride 112 float4.  The order is
+// copy_octant_nodes' (ascending near corner along the octant's diagonal, empty slots last, ties by index).
+__device__ __forceinline__ void copy_octant_nodes8(float4* __restrict__ sn, const float4* __restrict__ nodes,
+                                                   int n_node8) {
+    for (int i = threadIdx.x; i < 112 * n_node8; i += kBlock) {
+        const int n = i / 112, r = i - 112 * n, k = r / 14, slot = r - 14 * k;
+        const float4* src = nodes + 14 * n;
+        const bool refs = slot >= 12;
+        const int g = refs ? slot - 12 : slot / 6;        // the group of four output children
+        // plane slots: the source plane of axis ax, near or far for the octant's sign (refs: unused, 0)
+        const int s6 = refs ? 0 : slot - 6 * g, ax = s6 >> 1, sgn = (k >> ax) & 1, far = s6 & 1;
+        const int plane = 2 * ax + (sgn ^ far);
+        const float4 va = refs ? src[12] : src[plane], vb = refs ? src[13] : src[6 + plane];
+        float vin[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
+        const float4 ra = src[12], rb = src[13];
+        const int rr[8] = {__float_as_int(ra.x), __float_as_int(ra.y), __float_as_int(ra.z), __float_as_int(ra.w),
+                           __float_as_int(rb.x), __float_as_int(rb.y), __float_as_int(rb.z), __float_as_int(rb.w)};
+        if (refs) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) vin[c] = rr[c] == kSentinel ? __int_as_float(kSentinel16) : vin[c];
+        }
+        // near corner of each box, projected on the octant's diagonal
+        float key[8];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const float4* q = src + 6 * h;
+            const float4 cx = (k & 1) ? q[1] : q[0], cy = (k & 2) ? q[3] : q[2], cz = (k & 4) ? q[5] : q[4];
+            const float xs[4] = {cx.x, cx.y, cx.z, cx.w}, ys[4] = {cy.x, cy.y, cy.z, cy.w};
+            const float zs[4] = {cz.x, cz.y, cz.z, cz.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float v = ((k & 1) ? -xs[c] : xs[c]) + ((k & 2) ? -ys[c] : ys[c]) + ((k & 4) ? -zs[c] : zs[c]);
+                if (rr[4 * h + c] == kSentinel || !(v == v)) v = INFINITY;   // NaN (degenerate box): a total order
+                key[4 * h + c] = v;
+            }
+        }
+        int rank[8];   // position of child c in the order (a permutation of 0..7)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            rank[c] = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) rank[c] += (key[e] < key[c] || (key[e] == key[c] && e < c)) ? 1 : 0;
+        }
+        // output child j of the group takes the child of rank 4 g + j (selects, no indexed array in scratch)
+        float vout[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float v = vin[7];
+#pragma unroll
+            for (int c = 6; c >= 0; --c) v = rank[c] == 4 * g + j ? vin[c] : v;
+            vout[j] = v;
+        }
+        sn[i] = make_float4(vout[0], vout[1], vout[2], vout[3]);
+    }
+}
+// the block's octant copy of the tree of W children per node
+template <int W>
+__device__ __forceinline__ void copy_octant_tree(float4* __restrict__ sn, const float4* __restrict__ nodes,
+                                                 int n_node_f4) {
+    if constexpr (W == 8) copy_octant_nodes8(sn, nodes, n_node_f4 / 14);
+    else copy_octant_nodes(sn, nodes, n_node_f4 / 8);
+}
+
 }  // namespace
 }  // namespace prt

@@ -44,12 +44,15 @@ __device__ __forceinline__ float area_light_pdf(float t_light, V3 dir, V3 light_
 //              LDS entries plus a global spill area, and traversal tails are suspended and resumed in
 //              the next iteration.
 //   MIS        MIS direct lighting (sample_direct_lighting2) instead of NEE.
-template <int STACK, bool STATS, bool SCENE_LDS, bool MIS, int WPE>
+//   BW         children per node of the LDS-resident tree of the phase-aligned kernels (4, or 8: the BVH8);
+//              the MIS and global-scene kernels exist for 4 only.
+template <int STACK, bool STATS, bool SCENE_LDS, bool MIS, int WPE, int BW>
 __global__ __attribute__((amdgpu_flat_work_group_size(kBlock, kBlock), amdgpu_waves_per_eu(WPE)))
 void trace_kernel(TraceParams P) {
     // phase-aligned scheduling (see below): the LDS scenes' NEE kernels; the MIS estimator's three query
     // kinds and the global scenes' suspended queries keep the mixed schedule
     constexpr bool PHASE = SCENE_LDS && !MIS;
+    static_assert(BW == 4 || (BW == 8 && PHASE), "only the phase-aligned LDS kernels traverse the eight-wide tree");
     extern __shared__ float4 smem[];
     // LDS: the traversal stacks (16-bit entries for LDS-resident scenes), then the scene copy
     using StackT = typename std::conditional<SCENE_LDS, LdsStack16A, SpillStack<STACK>>::type;
@@ -71,7 +74,7 @@ void trace_kernel(TraceParams P) {
     if (SCENE_LDS) {
         // small scene: copy BVH + triangles, and the shading data (normals, frames,
         // materials, emitters), into LDS once per persistent block (layout: prt_lds_layout.h)
-        const TraceLds lay = trace_lds(lds_sizes(P, STACK));
+        const TraceLds lay = trace_lds(lds_sizes(P, STACK, BW));
         float4* sn = smem + lay.nodes;
         float4* st4 = smem + lay.tris;
         float4* snm = smem + lay.normals;
@@ -79,7 +82,7 @@ void trace_kernel(TraceParams P) {
         float4* smt = smem + lay.mats;
         float4* slv = smem + lay.light_v;
         int* slo = reinterpret_cast<int*>(smem + lay.light_off);
-        copy_octant_nodes(sn, P.nodes, P.n_node_f4 / 8);
+        copy_octant_tree<BW>(sn, P.nodes, P.n_node_f4);
         for (int i = threadIdx.x; i < P.n_tri_f4; i += kBlock) st4[i] = P.tris[i];
         for (int i = threadIdx.x; i < P.n_tri; i += kBlock) snm[i] = P.tri_nm[i];
         for (int i = threadIdx.x; i < 6 * P.n_tri; i += kBlock) sfr[i] = P.tri_frame[i];
@@ -249,10 +252,10 @@ void trace_kernel(TraceParams P) {
             hit = hid >= 0;
         } else if (PHASE) {
             if (do_shadow)
-                hit = traverse_ww4<STATS, 2, StackT, false, false, true>(g_nodes, g_tris, o, d, kTMin, tmax, true, stk,
+                hit = traverse_ww4<STATS, 2, StackT, false, false, true, BW>(g_nodes, g_tris, o, d, kTMin, tmax, true, stk,
                                                                          hid, ht, cn, nullptr, 0, Q.fault, lb, le, glim);
             else
-                hit = traverse_ww4<STATS, 1, StackT, false, false, true>(g_nodes, g_tris, o, d, kTMin, tmax, false, stk,
+                hit = traverse_ww4<STATS, 1, StackT, false, false, true, BW>(g_nodes, g_tris, o, d, kTMin, tmax, false, stk,
                                                                          hid, ht, cn, nullptr, 0, Q.fault, lb, le, glim);
         } else {
             // LDS scene, MIS: the mixed schedule (closest-hit queries of three kinds)

@@ -23,8 +23,8 @@ hipError_t PRT_CAT(launch_trace_, PRT_STACK, PRT_STATS)(const TraceParams& P, in
     return launch_var<PRT_STACK, PRT_STATS != 0>(P, var, grid, smem, stream);
 }
 
-int PRT_CAT(trace_occ_, PRT_STACK, PRT_STATS)(int var, size_t smem) {
-    return occ_var<PRT_STACK, PRT_STATS != 0>(var, smem);
+int PRT_CAT(trace_occ_, PRT_STACK, PRT_STATS)(int var, int width, size_t smem) {
+    return occ_var<PRT_STACK, PRT_STATS != 0>(var, width, smem);
 }
 
 }  // namespace prt

@@ -1,5 +1,6 @@
 #pragma once
-// prt_traverse.h — the per-lane traversal stacks and the while-while BVH4 traversal (traverse_ww4).
+// prt_traverse.h — the per-lane traversal stacks and the while-while traversal (traverse_ww4) of the BVH4
+// in its three forms and of the LDS-resident scenes' BVH8.
 #pragma clang fp contract(off)
 
 #include "prt_math.h"
@@ -347,10 +348,65 @@ __device__ __forceinline__ void visit_node4(const float4* __restrict__ nodes, in
     else step(stk);
 }
 
+// One inner-node visit of the eight-wide tree of an LDS-resident scene (prt_internal.h Bvh8Host; OCT
+// only, MODE 1 or 2).  `nodes` is the block's octant copy (copy_octant_nodes8): copy k of a node is 14
+// float4 — nx, fx, ny, fy, nz, fz of children 0-3, the same six of children 4-7, two ref quads — with the
+// eight children in k's front-to-back order; node stride 112 float4, `sx` = the query's copy offset 14 k.
+// The visit tests one group of four at a time: the first group's planes are dead before the second's are
+// needed, so only the eight refs and the eight hit masks (lane masks) span it.
+// Closest-hit (MODE 1): continues with the first hit child in stored order and pushes the other hit ones
+// r7 .. r1, so that they pop front to back; any-hit (MODE 2): pushes r0 .. r6 by their hit flags and
+// continues with r7 if hit, else pops (back to front), both as visit_node4 does over its octant copies.
+// Pushes are unconditional writes above the top (<= 7 above the entry top, Bvh8Host::stack_need).
+template <bool STATS, int MODE, class S>
+__device__ __forceinline__ void visit_node8(const float4* __restrict__ nodes, int& cur, int& sp, S stk, V3 inv, V3 oi,
+                                            int sx, float tmin, float best, Counters& cn) {
+    static_assert(MODE == 1 || MODE == 2, "the eight-wide visit has no mixed-kind form");
+    const LdsF4* nl = as_lds(nodes) + (int)(__umul24((uint32_t)cur, 112u) + (uint32_t)sx);
+    if (STATS) { cn.nodes++; cn.it_inner++; }
+    bool h[8];
+    float tn;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const float4 nx = lds4(nl, 6 * g), fx = lds4(nl, 6 * g + 1), ny = lds4(nl, 6 * g + 2);
+        const float4 fy = lds4(nl, 6 * g + 3), nz = lds4(nl, 6 * g + 4), fz = lds4(nl, 6 * g + 5);
+        h[4 * g] = slab_nf(nx.x, fx.x, ny.x, fy.x, nz.x, fz.x, oi, inv, tmin, best, tn);
+        h[4 * g + 1] = slab_nf(nx.y, fx.y, ny.y, fy.y, nz.y, fz.y, oi, inv, tmin, best, tn);
+        h[4 * g + 2] = slab_nf(nx.z, fx.z, ny.z, fy.z, nz.z, fz.z, oi, inv, tmin, best, tn);
+        h[4 * g + 3] = slab_nf(nx.w, fx.w, ny.w, fy.w, nz.w, fz.w, oi, inv, tmin, best, tn);
+    }
+    const float4 ra = lds4(nl, 12), rb = lds4(nl, 13);
+    const int r[8] = {__float_as_int(ra.x), __float_as_int(ra.y), __float_as_int(ra.z), __float_as_int(ra.w),
+                      __float_as_int(rb.x), __float_as_int(rb.y), __float_as_int(rb.z), __float_as_int(rb.w)};
+    if (MODE == 2) {
+#pragma unroll
+        for (int k = 0; k < 7; ++k) { stk.put(sp + S::kStep, r[k]); sp = stack_adv<S>(sp, h[k]); }
+        const int top = stk.get(sp);
+        cur = h[7] ? r[7] : top;
+        sp -= h[7] ? 0 : S::kStep;
+    } else {
+        // e[k]: some child before k is hit, i.e. k is not the one the visit continues with
+        bool e[8];
+        e[0] = false;
+#pragma unroll
+        for (int k = 1; k < 8; ++k) e[k] = e[k - 1] | h[k - 1];
+#pragma unroll
+        for (int k = 7; k >= 1; --k) { stk.put(sp + S::kStep, r[k]); sp = stack_adv<S>(sp, h[k] & e[k]); }
+        int nxt = stk.get(sp);
+#pragma unroll
+        for (int k = 7; k >= 0; --k) nxt = h[k] ? r[k] : nxt;
+        cur = nxt;
+        sp -= (e[7] | h[7]) ? 0 : S::kStep;
+    }
+}
+
 // MODE 0: per-lane query kind (`any` may differ between lanes); 1: every lane
 // closest-hit; 2: every lane any-hit (phase-aligned shadow iterations).  Any-hit
 // queries need no visiting order, so mode 2 skips the sorting network (visit_node4).
-template <bool STATS, int MODE, class S, bool QN = false, bool RES = false, bool OCT = false>
+// W: children per node of the tree at `nodes`: 4 (the BVH4 in every form), or 8 (OCT only: the block's
+// octant copy of an LDS-resident scene's BVH8, visit_node8).  Leaves, the suspended state and the
+// watchdog are the same for both.
+template <bool STATS, int MODE, class S, bool QN = false, bool RES = false, bool OCT = false, int W = 4>
 __device__ __forceinline__ bool traverse_ww4(const float4* __restrict__ nodes, const float4* __restrict__ tris, V3 o,
                                              V3 d, float tmin, float tmax, bool any_lane, S stk, int& hit_id,
                                              float& hit_t, Counters& cn, TState* tsp = nullptr, int min_lanes = 0,
@@ -362,7 +418,8 @@ __device__ __forceinline__ bool traverse_ww4(const float4* __restrict__ nodes, c
     // near plane index per axis (0 = lo, 1 = hi) from the sign of 1/d
     int sx = __float_as_int(inv.x) < 0 ? 1 : 0, sy = __float_as_int(inv.y) < 0 ? 1 : 0,
         sz = __float_as_int(inv.z) < 0 ? 1 : 0;
-    if (OCT) sx = 7 * (sx | (sy << 1) | (sz << 2));   // octant copy offset (visit_node4)
+    static_assert(W == 4 || (W == 8 && OCT && !QN), "the eight-wide tree exists as LDS octant copies only");
+    if (OCT) sx = (W == 8 ? 14 : 7) * (sx | (sy << 1) | (sz << 2));   // octant copy offset (visit_node4 / 8)
     TState ts;
     if (RES) ts = *tsp;
     else tstate_init(ts, stk, tmax);
@@ -374,7 +431,8 @@ __device__ __forceinline__ bool traverse_ww4(const float4* __restrict__ nodes, c
     int leaf = ts.leaf;
     do {
         while (cur >= 0 && cur != S::kSent) {
-            visit_node4<STATS, MODE, S, QN, OCT>(nodes, cur, sp, stk, inv, oi, sx, sy, sz, tmin, best, cn, any);
+            if constexpr (W == 8) visit_node8<STATS, MODE, S>(nodes, cur, sp, stk, inv, oi, sx, tmin, best, cn);
+            else visit_node4<STATS, MODE, S, QN, OCT>(nodes, cur, sp, stk, inv, oi, sx, sy, sz, tmin, best, cn, any);
             if (STATS) wave_tick(cn.wi, cn.li);
             if (STATS) cn.max_sp = max(cn.max_sp, (uint32_t)(stk.depth(sp) + 1));
             if (cur < 0 && leaf >= 0) {   // postpone the leaf, keep descending

@@ -6,7 +6,9 @@
 namespace prt {
 
 // trace kernel variants (selectable at run time through PRT_FLAG_VARIANT).  All run the
-// while-while BVH4 traversal (prt_traverse.h traverse_ww4) and give bit-identical images;
+// while-while traversal (prt_traverse.h traverse_ww4) over the BVH4 — the LDS-resident reference
+// kernels (1, 2, 6, 7, 8) over the scene's BVH8 instead where the width rule says so (prt_plan.h
+// lds_width; one instantiation per width, no variant id of its own) — and give bit-identical images;
 // the measured history of the variants this set replaced is in DESIGN.md §2.
 constexpr int kVarLds = 1;         // LDS-resident scene, phase-aligned ext/shadow iterations, >= 7 waves/SIMD
                                    // (72 VGPRs: C2 4.40 -> 4.23 ms against the 6-wave build)

@@ -39,7 +39,13 @@ static hipError_t launch_var(const TraceParams& P, int var, int grid, size_t sme
         if constexpr (v.pool) {
             e = launch_trace_pool(P, STATS, v.wpe, grid, smem, stream);
         } else {
-            trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe><<<grid, kBlock, smem, stream>>>(P);
+            // the LDS reference kernels exist per tree width (prt_plan.h variant_takes_width)
+            if constexpr (v.lds && !v.mis) {
+                if (P.lds_width == 8) trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 8><<<grid, kBlock, smem, stream>>>(P);
+                else trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 4><<<grid, kBlock, smem, stream>>>(P);
+            } else {
+                trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 4><<<grid, kBlock, smem, stream>>>(P);
+            }
             e = hipGetLastError();
         }
     });
@@ -47,15 +53,23 @@ static hipError_t launch_var(const TraceParams& P, int var, int grid, size_t sme
 }
 
 template <int STACK, bool STATS>
-static int occ_var(int var, size_t smem) {
+static int occ_var(int var, int width, size_t smem) {
     int n = 0;
     with_variant<STACK>(var, [&](auto row) {
         constexpr Variant v = kVariants[decltype(row)::value];
-        if constexpr (v.pool)
-            n = trace_occ_pool(STATS, v.wpe, smem);
-        else
-            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe>,
+        if constexpr (v.pool) {
+            n = trace_occ_pool(STATS, v.wpe, width, smem);
+        } else if constexpr (v.lds && !v.mis) {
+            if (width == 8)
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &n, trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 8>, kBlock, smem);
+            else
+                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &n, trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 4>, kBlock, smem);
+        } else {
+            (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, trace_kernel<STACK, STATS, v.lds, v.mis, v.wpe, 4>,
                                                                kBlock, smem);
+        }
     });
     return n;
 }

@@ -16,7 +16,12 @@ of the same rays, and VALU per 64 queries with the iteration overhead priced per
 The greedy collapse stands in for the build's SAH-optimal one (3.44 vs 3.17 node visits per query); at
 npost 2 the lane fractions match the GPU lane table (0.463 / 0.269 against 0.444 / 0.294).
 
-    python tools/bvh4_sim.py [--persistent [--blocks 8] [--queries 2560]]
+--width 8 (round 13, profiles/r13/lds_bvh8/): the same over the eight-wide tree of LDS-resident scenes (the
+greedy collapse opened to 8 children, the octant orders over 8), a visit priced at the eight-wide visit's VALU
+count (161 against 79 in the extension loop of the pooled kernel's listing; the shadow loop's 129 against 69
+is not priced apart).  --le sweeps the leaf-phase exit of the plain table at npost 2, lb 0.
+
+    python tools/bvh4_sim.py [--width {4,8}] [--le 8 16] [--persistent [--blocks 8] [--queries 2560]]
 """
 import numpy as np, sys, time
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
@@ -27,7 +32,11 @@ from pyrenderer_amd.flatten import flatten_scene
 from pyrenderer_amd._native import Bvh
 SENT = 1 << 30
 
-def load(max_leaf=4):
+V_NODE_BY_WIDTH = {4: 79, 8: 161}   # VALU per node visit (E loop of the pooled kernel's listing: 77 and 159 in the visit's block, 2 around it)
+V_TRI = 73
+V_ITER_W4 = 539   # --persistent: VALU per wave iteration outside the traversals, as width 4's threshold-0 row calibrates it
+
+def load(max_leaf=4, width=4):
     scene, cam = read_file(scenes.CORNELL)
     flat = flatten_scene(scene)
     nodes, tris, _ = Bvh(flat.tri_v, max_leaf=max_leaf).export()
@@ -37,11 +46,11 @@ def load(max_leaf=4):
         return (np.array([f[0], f[2], f[4]]), np.array([f[1], f[3], f[5]]), int(refs[n, s]))
     def area(c):
         d = c[1] - c[0]; return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0])
-    # greedy BVH4 collapse
+    # greedy collapse to `width` children
     n4 = []          # list of children lists
     def make(n2):
         ch = [child(n2, 0), child(n2, 1)]
-        while len(ch) < 4:
+        while len(ch) < width:
             inner = [i for i, c in enumerate(ch) if c[2] >= 0]
             if not inner: break
             i = max(inner, key=lambda i: area(ch[i]))
@@ -222,7 +231,7 @@ class Sim:
 
 def persistent(args):
     """The --persistent table (see the module docstring)."""
-    flat, cam, n4, orders, T = load()
+    flat, cam, n4, orders, T = load(width=args.width)
     sim = Sim(n4, orders, T)
     rng = np.random.default_rng(0)
     O_, D_, B = bounce_rays(flat, cam, 20000, rng)
@@ -248,8 +257,9 @@ def persistent(args):
     # VALU per trip from the pooled kernel's ISA; the rest of an iteration (shading, S claim, resolve, refill,
     # loop control) is priced per wave iteration, calibrated on the threshold-0 row so that E : (S + rest) is
     # the profiled 102 : 96 wave-level VALU per sample
-    V_NODE, V_TRI = 79, 73
-    print(f"persistent model: {args.blocks} blocks x {args.queries} queries, 4 waves, npost 2 lb 0 le 8")
+    V_NODE = V_NODE_BY_WIDTH[args.width]
+    print(f"persistent model: width {args.width} ({len(n4)} nodes, {V_NODE} VALU per visit), {args.blocks} blocks x "
+          f"{args.queries} queries, 4 waves, npost 2 lb 0 le {args.le[0]}")
     print("thr | E node trips/64q (lanes) | E tri trips/64q (lanes) | iter/64q | shade share | susp/query | "
           "S node+tri trips/64q free-lane (lanes n, t) | same rays in 64-chunks | VALU/64q E, S, iter, total")
     rows = []
@@ -257,13 +267,16 @@ def persistent(args):
         tot = None
         for b in range(args.blocks):
             queue = [(O_[i], D_[i], 99999.9, False) for i in perm[b * args.queries:(b + 1) * args.queries]]
-            r = sim.block(queue, thr, shadow)
+            r = sim.block(queue, thr, shadow, le=args.le[0])
             if tot is None: tot = r
             else:
                 for k, v in r.items(): tot[k] = tot[k] + v
         rows.append((thr, tot))
         print(f"# threshold {thr} done", file=sys.stderr, flush=True)
-    v_iter = None
+    # width 8 takes the rest of an iteration as calibrated at width 4 (the profiled ratio is that build's)
+    v_iter = None if args.width == 4 else V_ITER_W4
+    if v_iter is not None:
+        print(f"rest of an iteration: {v_iter:.0f} VALU per wave iteration (the width-4 calibration)")
     for thr, tot in rows:
         w = tot['queries'] / 64.0
         E, Sf, Sc = tot['E'], tot['S_free'], tot['S_chunk']
@@ -286,12 +299,19 @@ if __name__ == "__main__":
     ap.add_argument("--blocks", type=int, default=8)
     ap.add_argument("--queries", type=int, default=2560, help="extension queries per block")
     ap.add_argument("--thresholds", type=int, nargs="+", default=[0, 7, 11, 15, 23, 31])
+    ap.add_argument("--width", type=int, choices=(4, 8), default=4, help="children per node of the collapsed tree")
+    ap.add_argument("--le", type=int, nargs="+", default=None,
+                    help="leaf-phase exit thresholds: the plain table's sweep at npost 2, lb 0 (instead of its "
+                         "full grid); --persistent takes the first (default 8)")
     args = ap.parse_args()
+    sweep = args.le
+    args.le = args.le or [8]
     if args.persistent:
         persistent(args)
         sys.exit(0)
-    flat, cam, n4, orders, T = load()
-    print("BVH4 nodes", len(n4))
+    flat, cam, n4, orders, T = load(width=args.width)
+    V_NODE = V_NODE_BY_WIDTH[args.width]
+    print(f"BVH{args.width} nodes", len(n4), "| VALU per visit", V_NODE)
     sim = Sim(n4, orders, T)
     rng = np.random.default_rng(0)
     O_, D_, B = bounce_rays(flat, cam, 20000, rng)
@@ -304,9 +324,13 @@ if __name__ == "__main__":
             wi, li, wl, ll, rr = wi + r[0], li + r[1], wl + r[2], ll + r[3], rr + r[4]
         nq = len(perm)
         pk = kw.get("packed", False)
-        cost = (wi * 79 + wl * (73 + (X if pk else 0)) + (rr * Y if pk else 0)) / (nq / 64)
+        cost = (wi * V_NODE + wl * (V_TRI + (X if pk else 0)) + (rr * Y if pk else 0)) / (nq / 64)
         print(f"{label:28s} inner trips/wave {wi/(nq/64):.2f} lanes {li/(64*wi):.3f} | tri trips/wave {wl/(nq/64):.2f} lanes {ll/(64*wl):.3f} | visits/ray {li/nq:.2f} tests/ray {ll/nq:.2f} | VALU/wave {cost:.0f}", flush=True)
     print("---")
+    if sweep:
+        for le in sweep:
+            run(f"npost 2 lb0 le{le}", npost=2, lb=0, le=le)
+        sys.exit(0)
     for npost in (2, 3, 4):
         for lb, le in ((0, 8), (4, 8), (8, 8), (0, 16), (8, 16)):
             run(f"npost {npost} lb{lb} le{le}", npost=npost, lb=lb, le=le)

@@ -31,6 +31,9 @@ def main():
     csrc = os.path.join(a.src, "pyrenderer_amd", "csrc")
     units = [(f"trace_{s}_{t}", B.TRACE_INST, [f"-DPRT_STACK={s}", f"-DPRT_STATS={t}"]) for s, t in B.TRACE_SETS]
     units += [(os.path.splitext(f)[0], f, B.UNIT_FLAGS.get(f, [])) for f in ("prt_trace_pool.hip", "prt_kernels.hip")]
+    # the pooled kernel's units for the wider trees (a parent tree without them has no POOL_WIDE)
+    units += [(f"prt_trace_pool{w}", B.POOL_UNIT, B.UNIT_FLAGS[B.POOL_UNIT] + [f"-DPRT_POOL_WIDTH={w}"])
+              for w, _ in getattr(B, "POOL_WIDE", []) if a.src == ROOT]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
     def compile_unit(u):

@@ -93,12 +93,14 @@ def _to_world(local, axis):
     return out
 
 
-def _lattice_local():
+def _lattice_local(cells=8):
+    """cells x cells cells over [-1, 1]^2, two triangles each, then the light's two."""
+    w = 2.0 / cells
     tris = []
-    for j in range(8):
-        for i in range(8):
-            u0, v0 = -1 + 0.25 * i, -1 + 0.25 * j
-            u1, v1 = u0 + 0.25, v0 + 0.25
+    for j in range(cells):
+        for i in range(cells):
+            u0, v0 = -1 + w * i, -1 + w * j
+            u1, v1 = u0 + w, v0 + w
             tris.append([[u0, v0, 0], [u1, v0, 0], [u1, v1, 0]])
             tris.append([[u0, v0, 0], [u1, v1, 0], [u0, v1, 0]])
     tris.append([[-0.5, -0.5, 2], [0.5, 0.5, 2], [0.5, -0.5, 2]])     # the light, facing the lattice
@@ -125,7 +127,13 @@ def lattice(axis):
     g = -1 + 0.125 * np.arange(17)
     uu, vv = np.meshgrid(g, g, indexing="ij")
     o_loc = np.stack([uu.ravel(), vv.ravel(), np.ones(uu.size)], 1)
-    a, b, c = loc[:128, 0, :2], loc[:128, 1, :2], loc[:128, 2, :2]
+    return flat, _lattice_rays(loc[:128], o_loc, axis)
+
+
+def _lattice_rays(loc, o_loc, axis):
+    """One (o, d, expected_id, n_candidates) per direction of LATTICE_DIRS from the local origins `o_loc` at
+    height 1 over the lattice triangles `loc` (without the light), decided in float64."""
+    a, b, c = loc[:, 0, :2], loc[:, 1, :2], loc[:, 2, :2]
 
     def cross2(p, q):
         return p[..., 0] * q[..., 1] - p[..., 1] * q[..., 0]
@@ -140,7 +148,36 @@ def lattice(axis):
         expect = np.where(cand > 0, inside.argmax(1), -1).astype(np.int64)
         rays.append((_to_world(o_loc, axis).astype(F), np.tile(_to_world(dl, axis), (o_loc.shape[0], 1)).astype(F),
                      expect, cand))
-    return flat, rays
+    return rays
+
+
+N_LATTICE_SMALL_RAYS = 4096
+_ROWS3 = [[0.9, 0.15, 0.15, 0, 0, 0, 1, 0], [0.15, 0.9, 0.15, 0, 0, 0, 1, 0], [0.15, 0.15, 0.9, 0, 0, 0, 1, 0]]
+
+
+def lattice_small(axis, cells=4):
+    """The dyadic lattice small enough for the LDS-resident kernels: cells x cells cells (4: of width 0.5,
+    32 triangles) and the two-triangle light at height 2, with a material per triangle: three diffuse rows
+    of clearly different albedo, tri_mat[i] = i % 3, and the emitter on the light.  The two triangles of a
+    cell and most neighbours across a cell edge differ in material, so the winner of a tie changes the
+    path's radiance, not only the id.
+
+    Returns (flat, (o, d, expected_id, n_candidates)): the (2 cells + 1)^2 half-cell origins at height 1 for
+    each direction of LATTICE_DIRS, one direction after the other, tiled to 4096 rays (a caller ray's path
+    is drawn by its index, so a repeated ray is another path); expected_id as lattice() decides it."""
+    loc = _lattice_local(cells)
+    tv = _to_world(loc, axis).reshape(-1, 9)
+    n = tv.shape[0]
+    mat = np.array(_ROWS3 + [_EMIT], F)
+    tri_mat = (np.arange(n) % 3).astype(np.int32)
+    tri_mat[-2:] = 3
+    flat = _per_triangle(tv, _unit_normals(tv), tri_mat, mat, [[n - 2, n - 1]], [0.9, 0.85, 0.7])
+    g = -1 + (1.0 / cells) * np.arange(2 * cells + 1)
+    uu, vv = np.meshgrid(g, g, indexing="ij")
+    o_loc = np.stack([uu.ravel(), vv.ravel(), np.ones(uu.size)], 1)
+    rays = _lattice_rays(loc[:-2], o_loc, axis)
+    idx = np.arange(N_LATTICE_SMALL_RAYS) % (len(rays) * o_loc.shape[0])
+    return flat, tuple(np.concatenate([r[k] for r in rays])[idx] for k in range(4))
 
 
 # ------------------------------------------------------------------ layers

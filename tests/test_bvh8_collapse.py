@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import bvh8_scenes as S8
+import hard_scenes as HS
 from conftest import GOLDEN, ROOT
 
 EMPTY = 0x7FFFFFFF
@@ -24,12 +25,20 @@ def _specular_tri_v():
 
 def _tri_v(name, cornell):
     flat = cornell[2]
+    if name in HOSTILE:
+        return HS.case(cornell, name)[0].tri_v
     return {"cornell": lambda: flat.tri_v, "specular": _specular_tri_v,
             "five": lambda: S8.five_triangles(flat).tri_v, "nine-leaves": lambda: S8.nine_leaves(flat).tri_v,
-            "soup": S8.soup}[name]()
+            "soup": S8.soup, "lattice-small": lambda: HS.lattice_small(2)[0].tri_v,
+            "soup-scene": lambda: S8.soup_scene(flat).tri_v}[name]()
 
 
-SCENES = ["cornell", "specular", "five", "nine-leaves", "soup"]
+# of tests/hard_scenes.py: coincident quads, needles, point and collinear triangles, a triangle referenced
+# from several leaves, exact lattices, placements at other scales (two of them not LDS-resident: the
+# collapse itself does not ask)
+HOSTILE = ["layers-0", "layers-1", "layers-2", "slivers8-1e-5", "slivers-1e-5", "slivers-1e-3", "lattice-z", "box-p0",
+           "box-p3", "soup-p3"]
+SCENES = ["cornell", "specular", "five", "nine-leaves", "soup"] + HOSTILE + ["lattice-small", "soup-scene"]
 
 
 @pytest.fixture(scope="module")
@@ -165,6 +174,15 @@ def test_bvh4_is_unchanged_by_the_width_option(trees, name, cornell):
         pinned = json.load(open(os.path.join(GOLDEN, "bvh_trees.json")))["cornell"]
         assert _fnv1a64(first[0]) == pinned["nodes4"]
         assert (len(first[0]), first[1], first[2]) == (pinned["bvh4_nodes"], pinned["bvh4_depth"], pinned["stack_need"])
+
+
+@pytest.mark.parametrize("name", ["layers-0", "slivers8-1e-5"])
+def test_hostile_lds_scenes_have_a_two_level_bvh8(trees, name):
+    """What tests/test_gpu_lds_width_hard.py relies on: forced to width 8, these scenes give the eight-wide
+    kernels a tree with a second level of inner nodes and more stack than the Cornell box's 15 entries."""
+    tree, depth, need = trees(name)[2][8]
+    assert depth == 2 and 15 < need <= 32, (name, depth, need)
+    assert any(r >= 0 for i in [r for _, _, r in tree[0] if r >= 0] for _, _, r in tree[i])
 
 
 def test_chain_scene_needs_more_stack_at_width_8(cornell):

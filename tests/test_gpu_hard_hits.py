@@ -132,6 +132,7 @@ def _check_trace(ds, osc, case, o, d, v, lds_scene=True):
     flags = (v << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
     assert ds.kernel_info()["lds_scene"] == lds_scene, ds.kernel_info()
     assert ds.kernel_info(n_items=N_TRACE, flags=flags)["variant"] == v
+    print(f"{case}: variant {v} ran at bvh_arity {ds.kernel_info(n_items=N_TRACE, flags=flags)['bvh_arity']}")
     ref = _oracle_trace(case, osc, o, d, mis)
     assert np.isfinite(ref).all() and ref.mean() > 0
     L = ds.trace_rays(o, d, DEPTH, seed=17, flags=flags)

@@ -54,6 +54,33 @@ def test_lattice_ties_are_exact_and_resolved_to_the_lowest_id(axis):
         assert np.array_equal(_closest_ids(osc, o[h], d[h], np.nextafter(tt, np.float32(0)), T_MAX)[0], oid[h])
 
 
+@pytest.mark.parametrize("axis", [0, 1, 2])
+def test_small_lattice_ties_decide_the_radiance(axis):
+    """lattice_small, the lattice of the LDS-resident kernels (tests/test_gpu_lds_width_hard.py): at least
+    half its rays end on a bit-equal tie (the reference gives 0.65), the brute-force winner is the float64
+    expectation, and for at least 0.3 of the paths (the reference alone gives 0.48) the oracle's radiance at
+    depth 4 changes when the triangle order, and with it every tie's winner, is reversed: a kernel that
+    resolves ties otherwise cannot produce the oracle's image.  Conditions on the input, not measurements."""
+    flat, (o, d, expect, cand) = HS.lattice_small(axis)
+    n = flat.n_tri
+    assert n == 34 and o.shape == d.shape == (HS.N_LATTICE_SMALL_RAYS, 3) and flat.n_light == 1
+    assert set(flat.tri_mat[:32]) == {0, 1, 2} and (flat.mat[flat.tri_mat[flat.light_tri], 3] > 0).all()
+    assert np.abs(np.linalg.norm(flat.tri_n.astype(np.float64), axis=1) - 1).max() < 1e-6
+    assert np.unique(flat.mat[:3, :3], axis=0).shape[0] == 3
+    osc = O.OracleScene.from_flat(flat)
+    oid, _ = _closest_ids(osc, o, d)
+    assert np.array_equal(oid, expect)
+    ties = HS.tie_rays(flat, o, d)
+    assert not (ties & (cand < 2)).any()
+    assert ties.mean() >= 0.5, ties.mean()
+    L = osc.trace_rays(o, d, 4, seed=17)
+    R = O.OracleScene.from_flat(HS.reindexed(flat, np.arange(n)[::-1])).trace_rays(o, d, 4, seed=17)
+    assert np.isfinite(L).all() and np.isfinite(R).all() and L.mean() > 0
+    changed = np.any(L.view(np.uint32) != R.view(np.uint32), axis=1)
+    print(f"lattice_small axis {axis}: tie share {ties.mean():.3f}, radiance changed on {changed.mean():.3f}")
+    assert changed.mean() >= 0.3, changed.mean()
+
+
 def test_cornell_far_rays_hit_and_tie(cornell, oracle_scene):
     flat, sets = HS.case(cornell, "cornell")
     assert HS.tie_rays(flat, *sets["interior"]).sum() >= 40      # measured 94: box bottoms coplanar with the floor

@@ -217,14 +217,14 @@ def _old_variant(z, need4, stack4, mis):
     return 1 if smem * 7 <= 160 * 1024 else 6 if smem * 6 <= 160 * 1024 else 2
 
 
-def _with_total(total, fn, **counts):
-    """The size tuple of `counts` with n_refs, n_mat and n_lt chosen so that fn(sizes) == total."""
+def _with_total(total, fn, make=_sizes, **counts):
+    """The size tuple make(**counts) with n_refs, n_mat and n_lt chosen so that fn(sizes) == total."""
     for n_mat in range(1, 8):
         for n_lt in range(1, 5):
-            z0 = _sizes(n_refs=0, n_mat=n_mat, n_lt=n_lt, **counts)
+            z0 = make(n_refs=0, n_mat=n_mat, n_lt=n_lt, **counts)
             rest = total - fn(z0)
             if rest >= 48 * counts["n_tri"] and rest % 48 == 0:
-                z = _sizes(n_refs=int(rest // 48), n_mat=n_mat, n_lt=n_lt, **counts)
+                z = make(n_refs=int(rest // 48), n_mat=n_mat, n_lt=n_lt, **counts)
                 assert fn(z) == total
                 return z
     raise AssertionError("no tuple with total %d" % total)
@@ -310,6 +310,122 @@ def test_variant_choice_matches_the_parent_rule(built):
         assert rep["mis"] == _old_variant(z, n4, s4, True), (name, n4, s4)
         seen.update((rep["nee"], rep["mis"]))
     assert seen == {1, 2, 3, 4, 5, 6, 7}   # every variant a default can be (8 is only ever forced)
+
+
+# ---------------------------------------------------------------- the width rule
+# prt_plan.cpp lds_width restated from its text.  The restatements above extended by the width: a width
+# tuple is a size tuple followed by the width, its n_node_f4 counting 14 float4 per BVH8 node, and a
+# width-8 node copy is 8 x n_node_f4 where the BVH4's is 7 x n_node_f4.
+
+def _sizes8(n_node8=1, width=8, **counts):
+    z = _sizes(n_node4=0, **counts)
+    z[0] = 14 * n_node8
+    return np.append(z, width)
+
+
+def _node_copy_extra(z):
+    return 16 * z[0] if z[7] == 8 else 0
+
+
+def _scene_bytes_w(z):
+    return _old_scene_bytes(z[:7]) + _node_copy_extra(z)
+
+
+def _pool_bytes_w(z, stack):
+    zz = z[:7].copy()
+    zz[6] = stack
+    return _old_smem(16, 7, zz) + _node_copy_extra(z)
+
+
+def _fits_w(z):
+    n_nodes = z[0] // (14 if z[7] == 8 else 8)
+    return bool(_scene_bytes_w(z) <= 24 * 1024 and n_nodes < 0x7FFF and (z[1] // 3) * 8 <= 32768)
+
+
+def _width_rule(z, need8, knob):
+    can8 = z[7] == 8 and z[0] > 0 and 1 <= need8 <= 32 and _fits_w(z)
+    if not can8 or knob == 4:
+        return 4
+    if knob == 8:
+        return 8
+    return 8 if _pool_bytes_w(z, need8) * 7 <= 160 * 1024 else 4
+
+
+def _width_cases():
+    """(what the case names, width tuple, need8, knob, the width it claims)."""
+    box = dict(n_node8=3, n_refs=36, n_tri=36, n_mat=8, n_lt=2, n_light=1, stack=15)   # the Cornell box's BVH8
+    c = [("need8_%d" % need8, _sizes8(**box), need8, 8, want) for need8, want in ((0, 4), (1, 8), (32, 8), (33, 4))]
+    c += [("need8_1_default", _sizes8(**box), 1, 0, 8),
+          ("need8_32_default", _sizes8(**box), 32, 0, 4)]      # 16 KiB of stacks: seven blocks no longer fit
+    for total, want in ((24576, 8), (24592, 4)):
+        z = _with_total(total, _scene_bytes_w, make=_sizes8, n_node8=5, n_tri=40, n_light=3, stack=10)
+        c.append(("scene_%d" % total, z, 10, 8, want))
+    for total, want in ((23392, 8), (23408, 4)):
+        z = _with_total(total, lambda z: _pool_bytes_w(z, 10), make=_sizes8, n_node8=3, n_tri=36, n_light=3, stack=10)
+        c += [("pool7_%d" % total, z, 10, 0, want), ("pool7_%d_knob5" % total, z, 10, 5, want),
+              ("pool7_%d_forced" % total, z, 10, 8, 8)]
+    c += [("z8_width_4_knob%d" % knob, _sizes8(width=4, **box), 15, knob, 4) for knob in (0, 8)]
+    c += [("no_bvh8_knob%d" % knob, _sizes8(**dict(box, n_node8=0)), 15, knob, 4) for knob in (0, 8)]
+    c += [("knob_%d" % knob, _sizes8(**box), 15, knob, want) for knob, want in ((0, 8), (4, 4), (8, 8), (5, 8))]
+    return c
+
+
+WIDTH_CASES = _width_cases()
+
+
+def test_width_tuples_sit_on_the_thresholds_they_name():
+    by_name = {name: (z, need8, knob, want) for name, z, need8, knob, want in WIDTH_CASES}
+    assert len(by_name) == len(WIDTH_CASES)
+    for name, (z, need8, knob, want) in by_name.items():
+        assert _width_rule(z, need8, knob) == want, name
+    for total in (24576, 24592):
+        z = by_name["scene_%d" % total][0]
+        assert _scene_bytes_w(z) == total and _fits_w(z) == (total == 24576)
+        assert _scene_bytes_w(z) - _old_scene_bytes(z[:7]) == 5 * 224     # the eighth copy of five nodes' 14 float4
+        assert _pool_bytes_w(z, 10) * 7 > 160 * 1024                      # so only the forced width gets this far
+    for total in (23392, 23408):
+        z = by_name["pool7_%d" % total][0]
+        assert _pool_bytes_w(z, 10) == total and total % 16 == 0 and _fits_w(z)
+        assert (total * 7 <= 160 * 1024) == (total == 23392)
+    box = by_name["knob_0"][0]
+    assert _fits_w(box) and _pool_bytes_w(box, 15) * 7 <= 160 * 1024 < _pool_bytes_w(box, 32) * 7
+    assert by_name["z8_width_4_knob8"][0][7] == 4 and by_name["no_bvh8_knob8"][0][0] == 0
+    assert {want for *_, want in WIDTH_CASES} == {4, 8}
+
+
+def _widths(built, cases):
+    """lds_width of (width tuple, need8, knob) triples through the stand-alone driver."""
+    got = _run(built, "width", *[int(v) for z, need8, knob in cases for v in list(z) + [need8, knob]])["width"]
+    assert len(got) == len(cases)
+    return got
+
+
+def test_width_rule_matches_its_restatement(built):
+    got = _widths(built, [(z, need8, knob) for _, z, need8, knob, _ in WIDTH_CASES])
+    for (name, z, need8, knob, want), w in zip(WIDTH_CASES, got):
+        assert w == want == _width_rule(z, need8, knob), (name, w, want)
+
+
+def test_width_rule_on_the_real_scenes(built, cornell):
+    """The sizes of the Cornell box and of the two hostile LDS-resident scenes, from the builder's own
+    collapse: the default rule picks 8 for the box and 4 for the others, whose eight-wide pooled layout no
+    longer fits seven blocks per CU; forced, all three run at width 8 (tests/test_gpu_lds_width_hard.py)."""
+    import hard_scenes as HS
+    from pyrenderer_amd import _native as N
+    cases = []
+    for name in ("cornell", "layers-0", "slivers8-1e-5"):
+        flat = HS.case(cornell, name)[0]
+        b = N.Bvh(flat.tri_v, max_leaf=4)
+        nodes8, _, need8 = b.collapse(8)
+        z8 = np.array([14 * len(nodes8), 3 * b.n_tri, flat.n_tri, flat.mat.shape[0], flat.light_tri.shape[0],
+                       flat.n_light, need8, 8], np.int64)
+        assert _fits_w(z8) and need8 <= 32, name
+        print(name, "BVH8 nodes", len(nodes8), "need", need8, "scene bytes", _scene_bytes_w(z8), "pooled",
+              _pool_bytes_w(z8, need8))
+        cases += [(z8, need8, knob) for knob in (0, 4, 8)]
+    got = _widths(built, cases)
+    assert got == [_width_rule(*c) for c in cases]
+    assert got == [8, 4, 8, 4, 4, 8, 4, 4, 8], got
 
 
 # ---------------------------------------------------------------- knobs and camera

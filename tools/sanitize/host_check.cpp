@@ -17,6 +17,8 @@
 //       bytes, lds_scene_bytes, and trace_smem_bytes(stack, var, sizes) for var = 0 .. kVarLast + 1
 //   host_check variant (<n_node_f4> <n_tri_f4> <n_tri> <n_mat> <n_lt> <n_light> <need4> <stack4>)...
 //       per tuple: lds_fits, and choose_variant without and with the MIS estimator
+//   host_check width (<n_node_f4> <n_tri_f4> <n_tri> <n_mat> <n_lt> <n_light> <stack> <width> <need8> <knob>)...
+//       per tuple: lds_width of those sizes (the scene's with its BVH8), need8 and PRT_LDS_WIDTH = knob
 //   host_check scene <dir> <n_tri> <n_sph> <n_mat> <n_light>
 //       reads <dir>/{tri_v,tri_n,sph,mat}.f32 and {tri_mat,sph_mat,light_tri,light_off}.i32 (raw, as
 //       numpy.tofile writes them; a missing file is a NULL argument), validates, and when valid packs
@@ -195,6 +197,16 @@ int main(int argc, char** argv) {
                         prt::choose_variant(z, need4, stack4, true));
         }
         std::printf("]\n");
+    } else if (mode == "width" && argc >= 12 && (argc - 2) % 10 == 0) {
+        std::vector<int> w;
+        for (int i = 2; i < argc; i += 10) {
+            const prt::LdsSizes z8{(int)num(i), (int)num(i + 1), (int)num(i + 2), (int)num(i + 3), (int)num(i + 4),
+                                   (int)num(i + 5), (int)num(i + 6), (int)num(i + 7)};
+            w.push_back(prt::lds_width(z8, (int)num(i + 8), (int)num(i + 9)));
+        }
+        std::printf("{\"width\": ");
+        print_list(w);
+        std::printf("}\n");
     } else if (mode == "scene" && argc == 7) {
         return scene_mode(argv[2], num(3), num(4), (int)num(5), (int)num(6));
     } else {

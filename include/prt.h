@@ -45,7 +45,8 @@ extern "C" {
  * of slots outside the frame; prt_selftest_guards added.  Added later under the same number (purely
  * additive, no existing entry point changed): the denoiser's four entry points at the end of this
  * header, then the three of its variance-guided mode (prt_denoise_var*), then the four of the
- * sample-moments variance (prt_moments_add*, prt_denoise_var_given*). */
+ * sample-moments variance (prt_moments_add*, prt_denoise_var_given*), then the four of the temporal
+ * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -512,6 +513,78 @@ int prt_denoise_var_given(int device, const float* color, const float* feat, con
  * prt_denoise_var_work_bytes(W, H) bytes, 16-byte aligned (no more than prt_denoise_var_device needs).
  * The aliasing rules of prt_denoise_var_device hold, and d_in_var must not alias d_out or d_out_var. */
 int prt_denoise_var_given_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
+                                 int W, int H, int iterations, const float* params5, float* d_out,
+                                 float* d_out_var, void* d_work, int64_t work_bytes, void* stream);
+
+/* Temporal accumulation.  Added under ABI 4, purely additive.  The previous frame's
+ * integrated demodulated colour and luminance moments are reprojected through the first-hit features
+ * into this frame's camera and blended with this frame: a source of colour and of variance for the
+ * variance-guided filter while the camera moves.  Static geometry, pinhole cameras, one device.
+ *
+ * State: W x H x PRT_TEMPORAL_CHANNELS f32 [x][y], two float4 per pixel: I.rgb (integrated demodulated
+ * colour), h (history length, in frames), m1, m2 (integrated first and second moment of the demodulated
+ * luminance), the variance plane value, 0.  No state is "empty": the first frame passes NULL for
+ * prev_feat, prev_cam24 and prev_state (all three or none).
+ *   color, feat   this frame's mean radiance (W x H x 3) and features (W x H x 8), as for prt_denoise
+ *   cam24         this frame's camera record (PRT_CAM_FLOATS floats, a HOST pointer in both forms)
+ *   prev_*        the previous frame's features, camera record (host) and state
+ *   params8       alpha, alpha_m in [0, 1] (floors of the blend weights of colour and moments; 0 = a
+ *                 plain running average), tau_n in [-1, 1], tau_z > 0, tau_a >= 0 (consistency bounds on
+ *                 normal, relative depth and albedo), eps_a > 0 (the demodulation's albedo floor),
+ *                 min_history >= 1, w_min in (0, 1]; all finite
+ *   state         the new state; must not be prev_state (taps read neighbours)
+ *   out_color     (may be NULL) W x H x 3, the integrated colour re-modulated
+ *   out_var       (may be NULL) W x H, the state's variance plane
+ * Per pixel p = (x, y), every operation one IEEE f32 operation in this association
+ * (tests/temporal_ref.py restates it in NumPy):
+ *  1. hit = F[7] > 0;  a_c = fmax(A_c, eps_a);  I_c = hit ? C_c / a_c : C_c;  l = (0.2126 I_r + 0.7152 I_g)
+ *     + 0.0722 I_b.  A pixel with a channel of C, I or F that is not finite takes no part: its state is all
+ *     zeroes (h = 0: it donates nothing later), out_color = C, out_var = the marker.
+ *  2. Without history (a miss, the first frame, any failure below): state (I, 1, l, l * l, marker, 0).
+ *     The marker is the quiet NaN 0x7fc00000: "no trustworthy temporal variance here".
+ *  3. u = (x + 0.5) / (W - 1), v = (y + 0.5) / (H - 1);  rx = (u - 0.5) * sw / 0.5, ry likewise with sh;
+ *     f_i = (((rx * side_i + ry * up_i) + (-fd) * back_i) + E_i) - E_i;  d = f / sqrt((f0^2 + f1^2) + f2^2);
+ *     rel_i = (E_i + Z * d_i) - Eprev_i;  r = sqrt((rel0^2 + rel1^2) + rel2^2);
+ *     a, b, c = (rel0 * k_0 + rel1 * k_1) + rel2 * k_2 for k the previous side, up, back;
+ *     px = (0.5 + ((0.5 * fd') * a) / (sw' * -c)) * (W - 1) - 0.5, py likewise with b, sh' and H.
+ *  4. Only if c < 0 && px > -1 && px < W && py > -1 && py < H (a NaN fails): x0 = floor(px),
+ *     fx = px - x0, likewise y; no index is formed before this test and none outside the frame is loaded.
+ *  5. Taps q = (x0 + jx, y0 + jy), jx outer, jy inner, weight w = wx[jx] * wy[jy] with wx = (1 - fx, fx).
+ *     A tap counts when it is inside the frame, h_q > 0, Fprev_q[7] > 0,
+ *     (N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z >= tau_n, |Zprev_q - r| <= tau_z * r and
+ *     max_c |Aprev_q,c - A_p,c| <= tau_a.  sum_w += w; acc_k += w * state_q,k for k = I.rgb, h, m1, m2.
+ *  6. If sum_w >= w_min: hist = acc / sum_w;  h' = hist.h + 1;  ac = fmax(1 / h', alpha),
+ *     am = fmax(1 / h', alpha_m);  I' = hist.I + ac * (I - hist.I);  m1' = hist.m1 + am * (l - hist.m1);
+ *     m2' = hist.m2 + am * (l * l - hist.m2).  Otherwise step 2.
+ *  7. var = fmax(0, m2' - m1' * m1') * ac if h' >= min_history, else the marker.
+ *  8. Two bytewise equal camera records: the one tap q = p with weight 1 and r = Z_p, steps 3 and 4
+ *     skipped, the tests of step 5 kept.  With alpha = alpha_m = 0 a static sequence is a running mean.
+ * out_color = hit ? I' * a : I'.  A frame with W = 1 or H = 1 divides by zero in step 3; its pixels fail
+ * step 4 and come out as step 2 (a static one accumulates).  Finiteness: the state of a pixel that takes
+ * part is finite while |I_c| <= 2^62.
+ * Host pointers, synchronous.  Bad arguments (NULL, some but not all of prev_* NULL, W or H outside
+ * 1..32768, a parameter outside its range or not finite, a camera record that is not finite or has an
+ * aperture > 0 — a thin lens has no unique reprojection —, state == prev_state) return PRT_ERR_ARG
+ * before any device is touched, with the text in prt_denoise_last_error. */
+#define PRT_TEMPORAL_CHANNELS 8
+int prt_temporal_accumulate(int device, const float* color, const float* feat, const float* cam24,
+                            const float* prev_feat, const float* prev_cam24, const float* prev_state, int W, int H,
+                            const float* params8, float* state, float* out_color, float* out_var);
+/* prt_temporal_accumulate on device pointers (cam24 and prev_cam24 stay host pointers, read before the
+ * call returns), enqueued on `stream` with no host synchronisation.  d_state and d_prev_state must be
+ * 16-byte aligned; no output may alias an input or another output. */
+int prt_temporal_accumulate_device(int device, const float* d_color, const float* d_feat, const float* cam24,
+                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
+                                   int W, int H, const float* params8, float* d_state, float* d_out_color,
+                                   float* d_out_var, void* stream);
+/* prt_denoise_var_given with a spatial fallback: the 7 x 7 estimate of prt_denoise_var runs first, then
+ * in_var replaces it at every pixel that is not set aside where it is finite and >= 0 (-0 included);
+ * anywhere else — NaN (the temporal marker), inf, a negative value — the estimate stays.  out_var (may be
+ * NULL) receives the variance actually used.  With in_var all NaN it is prt_denoise_var, with in_var all
+ * finite and >= 0 prt_denoise_var_given, bit for bit.  Everything else is prt_denoise_var_given's. */
+int prt_denoise_var_mixed(int device, const float* color, const float* feat, const float* in_var, int W, int H,
+                          int iterations, const float* params5, float* out, float* out_var);
+int prt_denoise_var_mixed_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream);
 

@@ -132,6 +132,10 @@ EXPORTS = {
     "prt_moments_add_device": (_i, [_i, _vp, _i, _i64, ctypes.c_float, _vp, ctypes.c_float, _i, _i, _vp, _vp]),
     "prt_denoise_var_given": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "prt_denoise_var_given_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "prt_denoise_var_mixed": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "prt_denoise_var_mixed_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "prt_temporal_accumulate": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "prt_temporal_accumulate_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

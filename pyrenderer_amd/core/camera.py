@@ -106,3 +106,16 @@ class Camera:
 
     def get_resolution(self):
         return self.resolution
+
+
+def orbit(camera, degrees):
+    """`camera` turned about its look-at point around its up vector by `degrees` (Rodrigues' rotation of the
+    eye, float64): one step of a turntable.  Every other setting is the camera's."""
+    k = np.asarray(camera.up, np.float64)
+    k = k / np.sqrt(np.sum(k * k))
+    target = np.asarray(camera.looking_at, np.float64)
+    v = np.asarray(camera.position, np.float64) - target
+    t = radians(degrees)
+    v = v * np.cos(t) + np.cross(k, v) * np.sin(t) + k * np.dot(k, v) * (1.0 - np.cos(t))
+    return Camera(target + v, camera.looking_at, camera.up, camera.resolution, fov=camera.fov,
+                  aperture=camera.aperture, focal_dist=camera.focal_dist)

@@ -18,6 +18,9 @@ pyrenderer_amd.distributed (torch.distributed gather over RCCL/xGMI).
 `Accumulator` is the progressive form of main_taichi.py:108-127 (render() once
 per GUI frame, pixels += L, samples += 1, finish() of the running mean), with
 save / load to resume an accumulation.
+
+`TemporalAccumulator` / `render_sequence` render a camera path and carry the history across camera
+moves (pyrenderer_amd.denoise.temporal_accumulate, DESIGN.md §11 "Temporal accumulation").
 """
 import hashlib
 import os
@@ -377,6 +380,126 @@ class Accumulator:
             acc.moments_state[...] = z["moments"]
             acc.batch_spp = int(z["batch_spp"])
         return acc
+
+
+class TemporalAccumulator:
+    """Rendering a camera path on one device with history carried across camera moves
+    (pyrenderer_amd.denoise.temporal_accumulate; DESIGN.md §11 "Temporal accumulation").
+
+    `add(camera)` renders frame t: samples t * spp .. t * spp + spp - 1 of every pixel from zero sums with
+    that camera (one world, built at the first add), takes the frame's one-sample features, reprojects the
+    previous frame's state into the new camera and blends.  `mean()` is this frame alone, `accumulated()`
+    the integrated colour, `history()` the per-pixel history length (W, H), `denoised(**filter_params)` the
+    integrated colour through the variance-guided filter with the state's variance plane and the spatial
+    estimate where the history is short (variance_fallback="spatial").  `reset()` drops the history; the
+    sample count goes on, so the next frame still draws new samples.
+
+    `temporal_params` are temporal_accumulate's keyword parameters (alpha, alpha_m, tau_n, tau_z, tau_a,
+    eps_a, min_history, w_min).  resolution: (W, H); None takes the first camera's, and every later camera
+    must then have the same.  A camera with an aperture is a ValueError: a thin lens has no unique
+    reprojection.  Static geometry, one device, no save / load."""
+
+    def __init__(self, scene, *, depth, spp, seed=0, resolution=None, device=0, tile=64, world=None, nee="reference",
+                 **temporal_params):
+        from .. import denoise as D
+        unknown = sorted(set(temporal_params) - set(D.TEMPORAL_PARAMS))
+        if unknown:
+            raise TypeError(f"unknown temporal parameter(s) {unknown}: expected some of {D.TEMPORAL_PARAMS}")
+        if isinstance(spp, (bool, np.bool_)) or not isinstance(spp, (int, np.integer)) or spp < 1:
+            raise ValueError(f"spp must be an integer >= 1, not {spp!r}")
+        nee_flags(nee)
+        self.scene, self.depth, self.spp, self.seed = scene, int(depth), int(spp), int(seed)
+        self.resolution = None if resolution is None else (int(resolution[0]), int(resolution[1]))
+        self._from_camera = resolution is None   # the first camera sets it, the later ones must agree
+        self.device, self.tile, self.world, self.nee = device, int(tile), world, nee
+        self.params = dict(temporal_params)
+        self.frames = 0      # frames rendered: the next one starts at sample frames * spp
+        self.frame = None    # the last frame's _Frame
+        self._mean = self._color = self._state = self._prev = None
+
+    def add(self, camera):
+        """Render the next frame with `camera` and fold it into the history."""
+        from .. import denoise as D
+        if camera.aperture > 0:
+            raise ValueError("TemporalAccumulator needs a pinhole camera: a thin lens (aperture > 0) has no unique "
+                             "reprojection")
+        res = tuple(int(v) for v in camera.resolution)
+        if self.resolution is None:
+            self.resolution = res
+        elif self._from_camera and res != self.resolution:
+            raise ValueError(f"the resolution cannot change within a sequence: {res} after {self.resolution}")
+        if self.world is None:
+            self.world = build_world(self.scene, (self.device,))
+        f = _Frame.of(self.scene, camera, depth=self.depth, seed=self.seed, resolution=self.resolution,
+                      devices=(self.device,), tile=self.tile, world=self.world, nee=self.nee)
+        mean = _mean(f.unpack(f.add_samples(self.frames * self.spp, self.spp)), self.spp)
+        feat = f.features()
+        state, color = D.temporal_accumulate(mean, feat, f.cam, self._prev, device=self.device, **self.params)
+        self.frame, self._mean, self._color, self._state = f, mean, color, state
+        self._prev = (state, feat, f.cam)
+        self.frames += 1
+        return self
+
+    def _need_frame(self):
+        if self.frame is None:
+            raise ValueError("no frame yet: add(camera) first")
+
+    def mean(self):
+        """This frame's Monte-Carlo mean alone, (W, H, 3)."""
+        self._need_frame()
+        return self._mean
+
+    def accumulated(self):
+        """The integrated colour, re-modulated, (W, H, 3)."""
+        self._need_frame()
+        return self._color
+
+    def history(self):
+        """The history length per pixel, (W, H) float32: 1 where this frame started afresh, 0 at a pixel that
+        is not finite."""
+        self._need_frame()
+        return self._state[..., 3]
+
+    def state(self):
+        """The temporal state, (W, H, 8) float32: I.rgb, h, m1, m2, the variance plane, 0."""
+        self._need_frame()
+        return self._state
+
+    def features(self):
+        """This frame's one-sample first-hit features."""
+        self._need_frame()
+        return self.frame.features()
+
+    def denoised(self, **filter_params):
+        """accumulated() through denoise_variance with the temporal variance and the spatial fallback."""
+        self._need_frame()
+        filter_params.setdefault("variance", self._state[..., 6])
+        filter_params.setdefault("variance_fallback", "spatial")
+        return self.frame.filter(self._color, "variance", **filter_params)
+
+    def reset(self):
+        """Forget the history: the next frame starts afresh at every pixel."""
+        self._prev = None
+        return self
+
+
+def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, device=0, tile=64, world=None,
+                    nee="reference", denoise="variance", **temporal_params):
+    """The frames of a camera path with temporal accumulation, (n, W, H, 3) float32: frame t is
+    TemporalAccumulator.add(cameras[t]) followed by denoised() (denoise="variance", the default) or
+    accumulated() (denoise=False).  Anything else is a ValueError."""
+    if not ((isinstance(denoise, str) and denoise == "variance") or denoise is False):
+        raise ValueError(f"denoise must be 'variance' or False, not {denoise!r}")
+    cameras = list(cameras)
+    if not cameras:
+        raise ValueError("render_sequence needs at least one camera")
+    acc = TemporalAccumulator(scene, depth=depth, spp=spp, seed=seed, resolution=resolution, device=device, tile=tile,
+                              world=world, nee=nee, **temporal_params)
+    out = []
+    for cam in cameras:
+        acc.add(cam)
+        out.append(acc.denoised() if denoise else acc.accumulated())
+    return np.stack(out).astype(np.float32)
 
 
 def scene_fingerprint(flat):

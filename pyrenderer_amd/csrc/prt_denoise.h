@@ -54,6 +54,37 @@ size_t var_work_bytes(int W, int H);
 hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
                        const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream);
 
+// enqueue_var with a variance plane that has gaps: the 7 x 7 estimate runs as with a null d_in_var, then
+// one select kernel replaces it at every usable pixel where d_in_var (required) is finite and >= 0;
+// elsewhere the estimate stays (SVGF's spatial fallback where a temporal history is too short).  Scratch,
+// aliasing and finiteness are enqueue_var's; d_out_var receives the variance actually used.
+hipError_t enqueue_var_mixed(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
+                             hipStream_t stream);
+
+// ---- temporal accumulation ----
+constexpr int kTemporalChannels = 8;   // I.rgb, h, m1, m2, var, 0: two float4 per pixel
+struct TemporalParams {
+    float alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min;
+};
+
+// Enqueue temporal_kernel on `stream` of the current device: this frame's mean radiance d_color (W x H x 3)
+// and features d_feat (W x H x 8) blended into the previous frame's state, reprojected from the previous
+// camera.  cam24 / prev_cam24 are HOST pointers to the 24-float records (read before the call returns);
+// d_prev_feat, prev_cam24 and d_prev_state are all null on the first frame.  is_static: the two records are
+// bytewise equal, every pixel reads its own previous state.  d_state and d_prev_state hold W x H x 8 floats,
+// 16-byte aligned, and must not be the same plane (taps read neighbours); d_out_color (W x H x 3,
+// re-modulated) and d_out_var (W x H, the state's variance plane) may be null.
+//
+// Finiteness: a pixel that takes part has finite colour, demodulated colour and features.  Its state is
+// finite while |I_c| <= 2^62: the luminance and its square, the blends between two such values and the
+// variance then stay in range.  The variance plane holds a quiet NaN wherever the history is shorter
+// than min_history: prt_denoise_var_mixed reads it as "estimate here".
+hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
+                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
+                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
+                            hipStream_t stream);
+
 // ---- variance from per-pixel sample moments ----
 
 // Running Welford update of the demodulated luminance over n_frames frames of per-pixel radiance sums

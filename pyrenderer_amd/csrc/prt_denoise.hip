@@ -1,14 +1,15 @@
 // prt_denoise.hip — edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) on
 // albedo-demodulated radiance, guided by first-hit normal and depth.
 //
-// Arithmetic contract: every operation is an IEEE f32 add, mul, div, sqrt, min, max or abs in the
+// Arithmetic contract: every operation is an IEEE f32 add, mul, div, sqrt, min, max, abs or floor in the
 // association written here (the unit is compiled with -ffp-contract=off and correctly rounded
-// division / sqrt), so tests/atrous_ref.py restates it in NumPy bit for bit.  No exp / pow.
+// division / sqrt), so tests/atrous_ref.py and its kin restate it in NumPy bit for bit.  No exp / pow.
 //
 // Frames are [x][y] with y contiguous (pixel index x * H + y).  One pixel per lane, 64 lanes along
 // y: the 16-byte loads of a tap are contiguous over a wave.  Taps come straight from global memory, except in the variance estimate
 // of the variance-guided mode, which stages its 7 x 7 windows in LDS.  The sample-moments kernels at the
-// end (moments_kernel, var_given_kernel) read and write each pixel once and take no taps.
+// end (moments_kernel, var_given_kernel, var_select_kernel) read and write each pixel once and take no taps;
+// temporal_kernel, the last one, gathers four taps per pixel from the previous frame's planes.
 #include "prt_denoise.h"
 
 namespace prt_dn {
@@ -325,6 +326,22 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_given_kernel(const float
     if (out_var) out_var[p] = var;
 }
 
+// mixed variance: after var_estimate_kernel, the caller's variance replaces the estimate at a usable pixel
+// where it is finite and >= 0 (a -0 passes as it is); everywhere else the estimate stays
+__global__ __launch_bounds__(kBlockX* kBlockY) void var_select_kernel(const float4* __restrict__ nc,
+                                                                      const float* __restrict__ in_var, int W, int H,
+                                                                      float4* __restrict__ iv,
+                                                                      float* __restrict__ out_var) {
+    int x, y;
+    if (!pixel_of_lane(W, H, x, y)) return;
+    const size_t p = (size_t)x * (size_t)H + (size_t)y;
+    if (__float_as_uint(nc[p].w) != kHit) return;
+    const float t = in_var[p];
+    if (!(finite_f(t) && t >= 0.0f)) return;
+    reinterpret_cast<float*>(iv + p)[3] = t;
+    if (out_var) out_var[p] = t;
+}
+
 // running Welford update of the demodulated luminance of the batch means over n_frames frames of
 // radiance sums; state (k, mean, M2, var_mean) per pixel, one 16-byte load and store
 __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* __restrict__ sums, int n_frames,
@@ -358,6 +375,164 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* 
     if (k >= 2.0f) vm = (m2 / (k - 1.0f)) / k;
     if (!finite_f(vm)) vm = 0.0f;
     state[p] = make_float4(k, mean, m2, vm);
+}
+
+// ---- temporal accumulation (DESIGN.md §11 "Temporal accumulation"; tests/temporal_ref.py restates it) ----
+// The previous frame's integrated demodulated colour and luminance moments, reprojected through the first-hit
+// features into this frame's camera (the temporal half of SVGF, Schied et al. 2017).  The state is two float4
+// per pixel: (I.rgb, h) and (m1, m2, var, 0).  The four bilinear taps of a pixel come straight from global
+// memory: neighbouring lanes reproject to neighbouring previous pixels, so a wave's taps share cache lines.
+// The pinhole ray of PackedCamera.gen_ray is restated here at the pixel centre; floor joins the operations of
+// the arithmetic contract.
+
+constexpr uint32_t kNoVariance = 0x7fc00000u;   // the quiet NaN that marks "no trustworthy temporal variance"
+
+// the parts of the two 24-float camera records the kernel reads, by value in the kernel arguments
+struct Cameras {
+    float cur[12];    // rows 0..2 of this frame's record: (side_i, up_i, back_i, eye_i) per world axis i
+    float sw, sh, fd;
+    float prev[12];
+    float psw, psh, pfd;
+};
+
+__global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
+    const float* __restrict__ color, const float* __restrict__ feat, const float* __restrict__ prev_feat,
+    const float4* __restrict__ prev_state, const Cameras cams, int W, int H, int is_static, const TemporalParams P,
+    float4* __restrict__ state, float* __restrict__ out_color, float* __restrict__ out_var) {
+    int x, y;
+    if (!pixel_of_lane(W, H, x, y)) return;
+    const size_t p = (size_t)x * (size_t)H + (size_t)y;
+    const float marker = __uint_as_float(kNoVariance);
+
+    // 1. prepare: the filter's demodulation and its notion of a pixel that takes no part
+    float F[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) F[j] = feat[p * 8 + j];
+    const float c0 = color[p * 3], c1 = color[p * 3 + 1], c2 = color[p * 3 + 2];
+    const bool hit = F[7] > 0.0f;
+    const float a0 = fmaxf(F[0], P.eps_a), a1 = fmaxf(F[1], P.eps_a), a2 = fmaxf(F[2], P.eps_a);
+    float i0 = c0, i1 = c1, i2 = c2;
+    if (hit) {
+        i0 = c0 / a0;
+        i1 = c1 / a1;
+        i2 = c2 / a2;
+    }
+    bool bad = !(finite_f(c0) && finite_f(c1) && finite_f(c2) && finite_f(i0) && finite_f(i1) && finite_f(i2));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bad = bad || !finite_f(F[j]);
+    if (bad) {
+        state[p * 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        state[p * 2 + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (out_color) {
+            out_color[p * 3] = c0;
+            out_color[p * 3 + 1] = c1;
+            out_color[p * 3 + 2] = c2;
+        }
+        if (out_var) out_var[p] = marker;
+        return;
+    }
+    const float l = lum(i0, i1, i2);
+
+    // 2. without history: the state a miss, the first frame and every rejected reprojection end in
+    float n0 = i0, n1 = i1, n2 = i2, nh = 1.0f, nm1 = l, nm2 = l * l, nv = marker;
+
+    if (hit && prev_state) {
+        // 3. project the first hit into the previous camera
+        float r = F[6], px = (float)x, py = (float)y;
+        bool in_range = true;
+        if (!is_static) {
+            const float u = ((float)x + 0.5f) / (float)(W - 1), v = ((float)y + 0.5f) / (float)(H - 1);
+            const float rx = (u - 0.5f) * cams.sw / 0.5f, ry = (v - 0.5f) * cams.sh / 0.5f, rz = -cams.fd;
+            float E[3], f[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float* c = cams.cur + 4 * i;
+                E[i] = c[3];
+                f[i] = (((rx * c[0] + ry * c[1]) + rz * c[2]) + c[3]) - E[i];
+            }
+            const float ln = sqrtf((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
+            float rel[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) rel[i] = (E[i] + F[6] * (f[i] / ln)) - cams.prev[4 * i + 3];
+            r = sqrtf((rel[0] * rel[0] + rel[1] * rel[1]) + rel[2] * rel[2]);
+            const float a = (rel[0] * cams.prev[0] + rel[1] * cams.prev[4]) + rel[2] * cams.prev[8];
+            const float b = (rel[0] * cams.prev[1] + rel[1] * cams.prev[5]) + rel[2] * cams.prev[9];
+            const float c = (rel[0] * cams.prev[2] + rel[1] * cams.prev[6]) + rel[2] * cams.prev[10];
+            const float nc = -c;
+            px = (0.5f + ((0.5f * cams.pfd) * a) / (cams.psw * nc)) * (float)(W - 1) - 0.5f;
+            py = (0.5f + ((0.5f * cams.pfd) * b) / (cams.psh * nc)) * (float)(H - 1) - 0.5f;
+            // 4. the range test, in float comparisons a NaN fails, before any conversion or load
+            in_range = c < 0.0f && px > -1.0f && px < (float)W && py > -1.0f && py < (float)H;
+        }
+        if (in_range) {
+            int tx[2] = {x, x}, ty[2] = {y, y};
+            float wx[2] = {1.0f, 0.0f}, wy[2] = {1.0f, 0.0f};
+            if (!is_static) {
+                const float fx0 = floorf(px), fy0 = floorf(py);
+                const float fx = px - fx0, fy = py - fy0;
+                tx[0] = (int)fx0;
+                tx[1] = tx[0] + 1;
+                ty[0] = (int)fy0;
+                ty[1] = ty[0] + 1;
+                wx[0] = 1.0f - fx;
+                wx[1] = fx;
+                wy[0] = 1.0f - fy;
+                wy[1] = fy;
+            }
+            // 5. the taps, x outer, y inner; a static camera takes the one tap q = p with weight 1
+            float sw = 0.0f, s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, sh = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
+#pragma unroll
+            for (int jx = 0; jx < 2; ++jx) {
+                const int qx = tx[jx];
+                if (qx < 0 || qx >= W) continue;
+#pragma unroll
+                for (int jy = 0; jy < 2; ++jy) {
+                    const int qy = ty[jy];
+                    if (qy < 0 || qy >= H || (is_static && (jx | jy))) continue;
+                    const size_t q = (size_t)qx * (size_t)H + (size_t)qy;
+                    const float4 h0 = prev_state[q * 2];
+                    if (!(h0.w > 0.0f)) continue;
+                    const float* G = prev_feat + q * 8;
+                    if (!(G[7] > 0.0f)) continue;
+                    const float nd = (F[3] * G[3] + F[4] * G[4]) + F[5] * G[5];
+                    if (!(nd >= P.tau_n)) continue;
+                    if (!(fabsf(G[6] - r) <= P.tau_z * r)) continue;
+                    const float da = fmaxf(fmaxf(fabsf(G[0] - F[0]), fabsf(G[1] - F[1])), fabsf(G[2] - F[2]));
+                    if (!(da <= P.tau_a)) continue;
+                    const float4 h1 = prev_state[q * 2 + 1];
+                    const float w = wx[jx] * wy[jy];
+                    sw = sw + w;
+                    s0 = s0 + w * h0.x;
+                    s1 = s1 + w * h0.y;
+                    s2 = s2 + w * h0.z;
+                    sh = sh + w * h0.w;
+                    sm1 = sm1 + w * h1.x;
+                    sm2 = sm2 + w * h1.y;
+                }
+            }
+            // 6. valid history and blend
+            if (sw >= P.w_min) {
+                const float g0 = s0 / sw, g1 = s1 / sw, g2 = s2 / sw, gm1 = sm1 / sw, gm2 = sm2 / sw;
+                nh = sh / sw + 1.0f;
+                const float ac = fmaxf(1.0f / nh, P.alpha), am = fmaxf(1.0f / nh, P.alpha_m);
+                n0 = g0 + ac * (i0 - g0);
+                n1 = g1 + ac * (i1 - g1);
+                n2 = g2 + ac * (i2 - g2);
+                nm1 = gm1 + am * (l - gm1);
+                nm2 = gm2 + am * (l * l - gm2);
+                // 7. the variance of the integrated luminance, once the history is long enough
+                if (nh >= P.min_history) nv = fmaxf(0.0f, nm2 - nm1 * nm1) * ac;
+            }
+        }
+    }
+    state[p * 2] = make_float4(n0, n1, n2, nh);
+    state[p * 2 + 1] = make_float4(nm1, nm2, nv, 0.0f);
+    if (out_color) {
+        out_color[p * 3] = hit ? n0 * a0 : n0;
+        out_color[p * 3 + 1] = hit ? n1 * a1 : n1;
+        out_color[p * 3 + 2] = hit ? n2 * a2 : n2;
+    }
+    if (out_var) out_var[p] = nv;
 }
 
 // the planes of a frame's scratch, in the order work_bytes / var_work_bytes count them
@@ -429,8 +604,12 @@ size_t var_work_bytes(int W, int H) {
     return (n * 60 + 255) & ~(size_t)255;
 }
 
-hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
-                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream) {
+namespace {
+
+// enqueue_var (mixed false) and enqueue_var_mixed
+hipError_t enqueue_var_with(bool mixed, const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                            int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
+                            hipStream_t stream) {
     const Planes s(d_work, W, H, true);
     const dim3 grid = grid_of(W, H);
     (void)hipGetLastError();
@@ -439,15 +618,33 @@ hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d
     pre_kernel<<<grid, kBlock, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, s.a[1], s.nc, s.grad);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (d_in_var)
+    if (d_in_var && !mixed)
         var_given_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, d_in_var, W, H, s.a[0], s.zp, d_out_var);
     else
         var_estimate_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, s.grad, W, H, p.sigma_z, p.eps_z, s.a[0], s.zp,
                                                          d_out_var);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    if (mixed) {
+        var_select_kernel<<<grid, kBlock, 0, stream>>>(s.nc, d_in_var, W, H, s.a[0], d_out_var);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
     return passes_and_post<true>(s, d_color, d_feat, W, H, iterations, p.sigma_l, p.sigma_z, p.eps_a, p.eps_z, p.eps_l,
                                  d_out, stream);
+}
+
+}  // namespace
+
+hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
+                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream) {
+    return enqueue_var_with(false, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+}
+
+hipError_t enqueue_var_mixed(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
+                             hipStream_t stream) {
+    return enqueue_var_with(true, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
 }
 
 hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
@@ -455,6 +652,29 @@ hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch
     (void)hipGetLastError();
     moments_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
                                                          reinterpret_cast<float4*>(d_io_state));
+    return hipGetLastError();
+}
+
+hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
+                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
+                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
+                            hipStream_t stream) {
+    Cameras cams = {};
+    for (int i = 0; i < 12; ++i) cams.cur[i] = cam24[i];
+    cams.sw = cam24[16];
+    cams.sh = cam24[17];
+    cams.fd = cam24[18];
+    if (prev_cam24) {
+        for (int i = 0; i < 12; ++i) cams.prev[i] = prev_cam24[i];
+        cams.psw = prev_cam24[16];
+        cams.psh = prev_cam24[17];
+        cams.pfd = prev_cam24[18];
+    }
+    (void)hipGetLastError();   // an error left on this thread by earlier, unrelated calls is not ours
+    temporal_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_color, d_feat, d_prev_feat,
+                                                reinterpret_cast<const float4*>(d_prev_state), cams, W, H,
+                                                is_static ? 1 : 0, p, reinterpret_cast<float4*>(d_state), d_out_color,
+                                                d_out_var);
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -203,28 +204,40 @@ int check_aliasing(const std::string& who, const float* d_color, const float* d_
     return PRT_OK;
 }
 
-// prt_denoise_var_device and, with `given` (d_in_var is then required), prt_denoise_var_given_device
-int var_device(const std::string& who, bool given, int device, const float* d_color, const float* d_feat,
+// where the variance-guided filter takes its variance from: its own 7 x 7 estimate, the caller's plane
+// (d_in_var is then required), or the plane where it is finite and >= 0 and the estimate elsewhere
+enum VarSource { kEstimate, kGiven, kMixed };
+
+hipError_t enqueue_var_from(VarSource src, const float* d_color, const float* d_feat, const float* d_in_var, int W,
+                            int H, int iterations, const prt_dn::VarParams& p, float* d_out, float* d_out_var,
+                            void* d_work, hipStream_t stream) {
+    if (src == kMixed)
+        return prt_dn::enqueue_var_mixed(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+    return prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+}
+
+// prt_denoise_var_device, prt_denoise_var_given_device and prt_denoise_var_mixed_device
+int var_device(const std::string& who, VarSource src, int device, const float* d_color, const float* d_feat,
                const float* d_in_var, int W, int H, int iterations, const float* params5, float* d_out,
                float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
     prt_dn::VarParams p;
-    if (!d_color || !d_feat || (given && !d_in_var) || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    if (!d_color || !d_feat || (src != kEstimate && !d_in_var) || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
     DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
     DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::var_work_bytes(W, H), "prt_denoise_var_work_bytes"));
     DN_TRY(check_aliasing(who, d_color, d_feat, d_out, d_out_var, d_in_var));
     DN_TRY(check_device(who, device));
     DeviceGuard g(device);
     DN_HIP_TRY(g.err);
-    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
-                                   static_cast<hipStream_t>(stream)));
+    DN_HIP_TRY(enqueue_var_from(src, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
+                                static_cast<hipStream_t>(stream)));
     return PRT_OK;
 }
 
-// prt_denoise_var and, with `given` (in_var is then required), prt_denoise_var_given
-int var_host(const std::string& who, bool given, int device, const float* color, const float* feat, const float* in_var,
+// prt_denoise_var, prt_denoise_var_given and prt_denoise_var_mixed
+int var_host(const std::string& who, VarSource src, int device, const float* color, const float* feat, const float* in_var,
              int W, int H, int iterations, const float* params5, float* out, float* out_var) {
     prt_dn::VarParams p;
-    if (!color || !feat || (given && !in_var) || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    if (!color || !feat || (src != kEstimate && !in_var) || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
     DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
     DN_TRY(check_device(who, device));
     DeviceGuard g(device);
@@ -233,14 +246,52 @@ int var_host(const std::string& who, bool given, int device, const float* color,
     Staging s;
     const float* d_color = s.in(color, n * 3);
     const float* d_feat = s.in(feat, n * 8);
-    const float* d_in_var = given ? s.in(in_var, n) : nullptr;
+    const float* d_in_var = src != kEstimate ? s.in(in_var, n) : nullptr;
     float* d_out = s.out(out, n * 3);
     float* d_out_var = s.out(out_var, n);
     void* d_work = s.bytes(prt_dn::var_work_bytes(W, H));
     if (s.oom()) return fail_oom(who);
     DN_HIP_TRY(s.upload());
-    DN_HIP_TRY(prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, nullptr));
+    DN_HIP_TRY(enqueue_var_from(src, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, nullptr));
     DN_HIP_TRY(s.download());
+    return PRT_OK;
+}
+
+// checks of the temporal entry points that need no pointer: the frame and params8 = alpha, alpha_m, tau_n,
+// tau_z, tau_a, eps_a, min_history, w_min; fills `p`.  A comparison with a NaN is false, so each range is
+// written as the condition a legal value meets.
+int check_temporal_params(const std::string& who, int device, int W, int H, const float* params8,
+                          prt_dn::TemporalParams* p) {
+    DN_TRY(check_frame(who, device, W, H));
+    if (!params8) return fail(PRT_ERR_ARG, who + ": params8 is NULL");
+    *p = {params8[0], params8[1], params8[2], params8[3], params8[4], params8[5], params8[6], params8[7]};
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f)) return fail(PRT_ERR_ARG, who + ": alpha must be in [0, 1]");
+    if (!(p->alpha_m >= 0.0f && p->alpha_m <= 1.0f)) return fail(PRT_ERR_ARG, who + ": alpha_m must be in [0, 1]");
+    if (!(p->tau_n >= -1.0f && p->tau_n <= 1.0f)) return fail(PRT_ERR_ARG, who + ": tau_n must be in [-1, 1]");
+    if (!positive_finite(p->tau_z)) return fail(PRT_ERR_ARG, who + ": tau_z must be positive and finite");
+    if (!(p->tau_a >= 0.0f && std::isfinite(p->tau_a))) return fail(PRT_ERR_ARG, who + ": tau_a must be >= 0 and finite");
+    if (!positive_finite(p->eps_a)) return fail(PRT_ERR_ARG, who + ": eps_a must be positive and finite");
+    if (!(p->min_history >= 1.0f && std::isfinite(p->min_history)))
+        return fail(PRT_ERR_ARG, who + ": min_history must be >= 1 and finite");
+    if (!(p->w_min > 0.0f && p->w_min <= 1.0f)) return fail(PRT_ERR_ARG, who + ": w_min must be in (0, 1]");
+    return PRT_OK;
+}
+
+// the camera records of a temporal call: the three `prev` pointers are NULL together (the first frame) or
+// not at all, every float is finite, and neither camera has an aperture (a thin lens has no unique
+// reprojection).  `is_static`: the two records are bytewise equal.
+int check_temporal_cameras(const std::string& who, const float* cam24, const void* prev_feat, const float* prev_cam24,
+                           const void* prev_state, bool* is_static) {
+    const int n_prev = (prev_feat ? 1 : 0) + (prev_cam24 ? 1 : 0) + (prev_state ? 1 : 0);
+    if (n_prev != 0 && n_prev != 3)
+        return fail(PRT_ERR_ARG, who + ": prev_feat, prev_cam24 and prev_state must be NULL together or not at all");
+    for (const float* cam : {cam24, prev_cam24}) {
+        if (!cam) continue;
+        for (int i = 0; i < PRT_CAM_FLOATS; ++i)
+            if (!std::isfinite(cam[i])) return fail(PRT_ERR_ARG, who + ": a camera record is not finite");
+        if (cam[19] > 0.0f) return fail(PRT_ERR_ARG, who + ": a camera with an aperture > 0 cannot be reprojected");
+    }
+    *is_static = prev_cam24 && std::memcmp(cam24, prev_cam24, PRT_CAM_FLOATS * sizeof(float)) == 0;
     return PRT_OK;
 }
 
@@ -300,13 +351,13 @@ int64_t prt_denoise_var_work_bytes(int W, int H) {
 int prt_denoise_var_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
                            const float* params5, float* d_out, float* d_out_var, void* d_work, int64_t work_bytes,
                            void* stream) {
-    return var_device("prt_denoise_var_device", false, device, d_color, d_feat, nullptr, W, H, iterations, params5,
+    return var_device("prt_denoise_var_device", kEstimate, device, d_color, d_feat, nullptr, W, H, iterations, params5,
                       d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var(int device, const float* color, const float* feat, int W, int H, int iterations,
                     const float* params5, float* out, float* out_var) {
-    return var_host("prt_denoise_var", false, device, color, feat, nullptr, W, H, iterations, params5, out, out_var);
+    return var_host("prt_denoise_var", kEstimate, device, color, feat, nullptr, W, H, iterations, params5, out, out_var);
 }
 
 // ---- variance from per-pixel sample moments ----
@@ -314,13 +365,13 @@ int prt_denoise_var(int device, const float* color, const float* feat, int W, in
 int prt_denoise_var_given_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
-    return var_device("prt_denoise_var_given_device", true, device, d_color, d_feat, d_in_var, W, H, iterations,
+    return var_device("prt_denoise_var_given_device", kGiven, device, d_color, d_feat, d_in_var, W, H, iterations,
                       params5, d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var_given(int device, const float* color, const float* feat, const float* in_var, int W, int H,
                           int iterations, const float* params5, float* out, float* out_var) {
-    return var_host("prt_denoise_var_given", true, device, color, feat, in_var, W, H, iterations, params5, out,
+    return var_host("prt_denoise_var_given", kGiven, device, color, feat, in_var, W, H, iterations, params5, out,
                     out_var);
 }
 
@@ -357,6 +408,85 @@ int prt_moments_add(int device, const float* sums, int n_frames, int64_t frame_p
     DN_HIP_TRY(s.upload());
     DN_HIP_TRY(prt_dn::enqueue_moments(d_sums, n_frames, (size_t)frame_pitch, n_samples, d_feat, eps_a, W, H, d_state,
                                        nullptr));
+    DN_HIP_TRY(s.download());
+    return PRT_OK;
+}
+
+// ---- variance plane with a spatial fallback ----
+
+int prt_denoise_var_mixed_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
+                                 int W, int H, int iterations, const float* params5, float* d_out,
+                                 float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
+    return var_device("prt_denoise_var_mixed_device", kMixed, device, d_color, d_feat, d_in_var, W, H, iterations,
+                      params5, d_out, d_out_var, d_work, work_bytes, stream);
+}
+
+int prt_denoise_var_mixed(int device, const float* color, const float* feat, const float* in_var, int W, int H,
+                          int iterations, const float* params5, float* out, float* out_var) {
+    return var_host("prt_denoise_var_mixed", kMixed, device, color, feat, in_var, W, H, iterations, params5, out,
+                    out_var);
+}
+
+// ---- temporal accumulation ----
+
+int prt_temporal_accumulate_device(int device, const float* d_color, const float* d_feat, const float* cam24,
+                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
+                                   int W, int H, const float* params8, float* d_state, float* d_out_color,
+                                   float* d_out_var, void* stream) {
+    const std::string who("prt_temporal_accumulate_device");
+    prt_dn::TemporalParams p;
+    bool is_static = false;
+    if (!d_color || !d_feat || !cam24 || !d_state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_temporal_params(who, device, W, H, params8, &p));
+    DN_TRY(check_temporal_cameras(who, cam24, d_prev_feat, prev_cam24, d_prev_state, &is_static));
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 != 0 || reinterpret_cast<uintptr_t>(d_prev_state) % 16 != 0)
+        return fail(PRT_ERR_ARG, who + ": d_state and d_prev_state must be 16-byte aligned");
+    // every output against every input and against the other outputs
+    const void* ins[] = {d_color, d_feat, d_prev_feat, d_prev_state};
+    const void* outs[] = {d_state, d_out_color, d_out_var};
+    for (int i = 0; i < 3; ++i) {
+        if (!outs[i]) continue;
+        for (const void* in : ins)
+            if (outs[i] == in)
+                return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias an input (d_state "
+                                               "not d_prev_state: taps read neighbours)");
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias each other");
+    }
+    DN_TRY(check_device(who, device));
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static,
+                                        p, d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+int prt_temporal_accumulate(int device, const float* color, const float* feat, const float* cam24,
+                            const float* prev_feat, const float* prev_cam24, const float* prev_state, int W, int H,
+                            const float* params8, float* state, float* out_color, float* out_var) {
+    const std::string who("prt_temporal_accumulate");
+    prt_dn::TemporalParams p;
+    bool is_static = false;
+    if (!color || !feat || !cam24 || !state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_temporal_params(who, device, W, H, params8, &p));
+    DN_TRY(check_temporal_cameras(who, cam24, prev_feat, prev_cam24, prev_state, &is_static));
+    if (state == prev_state) return fail(PRT_ERR_ARG, who + ": state must not alias prev_state");
+    DN_TRY(check_device(who, device));
+    DeviceGuard g(device);
+    DN_HIP_TRY(g.err);
+    const size_t n = (size_t)W * (size_t)H;
+    Staging s;
+    const float* d_color = s.in(color, n * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    const float* d_prev_feat = prev_feat ? s.in(prev_feat, n * 8) : nullptr;
+    const float* d_prev_state = prev_state ? s.in(prev_state, n * prt_dn::kTemporalChannels) : nullptr;
+    float* d_state = s.out(state, n * prt_dn::kTemporalChannels);
+    float* d_out_color = s.out(out_color, n * 3);
+    float* d_out_var = s.out(out_var, n);
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
+                                        d_state, d_out_color, d_out_var, nullptr));
     DN_HIP_TRY(s.download());
     return PRT_OK;
 }

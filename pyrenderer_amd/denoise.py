@@ -2,7 +2,9 @@
 
 `features()` computes per-pixel albedo / shading normal / depth / hit fraction of the render's own
 primary rays in one HIP kernel (prt_features; `features_device()` leaves them on the device);
-`denoise()` runs the HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise).  There is no CPU fallback.
+`denoise()` runs the HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise); `temporal_accumulate()`
+carries a frame's integrated colour and luminance moments into the next camera (prt_temporal_accumulate).
+There is no CPU fallback.
 """
 import ctypes
 
@@ -169,12 +171,23 @@ VAR_EPS_L = 1e-2
 MODES = ("fixed", "variance")
 
 
+VARIANCE_FALLBACKS = ("zero", "spatial")
+
+
 def _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l):
     return np.array([sigma_l, sigma_z, eps_a, eps_z, eps_l], np.float32)
 
 
+def _check_fallback(variance_fallback, has_plane):
+    if variance_fallback not in VARIANCE_FALLBACKS:
+        raise ValueError(f"variance_fallback must be one of {VARIANCE_FALLBACKS}, not {variance_fallback!r}")
+    if variance_fallback == "spatial" and not has_plane:
+        raise ValueError("variance_fallback='spatial' needs a variance plane to fall back from")
+
+
 def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A,
-                     eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False, variance=None):
+                     eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False, variance=None,
+                     variance_fallback="zero"):
     """denoise() with the colour edge-stopping width taken from the image's own noise: a 7 x 7
     estimate of the variance of the demodulated luminance scales it per pixel, and the variance is
     carried through the passes.  Returns (W, H, 3) float32, or with return_variance=True the pair
@@ -186,7 +199,12 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
     variance: None (default) estimates the variance from the image as described.  A (W, H) plane, e.g.
     channel 3 of a moments state (moments_add), is used in its place (prt_denoise_var_given): at a pixel
     that is filtered a finite value >= 0 is taken as it is, anything else counts as 0.  The variance
-    returned with return_variance=True is then the one actually used."""
+    returned with return_variance=True is then the one actually used.
+
+    variance_fallback: what stands where `variance` is not finite and >= 0.  "zero" (default) is the rule
+    above.  "spatial" (prt_denoise_var_mixed) runs the 7 x 7 estimate too and keeps it there: the plane of a
+    temporal state (temporal_accumulate) holds a NaN wherever its history is too short to trust."""
+    _check_fallback(variance_fallback, variance is not None)
     mean, feat, W, H = _frame_and_features(mean, feat)
     out = np.zeros_like(mean)
     var = np.zeros((W, H), np.float32) if return_variance else None
@@ -196,7 +214,8 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
         plane = np.ascontiguousarray(variance, np.float32)
         if plane.shape != (W, H):
             raise ValueError(f"variance must be {(W, H)}, not {plane.shape}")
-        fn, given = N.lib().prt_denoise_var_given, [N.ptr(plane)]
+        fn = N.lib().prt_denoise_var_mixed if variance_fallback == "spatial" else N.lib().prt_denoise_var_given
+        given = [N.ptr(plane)]
     N.check_denoise(fn(int(device), N.ptr(mean), N.ptr(feat), *given, W, H, int(iterations), N.ptr(par), N.ptr(out),
                        N.ptr(var)))
     return (out, var) if return_variance else out
@@ -223,15 +242,19 @@ def work_bytes_variance(W, H):
 
 def denoise_variance_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr, n_work_bytes, *, d_out_var_ptr=None,
                             iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A, eps_z=EPS_Z,
-                            eps_l=VAR_EPS_L, device=0, stream_ptr=None, d_in_var_ptr=None):
+                            eps_l=VAR_EPS_L, device=0, stream_ptr=None, d_in_var_ptr=None, variance_fallback="zero"):
     """prt_denoise_var_device: denoise_variance on device pointers, enqueued on `stream_ptr` without a
     host synchronisation; `d_out_var_ptr` (W x H floats, optional) receives the variance estimate.
     `d_in_var_ptr` (W x H floats, optional) is denoise_variance's `variance` (prt_denoise_var_given_device,
-    same scratch); it must not alias the output or `d_out_var_ptr`."""
+    same scratch); it must not alias the output or `d_out_var_ptr`.  variance_fallback="spatial" keeps the
+    7 x 7 estimate where that plane is not finite and >= 0 (prt_denoise_var_mixed_device)."""
+    _check_fallback(variance_fallback, bool(d_in_var_ptr))
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
     fn, given = N.lib().prt_denoise_var_device, []
     if d_in_var_ptr:
-        fn, given = N.lib().prt_denoise_var_given_device, [_vp(d_in_var_ptr)]
+        fn = (N.lib().prt_denoise_var_mixed_device if variance_fallback == "spatial"
+              else N.lib().prt_denoise_var_given_device)
+        given = [_vp(d_in_var_ptr)]
     N.check_denoise(fn(int(device), _vp(d_color_ptr), _vp(d_feat_ptr), *given, int(W), int(H), int(iterations),
                        N.ptr(par), _vp(d_out_ptr), _vp(d_out_var_ptr), _vp(d_work_ptr), int(n_work_bytes),
                        _vp(stream_ptr)))
@@ -281,3 +304,87 @@ def moments_add_device(d_sums_ptr, n_frames, n_samples, d_feat_ptr, W, H, d_stat
     N.check_denoise(N.lib().prt_moments_add_device(int(device), _vp(d_sums_ptr), int(n_frames), int(frame_pitch),
                                                    float(n_samples), _vp(d_feat_ptr), float(eps_a), int(W), int(H),
                                                    _vp(d_state_ptr), _vp(stream_ptr)))
+
+
+# ---- temporal accumulation (prt_temporal_accumulate; DESIGN.md §11 "Temporal accumulation") ----
+TEMPORAL_CHANNELS = 8        # I.rgb, h, m1, m2, var, 0
+# alpha (= alpha_m), tau_z and tau_n chosen by tools/denoise_sweep.py --mode temporal
+# (profiles/denoise_temporal_sweep.txt) by the filters' rule: the lowest geometric-mean RMSE ratio among the sets
+# that leave no sequence worse than the variance-guided filter alone (tau_n 0.8 and 0.9 tie; the stricter one
+# stands).  tau_a, min_history and w_min were not swept; eps_a is the filters'
+TEMPORAL_ALPHA = 0.2         # floor of the colour's blend weight: 1 / alpha frames of effective history
+TEMPORAL_ALPHA_M = 0.2       # ... of the luminance moments'
+TEMPORAL_TAU_N = 0.9         # least dot product of the two shading normals
+TEMPORAL_TAU_Z = 0.05        # greatest relative difference of the reprojected distance
+TEMPORAL_TAU_A = 0.05        # greatest difference of an albedo channel
+TEMPORAL_MIN_HISTORY = 4.0   # frames before the temporal variance is trusted (SVGF's threshold)
+TEMPORAL_W_MIN = 0.25        # least sum of accepted bilinear weights
+TEMPORAL_PARAMS = ("alpha", "alpha_m", "tau_n", "tau_z", "tau_a", "eps_a", "min_history", "w_min")
+
+
+def _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min):
+    return np.array([alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min], np.float32)
+
+
+def _camera_record(cam, name):
+    cam = np.ascontiguousarray(cam, np.float32)
+    if cam.shape != (24,):
+        raise ValueError(f"{name} must be a packed camera record of 24 floats, not {cam.shape}")
+    if cam[19] > 0:
+        raise ValueError(f"{name} has an aperture: a thin lens has no unique reprojection")
+    return cam
+
+
+def temporal_state(W, H):
+    """A (W, H, 8) float32 array of zeros for a temporal state, [x][y]: channels I.rgb (integrated
+    demodulated colour), h (history length), m1, m2 (integrated luminance moments), the variance plane, 0."""
+    return np.zeros((int(W), int(H), TEMPORAL_CHANNELS), np.float32)
+
+
+def temporal_accumulate(mean, feat, cam, prev=None, *, alpha=TEMPORAL_ALPHA, alpha_m=TEMPORAL_ALPHA_M,
+                        tau_n=TEMPORAL_TAU_N, tau_z=TEMPORAL_TAU_Z, tau_a=TEMPORAL_TAU_A, eps_a=EPS_A,
+                        min_history=TEMPORAL_MIN_HISTORY, w_min=TEMPORAL_W_MIN, device=0, return_color=True):
+    """One frame of temporal accumulation.  `mean` (W, H, 3), `feat` (W, H, 8) and `cam` (the packed 24-float
+    record) are this frame's; prev = (state, feat, cam) is the previous frame's, None on the first.  The
+    previous state is reprojected through this frame's first hits into the previous camera, tested for
+    consistency (normal, depth, albedo) and blended with this frame.  Returns (state, colour): the new
+    (W, H, 8) state and the integrated colour (W, H, 3), re-modulated; just the state with
+    return_color=False.  state[..., 3] is the history length, state[..., 6] the variance of the integrated
+    luminance, NaN where the history is shorter than min_history: denoise_variance(colour, feat,
+    variance=state[..., 6], variance_fallback="spatial") filters the result."""
+    mean, feat, W, H = _frame_and_features(mean, feat)
+    cam = _camera_record(cam, "cam")
+    par = _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min)
+    p_state = p_feat = p_cam = None
+    if prev is not None:
+        p_state, p_feat, p_cam = prev
+        p_state = np.ascontiguousarray(p_state, np.float32)
+        p_feat = np.ascontiguousarray(p_feat, np.float32)
+        if p_state.shape != (W, H, TEMPORAL_CHANNELS) or p_feat.shape != (W, H, FEATURE_CHANNELS):
+            raise ValueError(f"prev must hold a {(W, H, TEMPORAL_CHANNELS)} state and {(W, H, FEATURE_CHANNELS)} "
+                             f"features (the resolution cannot change), not {p_state.shape} and {p_feat.shape}")
+        p_cam = _camera_record(p_cam, "prev's camera")
+    state = temporal_state(W, H)
+    color = np.zeros_like(mean) if return_color else None
+    N.check_denoise(N.lib().prt_temporal_accumulate(int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam), N.ptr(p_feat),
+                                                    N.ptr(p_cam), N.ptr(p_state), W, H, N.ptr(par), N.ptr(state),
+                                                    N.ptr(color), None))
+    return (state, color) if return_color else state
+
+
+def temporal_accumulate_device(d_color_ptr, d_feat_ptr, cam, W, H, d_state_ptr, *, d_prev_feat_ptr=None, prev_cam=None,
+                               d_prev_state_ptr=None, d_out_color_ptr=None, d_out_var_ptr=None, alpha=TEMPORAL_ALPHA,
+                               alpha_m=TEMPORAL_ALPHA_M, tau_n=TEMPORAL_TAU_N, tau_z=TEMPORAL_TAU_Z,
+                               tau_a=TEMPORAL_TAU_A, eps_a=EPS_A, min_history=TEMPORAL_MIN_HISTORY,
+                               w_min=TEMPORAL_W_MIN, device=0, stream_ptr=None):
+    """prt_temporal_accumulate_device: temporal_accumulate on device pointers, enqueued on `stream_ptr` without
+    a host synchronisation.  `cam` and `prev_cam` are host records; the state planes (W x H x 8 floats) must
+    be 16-byte aligned and distinct; `d_out_var_ptr` (W x H floats) receives the variance plane, the
+    `d_in_var_ptr` of denoise_variance_device(..., variance_fallback="spatial")."""
+    cam = _camera_record(cam, "cam")
+    p_cam = None if prev_cam is None else _camera_record(prev_cam, "prev_cam")
+    par = _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min)
+    N.check_denoise(N.lib().prt_temporal_accumulate_device(
+        int(device), _vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam), _vp(d_prev_feat_ptr), N.ptr(p_cam),
+        _vp(d_prev_state_ptr), int(W), int(H), N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr),
+        _vp(stream_ptr)))

@@ -9,6 +9,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd --samples 8 --denoise --aov aov/                 # filtered image + feature buffers
     python -m pyrenderer_amd --samples 8 --denoise --denoise-mode variance    # width from the image's own noise
     python -m pyrenderer_amd --samples 64 --denoise --denoise-mode variance --variance-batches 8   # ... from sample moments
+    python -m pyrenderer_amd --samples 2 --frames 24 --orbit 2 --temporal --denoise --denoise-mode variance   # turntable
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
 no CPU fallback.
@@ -21,7 +22,8 @@ import time
 import numpy as np
 
 from . import denoise as D
-from .core.tracing import Accumulator, _check_variance_batches, _Frame, _mean, as_image
+from .core.camera import orbit
+from .core.tracing import Accumulator, TemporalAccumulator, _check_variance_batches, _Frame, _mean, as_image
 from .io_utils.read_tungsten import read_file
 from .tone_map import finish, reinhard_extended, save_hdr, to_uint8, write_png
 
@@ -67,6 +69,16 @@ def parse(argv=None):
                          "depth.npy ((W, H) float32 [x][y], 0 where no ray hits); with --denoise --denoise-mode "
                          "variance also variance.npy, the (W, H) float32 variance of the demodulated luminance "
                          "that the filter used (the spatial estimate, or with --variance-batches the sample moments')")
+    ap.add_argument("--frames", type=int, default=0, metavar="N",
+                    help="render N frames of --samples spp each and write out.0000.png ...; with --orbit the camera "
+                         "turns between them (0 = one image, the default)")
+    ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG",
+                    help="with --frames: turn the scene's camera about its look-at point around its up vector by "
+                         "DEG degrees per frame")
+    ap.add_argument("--temporal", action="store_true",
+                    help="with --frames: carry the previous frame's colour and luminance moments into the next "
+                         "camera (temporal accumulation); filtered with --denoise --denoise-mode variance, or "
+                         "written as accumulated without --denoise")
     args = ap.parse_args(argv)
     if args.denoise_iterations is not None:
         if not 0 <= args.denoise_iterations <= 8:
@@ -85,6 +97,23 @@ def parse(argv=None):
                          f"(equal batches), not {args.samples}")
         elif args.state:
             ap.error("--variance-batches with --state needs --interval (every pass is a batch)")
+    if args.frames < 0:
+        ap.error(f"--frames must be >= 0, not {args.frames}")
+    if not args.frames:
+        for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal)):
+            if given:
+                ap.error(f"{flag} needs --frames N")
+    else:
+        clash = [flag for flag, given in (("--interval", args.interval > 0), ("--state", args.state),
+                                          ("--variance-batches", args.variance_batches), ("--hdr", args.hdr),
+                                          ("--aov", args.aov), ("--devices", len(args.devices) != 1)) if given]
+        if clash:
+            ap.error(f"--frames renders whole frames on one device: it cannot be combined with {', '.join(clash)}")
+        if args.samples < 1:
+            ap.error(f"--frames needs --samples >= 1 per frame, not {args.samples}")
+        if args.temporal and args.denoise and args.denoise_mode != "variance":
+            ap.error("--temporal feeds the variance-guided filter: use --denoise --denoise-mode variance, or no "
+                     "--denoise at all")
     if args.hdr and args.hdr.lower().endswith(".npy"):
         # rounds <= 4 took a .npy FILE here; a directory named out.npy would silently replace it
         ap.error(f"--hdr takes a directory (hdr.npy and spp.npy are written into it), not a .npy file: {args.hdr}")
@@ -109,10 +138,48 @@ def _write(args, sums, samples, mean):
         write_png(args.out, to_uint8(as_image(img)))
 
 
+def frame_path(out, t):
+    """--frames: out.png -> out.0000.png for frame t."""
+    root, ext = os.path.splitext(out)
+    return f"{root}.{t:04d}{ext}"
+
+
+def render_frames(args, scene, camera, W, H):
+    """--frames N --orbit DEG [--temporal]: one image per camera; returns the last frame's mean."""
+    from .core.tracing import build_world
+    world = build_world(scene, (args.devices[0],))
+    it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
+    acc = None
+    if args.temporal:
+        acc = TemporalAccumulator(scene, depth=args.depth, spp=args.samples, seed=args.seed, resolution=(W, H),
+                                  device=args.devices[0], world=world, nee=args.nee)
+    mean = None
+    for t in range(args.frames):
+        cam = orbit(camera, t * args.orbit)
+        t0 = time.perf_counter()
+        if acc is not None:
+            acc.add(cam)
+            mean = acc.denoised(iterations=it) if args.denoise else acc.accumulated()
+        else:
+            frame = _Frame.of(scene, cam, depth=args.depth, seed=args.seed, resolution=(W, H),
+                              devices=(args.devices[0],), world=world, nee=args.nee)
+            mean = _mean(frame.unpack(frame.add_samples(t * args.samples, args.samples)), args.samples)
+            if args.denoise:
+                mean = frame.filter(mean, args.denoise_mode, iterations=it)
+        if args.out:
+            img = finish(mean) if args.tonemap == "sqrt" else reinhard_extended(mean)
+            write_png(frame_path(args.out, t), to_uint8(as_image(img)))
+        dt = time.perf_counter() - t0
+        print(f"frame {t}: {t * args.orbit:g} deg, {dt:.2f} s, mean RGB {mean.mean(axis=(0, 1))}", flush=True)
+    return mean
+
+
 def main(argv=None):
     args = parse(argv)
     scene, camera = read_file(args.scene)
     W, H = args.resolution if args.resolution else camera.resolution
+    if args.frames:
+        return render_frames(args, scene, camera, W, H)
     t0 = time.perf_counter()
     if args.interval > 0 or args.state:
         if len(args.devices) != 1:

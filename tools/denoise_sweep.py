@@ -19,6 +19,14 @@ the fixed filter's and the spatial estimate's defaults on those very frames:
 
     python tools/denoise_sweep.py --mode variance --variance-batches 4 8 --spp 4 8 16 32 64 \
         --out profiles/denoise_mom_sweep.txt
+
+--mode temporal sweeps the temporal accumulation's alpha (= alpha_m), tau_z and tau_n on turntables: per
+scene, size and spp an orbit of --frames frames at --orbit degrees per frame about the look-at point.  The
+score of a set is the RMSE of the last frame (temporal accumulation, then the variance-guided filter with
+the spatial fallback) against a --ref-spp render of the last camera, divided by the RMSE of the
+variance-guided filter on the last frame alone at the same per-frame spp:
+
+    python tools/denoise_sweep.py --mode temporal --spp 1 4 --ref-spp 1024 --out profiles/denoise_temporal_sweep.txt
 """
 import argparse
 import itertools
@@ -84,6 +92,83 @@ def sweep_variance(a, frames):
               f"(geometric-mean ratio {g:.4f}, worst frame {max(ratios):.4f})")
 
 
+TEMPORAL_ALPHA = (0.1, 0.2, 0.4)
+TEMPORAL_TAU_Z = (0.01, 0.02, 0.05)
+TEMPORAL_TAU_N = (0.8, 0.9, 0.95)
+
+
+def sweep_temporal(a):
+    """The --mode temporal leg: table and choice for alpha, tau_z, tau_n."""
+    from pyrenderer_amd import denoise as D
+    from pyrenderer_amd.core.camera import orbit
+    from pyrenderer_amd.core.tracing import _Frame, _mean, build_world, render
+    seqs = []   # (name, [(mean, feat, cam record)] per frame, reference, RMSE of the spatial-only filter)
+    for which in ("cornell", "specular"):
+        scene, cam = load(which)
+        world = build_world(scene, (0,))
+        cams = [orbit(cam, a.orbit * t) for t in range(a.frames)]
+        for size in a.sizes:
+            res = (size, size)
+            ref = render(scene, cams[-1], spp=a.ref_spp, depth=a.depth, seed=1, resolution=res, world=world)
+            for spp in a.spp:
+                frames = []
+                for t, c in enumerate(cams):   # frame t: samples t * spp ..., as TemporalAccumulator.add renders it
+                    f = _Frame.of(scene, c, depth=a.depth, seed=2, resolution=res, world=world)
+                    frames.append((_mean(f.unpack(f.add_samples(t * spp, spp)), spp), f.features(), f.cam))
+                alone = D.denoise_variance(frames[-1][0], frames[-1][1], iterations=a.iterations)
+                seqs.append((f"{which}-{size}-{spp}spp", frames, ref, rmse(alone, ref), rmse(frames[-1][0], ref)))
+            print(f"rendered {which} {size}", file=sys.stderr, flush=True)
+
+    def last_frame(frames, **par):
+        prev = None
+        for mean, feat, rec in frames:
+            state, color = D.temporal_accumulate(mean, feat, rec, prev, **par)
+            prev = (state, feat, rec)
+        return D.denoise_variance(color, feat, iterations=a.iterations, variance=state[..., 6],
+                                  variance_fallback="spatial"), state
+
+    rows = []
+    for al, tz, tn in itertools.product(TEMPORAL_ALPHA, TEMPORAL_TAU_Z, TEMPORAL_TAU_N):
+        ratios, shares = [], []
+        for _, frames, ref, e_alone, _ in seqs:
+            img, state = last_frame(frames, alpha=al, alpha_m=al, tau_z=tz, tau_n=tn)
+            hit = frames[-1][1][..., 7] > 0
+            ratios.append(rmse(img, ref) / e_alone)
+            shares.append(float((state[..., 3][hit] > 1).mean()))
+        rows.append((float(np.exp(np.mean(np.log(ratios)))), al, tz, tn, ratios, min(shares)))
+    rows.sort(key=lambda t: t[0])
+    names = [q[0] for q in seqs]
+    n_c = sum(n.startswith("cornell") for n in names)   # the Cornell sequences come first
+    gm = lambda v: float(np.exp(np.mean(np.log(v))))
+    out = sys.stdout if a.out == "-" else open(a.out, "w")
+    print(f"# temporal accumulation parameter sweep: {a.frames} frames at {a.orbit:g} degrees per frame, iterations "
+          f"{a.iterations}, depth {a.depth}, reference {a.ref_spp} spp of the last camera (seed 1), frames seed 2, "
+          f"alpha_m = alpha, tau_a {D.TEMPORAL_TAU_A:g}, min_history {D.TEMPORAL_MIN_HISTORY:g}, w_min {D.TEMPORAL_W_MIN:g}, "
+          f"filter defaults", file=out)
+    print("# last frame, unfiltered RMSE: " + "  ".join(f"{q[0]} {q[4]:.5f}" for q in seqs), file=out)
+    print("# last frame, variance-guided filter alone RMSE: " + "  ".join(f"{q[0]} {q[3]:.5f}" for q in seqs), file=out)
+    print("# columns: geometric-mean ratio, the same over the Cornell sequences, alpha, tau_z, tau_n, least share of hit "
+          "pixels with history in a last frame, then RMSE(temporal + filter) / RMSE(filter alone) of " + " ".join(names),
+          file=out)
+    for g, al, tz, tn, ratios, share in rows:
+        print(f"{g:.4f} {gm(ratios[:n_c]):.4f} {al:g} {tz:g} {tn:g} {share:.4f}  " + " ".join(f"{r:.4f}" for r in ratios),
+              file=out)
+    if out is not sys.stdout:
+        out.close()
+    g, al, tz, tn, ratios, _ = rows[0]
+    print(f"best: alpha {al:g} tau_z {tz:g} tau_n {tn:g} (geometric-mean ratio {g:.4f}, worst sequence {max(ratios):.4f})")
+    safe = [r for r in rows if max(r[4]) < 1.0]
+    if safe:
+        g, al, tz, tn, ratios, _ = safe[0]
+        print(f"best with no sequence worse than the filter alone: alpha {al:g} tau_z {tz:g} tau_n {tn:g} "
+              f"(geometric-mean ratio {g:.4f}, worst sequence {max(ratios):.4f})")
+    else:
+        on_c = sorted((r for r in rows if max(r[4][:n_c]) < 1.0), key=lambda r: gm(r[4][:n_c]))
+        print("no set keeps every sequence below the filter alone" + (
+            f"; on the Cornell sequences alone: alpha {on_c[0][1]:g} tau_z {on_c[0][2]:g} tau_n {on_c[0][3]:g} "
+            f"(geometric-mean ratio {gm(on_c[0][4][:n_c]):.4f}, worst {max(on_c[0][4][:n_c]):.4f})" if on_c else ""))
+
+
 def sweep_moments(a):
     """The --variance-batches leg: per K a table for sigma_l, eps_l, sigma_z with the moments' variance."""
     from pyrenderer_amd import denoise as D
@@ -143,9 +228,11 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=4096)
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--iterations", type=int, default=5)
-    ap.add_argument("--mode", choices=("fixed", "variance"), default="fixed",
+    ap.add_argument("--mode", choices=("fixed", "variance", "temporal"), default="fixed",
                     help="fixed: sigma_c, sigma_z, eps_a, eps_z of denoise(); variance: sigma_l, eps_l, sigma_z of "
-                         "denoise_variance()")
+                         "denoise_variance(); temporal: alpha, tau_z, tau_n of temporal_accumulate() on turntables")
+    ap.add_argument("--frames", type=int, default=8, help="--mode temporal: frames per turntable")
+    ap.add_argument("--orbit", type=float, default=2.0, help="--mode temporal: degrees per frame")
     ap.add_argument("--variance-batches", type=int, nargs="+", default=[], metavar="K",
                     help="with --mode variance: take the variance from K batch means (one section per K)")
     a = ap.parse_args()
@@ -153,6 +240,8 @@ def main():
         if a.mode != "variance" or min(a.variance_batches) < 2:
             ap.error("--variance-batches needs --mode variance and K >= 2")
         return sweep_moments(a)
+    if a.mode == "temporal":
+        return sweep_temporal(a)
     from pyrenderer_amd.core.tracing import build_world, render
     from pyrenderer_amd.denoise import denoise, features
 

@@ -8,6 +8,7 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
     python tools/denoise_time.py --mode moments --sizes 512 4096    # prt_moments_add_device over --frames frames (default 8)
     python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
     python tools/denoise_time.py --mode features --sizes 512 4096   # prt_features_device (1 and 8 samples); host wall clock of both compositions at 512^2
+    python tools/denoise_time.py --temporal --sizes 512 4096        # prt_temporal_accumulate_device, and beside it the filter with and without the spatial fallback
 """
 import argparse
 import json
@@ -31,6 +32,9 @@ def main():
     ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "batching", "features"),
                     default="fixed")
     ap.add_argument("--frames", type=int, default=8, help="--mode moments: n_frames per call")
+    ap.add_argument("--temporal", action="store_true",
+                    help="time the temporal accumulation (a camera turned by 2 degrees) and the variance-guided filter "
+                         "that follows it")
     a = ap.parse_args()
     import torch
     from pyrenderer_amd import denoise as D
@@ -44,6 +48,8 @@ def main():
         return time_batching(a, scene, cam, world)
     if a.mode == "features":
         return time_features(a, cam, world)
+    if a.temporal:
+        return time_temporal(a, scene, cam, world)
     noisy = render(scene, cam, spp=8, depth=8, seed=2, resolution=(base, base), world=world)
     feat = D.features(scene, cam, resolution=(base, base), samples=1, seed=2, world=world)
     dev = torch.device("cuda:0")
@@ -151,6 +157,74 @@ def time_moments(a, size, c, d_f, stream):
                           max_ms=round(ms[-1], 4), reps=a.reps, bytes_total=total,
                           implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
                           hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))), flush=True)
+
+
+def time_temporal(a, scene, cam, world):
+    """prt_temporal_accumulate_device per size: features of the scene's camera and of the camera turned by 2
+    degrees, both rendered at the size itself (the gather follows a real reprojection), an 8-spp colour tiled
+    from 512^2, and the previous state of a first frame.  In the same run the variance-guided filter on the
+    result: with its own estimate, and with the temporal plane and the spatial fallback."""
+    import torch
+    from pyrenderer_amd import denoise as D
+    from pyrenderer_amd.core.camera import orbit
+    from pyrenderer_amd.core.tracing import render
+    base = 512
+    noisy = render(scene, cam, spp=8, depth=8, seed=2, resolution=(base, base), world=world)
+    ds = world.device_scene(0)
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.Stream(dev)
+    turned = orbit(cam, 2.0)
+    for size in a.sizes:
+        k = (size + base - 1) // base
+        n = size * size
+        d_c = torch.from_numpy(np.ascontiguousarray(np.tile(noisy, (k, k, 1))[:size, :size])).to(dev)
+        recs = [c.convert_to_taichi_camera().packed() for c in (cam, turned)]
+        d_feats = [torch.empty((size, size, D.FEATURE_CHANNELS), dtype=torch.float32, device=dev) for _ in recs]
+        for rec, d_f in zip(recs, d_feats):
+            D.features_device(ds, rec, size, size, d_f.data_ptr(), samples=1, seed=2)
+        d_states = [torch.empty((size, size, D.TEMPORAL_CHANNELS), dtype=torch.float32, device=dev) for _ in recs]
+        d_col = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        d_var = torch.empty((size, size), dtype=torch.float32, device=dev)
+        d_out = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
+        need = D.work_bytes_variance(size, size)
+        d_work = torch.empty(need, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        # a first frame with min_history 1 leaves a state whose every hit pixel donates
+        D.temporal_accumulate_device(d_c.data_ptr(), d_feats[0].data_ptr(), recs[0], size, size, d_states[0].data_ptr())
+        torch.cuda.synchronize(dev)
+
+        def temporal():
+            D.temporal_accumulate_device(d_c.data_ptr(), d_feats[1].data_ptr(), recs[1], size, size, d_states[1].data_ptr(),
+                                         d_prev_feat_ptr=d_feats[0].data_ptr(), prev_cam=recs[0],
+                                         d_prev_state_ptr=d_states[0].data_ptr(), d_out_color_ptr=d_col.data_ptr(),
+                                         d_out_var_ptr=d_var.data_ptr(), min_history=1.0, stream_ptr=stream.cuda_stream)
+
+        def filt(**kw):
+            D.denoise_variance_device(d_col.data_ptr(), d_feats[1].data_ptr(), size, size, d_out.data_ptr(),
+                                      d_work.data_ptr(), need, iterations=a.iterations, stream_ptr=stream.cuda_stream, **kw)
+
+        legs = (("temporal_time", temporal, n * 156),
+                ("denoise_var_time", filt, None),
+                ("denoise_var_mixed_time", lambda: filt(d_in_var_ptr=d_var.data_ptr(), variance_fallback="spatial"), None))
+        valid = None
+        for what, run, total in legs:
+            ms = _median_ms(run, stream, a.warmup, a.reps)
+            med = ms[len(ms) // 2]
+            row = dict(what=what, size=size, median_ms=round(med, 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4),
+                       reps=a.reps)
+            if what == "temporal_time":
+                # compulsory traffic: colour 12, features 32, the previous state 32 and features 32 read (each tap
+                # plane once: neighbouring pixels share their taps), state 32, colour 12 and variance 4 written
+                st = d_states[1].cpu().numpy()
+                hit = d_feats[1].cpu().numpy()[..., 7] > 0
+                valid = float((st[..., 3][hit] > 1).mean())
+                row.update(bytes_total=total, implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
+                           hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                           hit_pixels_with_history=round(valid, 4))
+            else:
+                row.update(iterations=a.iterations)
+            print(json.dumps(row), flush=True)
+        del d_c, d_feats, d_states, d_col, d_var, d_out, d_work
 
 
 def time_features(a, cam, world):

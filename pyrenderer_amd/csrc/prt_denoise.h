@@ -12,55 +12,43 @@ namespace prt_dn {
 constexpr int kMaxIterations = 8;
 constexpr int kMaxSide = 32768;   // W, H: the launch grids and the 5-tap reach at step 128 stay in int
 
-struct Params {
-    float sigma_c, sigma_z, eps_a, eps_z;
+// Where the colour edge-stopping width comes from.  kFixed: sigma_c, halved every pass.  The other three are
+// the variance-guided mode, whose width follows the image's own noise: kEstimate takes the variance from
+// the 7 x 7 window, kGiven from the caller's plane d_in_var, and kMixed from that plane where it is finite
+// and >= 0 and from the window elsewhere (SVGF's spatial fallback where a temporal history is too short).
+enum class Mode { kFixed, kEstimate, kGiven, kMixed };
+
+// sigma is sigma_c (kFixed) or sigma_l (the variance-guided modes); eps_l is read by the latter only
+struct FilterParams {
+    float sigma, sigma_z, eps_a, eps_z, eps_l;
 };
 
-// scratch of one W x H frame: two (I.rgb, Z) ping-pong planes and the (N.xyz, class) plane as
-// float4, the depth-gradient plane as float2 — 56 bytes per pixel, rounded up to 256
-size_t work_bytes(int W, int H);
+// Scratch of one W x H frame, rounded up to 256 bytes.  Fixed filter: two (I.rgb, Z) ping-pong planes and
+// the (N.xyz, class) plane as float4, the depth-gradient plane as float2: 56 bytes per pixel.
+// `variance`: the ping-pong planes hold (I.rgb, var) and a float plane holds the depth: 60 bytes per pixel.
+size_t work_bytes(int W, int H, bool variance);
 
-// Enqueue pre-pass, `iterations` a-trous passes and the post-pass on `stream` of the current
-// device.  All pointers are device pointers; d_work holds work_bytes(W, H) bytes, 16-byte aligned.
-// Returns the first launch error.
-hipError_t enqueue(const float* d_color, const float* d_feat, int W, int H, int iterations, const Params& p,
-                   float* d_out, void* d_work, hipStream_t stream);
-
-// ---- variance-guided mode: the colour edge-stopping width follows the image's own noise ----
-struct VarParams {
-    float sigma_l, sigma_z, eps_a, eps_z, eps_l;
-};
-
-// scratch of one W x H frame: two (I.rgb, var) ping-pong planes and the (N.xyz, class) plane as
-// float4, the depth-gradient plane as float2, the depth plane as float — 60 bytes per pixel,
-// rounded up to 256
-size_t var_work_bytes(int W, int H);
-
-// Enqueue pre-pass, variance estimate, `iterations` variance-guided passes and the post-pass on
-// `stream` of the current device.  d_out_var (W x H floats, may be null) receives the variance
-// estimate of the demodulated luminance, before any pass; d_work holds var_work_bytes(W, H) bytes,
-// 16-byte aligned.  Returns the first launch error.
+// Enqueue the pre-pass, the mode's variance step (none for kFixed), `iterations` a-trous passes and the
+// post-pass on `stream` of the current device.  All pointers are device pointers; d_work holds
+// work_bytes(W, H, mode != kFixed) bytes, 16-byte aligned.  Returns the first launch error.
 //
-// d_in_var: null estimates the variance with the 7 x 7 window.  A plane of W x H floats (variance
-// from per-pixel sample moments) stands in its place: at a usable pixel a value that is finite and
-// >= 0 is taken as it is, anything else counts as 0, and d_out_var receives the variance actually
-// used.  d_in_var must not alias d_out or d_out_var.
+// d_out_var (W x H floats, may be null; not read for kFixed) receives the variance of the demodulated
+// luminance that the passes start from, the variance actually used.
+//
+// d_in_var (W x H floats; required for kGiven and kMixed, not read otherwise) is a variance from outside,
+// e.g. from per-pixel sample moments or a temporal state.  At a usable pixel a value that is finite and
+// >= 0 is taken as it is (a -0 too); anything else counts as 0 for kGiven and keeps the window's estimate
+// for kMixed, which the estimate's kernel selects in the same launch.  d_in_var must not alias d_out or
+// d_out_var.
 //
 // Finiteness: the variance planes are always finite (a variance that is not becomes 0, which is
 // what an overflow of l * l, |l| >= 2^64, ends in).  Every colour of a pixel that is not set aside
 // is finite while the demodulated radiance |C_c / fmax(A_c, eps_a)| <= 2^126 and the albedo
 // A_c <= 1: the luminance and the difference of two luminances then stay finite, so no weight is
 // inf / inf, and a weighted mean of such values times the albedo stays in range.
-hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
-                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream);
-
-// enqueue_var with a variance plane that has gaps: the 7 x 7 estimate runs as with a null d_in_var, then
-// one select kernel replaces it at every usable pixel where d_in_var (required) is finite and >= 0;
-// elsewhere the estimate stays (SVGF's spatial fallback where a temporal history is too short).  Scratch,
-// aliasing and finiteness are enqueue_var's; d_out_var receives the variance actually used.
-hipError_t enqueue_var_mixed(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
-                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
-                             hipStream_t stream);
+hipError_t enqueue_filter(Mode mode, const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                          int iterations, const FilterParams& p, float* d_out, float* d_out_var, void* d_work,
+                          hipStream_t stream);
 
 // ---- temporal accumulation ----
 constexpr int kTemporalChannels = 8;   // I.rgb, h, m1, m2, var, 0: two float4 per pixel

@@ -8,7 +8,7 @@
 // Frames are [x][y] with y contiguous (pixel index x * H + y).  One pixel per lane, 64 lanes along
 // y: the 16-byte loads of a tap are contiguous over a wave.  Taps come straight from global memory, except in the variance estimate
 // of the variance-guided mode, which stages its 7 x 7 windows in LDS.  The sample-moments kernels at the
-// end (moments_kernel, var_given_kernel, var_select_kernel) read and write each pixel once and take no taps;
+// end (moments_kernel, var_given_kernel) read and write each pixel once and take no taps;
 // temporal_kernel, the last one, gathers four taps per pixel from the previous frame's planes.
 #include "prt_denoise.h"
 
@@ -28,6 +28,54 @@ __device__ __forceinline__ bool pixel_of_lane(int W, int H, int& x, int& y) {
     return x < W && y < H;
 }
 
+// ---- the per-pixel prologue and epilogue, shared by pre_kernel, moments_kernel, temporal_kernel and post_kernel ----
+struct Rgb {
+    float r, g, b;
+};
+
+__device__ __forceinline__ Rgb load_rgb(const float* c) { return {c[0], c[1], c[2]}; }
+
+__device__ __forceinline__ void store_rgb(float* o, const Rgb& c) {
+    o[0] = c.r;
+    o[1] = c.g;
+    o[2] = c.b;
+}
+
+// the albedo of the features `f` with its floor: what the demodulation divides by
+__device__ __forceinline__ Rgb albedo_floor(const float* f, float eps_a) {
+    return {fmaxf(f[0], eps_a), fmaxf(f[1], eps_a), fmaxf(f[2], eps_a)};
+}
+
+__device__ __forceinline__ Rgb demodulate(const Rgb& c, const Rgb& a) { return {c.r / a.r, c.g / a.g, c.b / a.b}; }
+
+__device__ __forceinline__ Rgb remodulate(const Rgb& i, const Rgb& a) { return {i.r * a.r, i.g * a.g, i.b * a.b}; }
+
+// a finite colour over a tiny albedo may overflow: such a pixel is set aside like a non-finite one,
+// and so is a pixel with a non-finite feature (its weights, as a tap or a centre, would be NaN)
+__device__ __forceinline__ bool set_aside(const Rgb& c, const Rgb& i, const float* f) {
+    bool bad = !(finite_f(c.r) && finite_f(c.g) && finite_f(c.b) && finite_f(i.r) && finite_f(i.g) && finite_f(i.b));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bad = bad || !finite_f(f[j]);
+    return bad;
+}
+
+// A pixel as the filter and the temporal accumulation take it in: colour c, floored albedo a, the colour i
+// demodulated where a surface was hit, and whether the pixel is set aside.
+struct Pixel {
+    Rgb c, a, i;
+    bool hit, bad;
+};
+
+__device__ __forceinline__ Pixel prepare(const float* color3, const float* f, float eps_a) {
+    Pixel px;
+    px.c = load_rgb(color3);
+    px.hit = f[7] > 0.0f;
+    px.a = albedo_floor(f, eps_a);
+    px.i = px.hit ? demodulate(px.c, px.a) : px.c;
+    px.bad = set_aside(px.c, px.i, f);
+    return px;
+}
+
 // pre-pass: demodulate, normalise the normal, depth gradient, classify, repack
 __global__ __launch_bounds__(kBlockX* kBlockY) void pre_kernel(const float* __restrict__ color,
                                                                const float* __restrict__ feat, int W, int H,
@@ -37,19 +85,7 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void pre_kernel(const float* __re
     if (!pixel_of_lane(W, H, x, y)) return;
     const size_t p = (size_t)x * (size_t)H + (size_t)y;
     const float* f = feat + p * 8;
-    const float c0 = color[p * 3], c1 = color[p * 3 + 1], c2 = color[p * 3 + 2];
-    const bool hit = f[7] > 0.0f;
-    float i0 = c0, i1 = c1, i2 = c2;
-    if (hit) {
-        i0 = c0 / fmaxf(f[0], eps_a);
-        i1 = c1 / fmaxf(f[1], eps_a);
-        i2 = c2 / fmaxf(f[2], eps_a);
-    }
-    // a finite colour over a tiny albedo may overflow: such a pixel is set aside like a non-finite one,
-    // and so is a pixel with a non-finite feature (its weights, as a tap or a centre, would be NaN)
-    bool bad = !(finite_f(c0) && finite_f(c1) && finite_f(c2) && finite_f(i0) && finite_f(i1) && finite_f(i2));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bad = bad || !finite_f(f[j]);
+    const Pixel px = prepare(color + p * 3, f, eps_a);
     const float nx = f[3], ny = f[4], nz = f[5];
     const float len = sqrtf((nx * nx + ny * ny) + nz * nz);
     float ux = 0.0f, uy = 0.0f, uz = 0.0f;
@@ -65,8 +101,8 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void pre_kernel(const float* __re
     float gy = 0.5f * (feat[((size_t)x * H + yp) * 8 + 6] - feat[((size_t)x * H + ym) * 8 + 6]);
     if (!finite_f(gx)) gx = 0.0f;
     if (!finite_f(gy)) gy = 0.0f;
-    iz[p] = make_float4(i0, i1, i2, f[6]);
-    nc[p] = make_float4(ux, uy, uz, __uint_as_float((hit ? kHit : 0u) | (bad ? kBad : 0u)));
+    iz[p] = make_float4(px.i.r, px.i.g, px.i.b, f[6]);
+    nc[p] = make_float4(ux, uy, uz, __uint_as_float((px.hit ? kHit : 0u) | (px.bad ? kBad : 0u)));
     grad[p] = make_float2(gx, gy);
 }
 
@@ -198,34 +234,37 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void post_kernel(const float4* __
     if (!pixel_of_lane(W, H, x, y)) return;
     const size_t p = (size_t)x * (size_t)H + (size_t)y;
     const uint32_t cls = __float_as_uint(nc[p].w);
-    float o0, o1, o2;
+    Rgb o;
     if (cls & kBad) {
-        o0 = color[p * 3];
-        o1 = color[p * 3 + 1];
-        o2 = color[p * 3 + 2];
+        o = load_rgb(color + p * 3);
     } else {
         const float4 i = iz[p];
-        o0 = i.x;
-        o1 = i.y;
-        o2 = i.z;
-        if (cls & kHit) {
-            const float* f = feat + p * 8;
-            o0 = o0 * fmaxf(f[0], eps_a);
-            o1 = o1 * fmaxf(f[1], eps_a);
-            o2 = o2 * fmaxf(f[2], eps_a);
-        }
+        o = {i.x, i.y, i.z};
+        if (cls & kHit) o = remodulate(o, albedo_floor(feat + p * 8, eps_a));
     }
-    out[p * 3] = o0;
-    out[p * 3 + 1] = o1;
-    out[p * 3 + 2] = o2;
+    store_rgb(out + p * 3, o);
 }
 
 // ---- variance-guided mode ----
 // The pre-pass, the passes and the post-pass are the ones above.  Between pre and post the colour travels as
 // (I.rgb, var) and the depth in a float plane of its own; tests/atrous_var_ref.py restates the estimate.
 
+// the caller's variance is taken as it is when it is finite and >= 0 (a -0 passes)
+__device__ __forceinline__ bool usable_variance(float t) { return finite_f(t) && t >= 0.0f; }
+
+// the tail of both variance steps: (I.rgb, Z) repacked into (I.rgb, var) and the depth plane, and the
+// variance actually used into the caller's plane, if there is one
+__device__ __forceinline__ void store_repacked(size_t p, const float4& ip, float var, float4* iv, float* zp,
+                                               float* out_var) {
+    iv[p] = make_float4(ip.x, ip.y, ip.z, var);
+    zp[p] = ip.w;
+    if (out_var) out_var[p] = var;
+}
+
 // variance estimate: per hit pixel the weighted second central moment of the luminance over the
-// 7 x 7 window at step 1; repacks (I.rgb, Z) into (I.rgb, var) and the depth plane.  The block's
+// 7 x 7 window at step 1; repacks (I.rgb, Z) into (I.rgb, var) and the depth plane.  With a plane in_var
+// (the mixed mode; null otherwise) a usable pixel whose in_var is a usable variance takes that value in
+// place of the estimate, and every other pixel keeps the estimate.  The block's
 // 10 x 70 neighbourhood (its 4 x 64 pixels and a 3-pixel halo) is staged in LDS as luminance, depth,
 // normal and a "usable" flag (16.8 KB): measured against taps straight from global memory the
 // kernel takes 0.66 of the time at 4096^2.
@@ -234,7 +273,8 @@ constexpr int kTileX = kBlockX + 2 * kHalo, kTileY = kBlockY + 2 * kHalo;
 
 __global__ __launch_bounds__(kBlockX* kBlockY) void var_estimate_kernel(const float4* __restrict__ iz,
                                                                         const float4* __restrict__ nc,
-                                                                        const float2* __restrict__ grad, int W, int H,
+                                                                        const float2* __restrict__ grad,
+                                                                        const float* __restrict__ in_var, int W, int H,
                                                                         float sigma_z, float eps_z,
                                                                         float4* __restrict__ iv, float* __restrict__ zp,
                                                                         float* __restrict__ out_var) {
@@ -296,17 +336,18 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_estimate_kernel(const fl
         const float mu = m1 / sw;
         var = fmaxf(0.0f, m2 / sw - mu * mu);
         if (!finite_f(var)) var = 0.0f;
+        if (in_var) {
+            const float t = in_var[p];
+            if (usable_variance(t)) var = t;
+        }
     }
-    iv[p] = make_float4(ip.x, ip.y, ip.z, var);
-    zp[p] = ip.w;
-    if (out_var) out_var[p] = var;
+    store_repacked(p, ip, var, iv, zp, out_var);
 }
 
 // ---- variance from per-pixel sample moments (tests/moments_ref.py restates both) ----
 
 // given variance: stands where var_estimate_kernel stands.  Repacks (I.rgb, Z) into (I.rgb, v) and the
-// depth plane, with v the caller's variance at a usable pixel when it is finite and >= 0 (a -0 passes
-// as it is), else 0.
+// depth plane, with v the caller's variance at a usable pixel when it is a usable variance, else 0.
 __global__ __launch_bounds__(kBlockX* kBlockY) void var_given_kernel(const float4* __restrict__ iz,
                                                                      const float4* __restrict__ nc,
                                                                      const float* __restrict__ in_var, int W, int H,
@@ -319,27 +360,9 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_given_kernel(const float
     float var = 0.0f;
     if (__float_as_uint(nc[p].w) == kHit) {
         const float t = in_var[p];
-        if (finite_f(t) && t >= 0.0f) var = t;
+        if (usable_variance(t)) var = t;
     }
-    iv[p] = make_float4(ip.x, ip.y, ip.z, var);
-    zp[p] = ip.w;
-    if (out_var) out_var[p] = var;
-}
-
-// mixed variance: after var_estimate_kernel, the caller's variance replaces the estimate at a usable pixel
-// where it is finite and >= 0 (a -0 passes as it is); everywhere else the estimate stays
-__global__ __launch_bounds__(kBlockX* kBlockY) void var_select_kernel(const float4* __restrict__ nc,
-                                                                      const float* __restrict__ in_var, int W, int H,
-                                                                      float4* __restrict__ iv,
-                                                                      float* __restrict__ out_var) {
-    int x, y;
-    if (!pixel_of_lane(W, H, x, y)) return;
-    const size_t p = (size_t)x * (size_t)H + (size_t)y;
-    if (__float_as_uint(nc[p].w) != kHit) return;
-    const float t = in_var[p];
-    if (!(finite_f(t) && t >= 0.0f)) return;
-    reinterpret_cast<float*>(iv + p)[3] = t;
-    if (out_var) out_var[p] = t;
+    store_repacked(p, ip, var, iv, zp, out_var);
 }
 
 // running Welford update of the demodulated luminance of the batch means over n_frames frames of
@@ -353,18 +376,14 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* 
     const size_t p = (size_t)x * (size_t)H + (size_t)y;
     const float* f = feat + p * 8;
     const bool hit = f[7] > 0.0f;
-    const float a0 = fmaxf(f[0], eps_a), a1 = fmaxf(f[1], eps_a), a2 = fmaxf(f[2], eps_a);
+    const Rgb a = albedo_floor(f, eps_a);
     const float4 s = state[p];
     float k = s.x, mean = s.y, m2 = s.z;
     for (int fr = 0; fr < n_frames; ++fr) {
         const float* S = sums + (size_t)fr * frame_pitch + p * 3;
-        float i0 = S[0] / n, i1 = S[1] / n, i2 = S[2] / n;
-        if (hit) {
-            i0 = i0 / a0;
-            i1 = i1 / a1;
-            i2 = i2 / a2;
-        }
-        const float l = lum(i0, i1, i2);
+        Rgb i = {S[0] / n, S[1] / n, S[2] / n};
+        if (hit) i = demodulate(i, a);
+        const float l = lum(i.r, i.g, i.b);
         if (!finite_f(l)) continue;
         k = k + 1.0f;
         const float d = l - mean;
@@ -408,26 +427,13 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
     float F[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) F[j] = feat[p * 8 + j];
-    const float c0 = color[p * 3], c1 = color[p * 3 + 1], c2 = color[p * 3 + 2];
-    const bool hit = F[7] > 0.0f;
-    const float a0 = fmaxf(F[0], P.eps_a), a1 = fmaxf(F[1], P.eps_a), a2 = fmaxf(F[2], P.eps_a);
-    float i0 = c0, i1 = c1, i2 = c2;
-    if (hit) {
-        i0 = c0 / a0;
-        i1 = c1 / a1;
-        i2 = c2 / a2;
-    }
-    bool bad = !(finite_f(c0) && finite_f(c1) && finite_f(c2) && finite_f(i0) && finite_f(i1) && finite_f(i2));
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bad = bad || !finite_f(F[j]);
-    if (bad) {
+    const Pixel px = prepare(color + p * 3, F, P.eps_a);
+    const bool hit = px.hit;
+    const float i0 = px.i.r, i1 = px.i.g, i2 = px.i.b;
+    if (px.bad) {
         state[p * 2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         state[p * 2 + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (out_color) {
-            out_color[p * 3] = c0;
-            out_color[p * 3 + 1] = c1;
-            out_color[p * 3 + 2] = c2;
-        }
+        if (out_color) store_rgb(out_color + p * 3, px.c);
         if (out_var) out_var[p] = marker;
         return;
     }
@@ -528,19 +534,18 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
     state[p * 2] = make_float4(n0, n1, n2, nh);
     state[p * 2 + 1] = make_float4(nm1, nm2, nv, 0.0f);
     if (out_color) {
-        out_color[p * 3] = hit ? n0 * a0 : n0;
-        out_color[p * 3 + 1] = hit ? n1 * a1 : n1;
-        out_color[p * 3 + 2] = hit ? n2 * a2 : n2;
+        const Rgb n = {n0, n1, n2};
+        store_rgb(out_color + p * 3, hit ? remodulate(n, px.a) : n);
     }
     if (out_var) out_var[p] = nv;
 }
 
-// the planes of a frame's scratch, in the order work_bytes / var_work_bytes count them
+// the planes of a frame's scratch, in the order work_bytes counts them
 struct Planes {
     float4* a[2];   // ping-pong (I.rgb, Z) or (I.rgb, var)
     float4* nc;     // (N.xyz, class)
     float2* grad;   // depth gradient
-    float* zp;      // depth; only the variance-guided mode's scratch holds it
+    float* zp;      // depth; only the variance-guided modes' scratch holds it
     Planes(void* d_work, int W, int H, bool variance) {
         const size_t n = (size_t)W * (size_t)H;
         a[0] = static_cast<float4*>(d_work);
@@ -551,108 +556,66 @@ struct Planes {
     }
 };
 
-const dim3 kBlock(kBlockY, kBlockX);
-
-dim3 grid_of(int W, int H) {
-    return dim3((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
-}
-
-// `iterations` passes from s.a[0] and the post-pass; sigma is sigma_c (fixed) or sigma_l (variance-guided)
-template <bool kVar>
-hipError_t passes_and_post(const Planes& s, const float* d_color, const float* d_feat, int W, int H, int iterations,
-                           float sigma, float sigma_z, float eps_a, float eps_z, float eps_l, float* d_out,
-                           hipStream_t stream) {
-    const dim3 grid = grid_of(W, H);
-    int cur = 0;
-    for (int i = 0; i < iterations; ++i) {
-        float sg = sigma;
-        if constexpr (!kVar) {
-            // sigma_c * 2^-i is an exact scaling; its square is one f32 multiplication
-            const float sc = sigma * (1.0f / (float)(1 << i));
-            sg = sc * sc;
-        }
-        pass_kernel<kVar><<<grid, kBlock, 0, stream>>>(s.a[cur], s.a[cur ^ 1], s.nc, s.grad, s.zp, W, H, 1 << i, sg,
-                                                       sigma_z, eps_z, eps_l);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        cur ^= 1;
-    }
-    post_kernel<<<grid, kBlock, 0, stream>>>(s.a[cur], s.nc, d_color, d_feat, W, H, eps_a, d_out);
+// One kernel over the W x H frame on `stream`.  An error left on this thread by earlier, unrelated calls
+// is not ours: it is cleared before the launch, and the launch's own is returned.
+template <typename... Params, typename... Args>
+hipError_t launch(void (*kernel)(Params...), int W, int H, hipStream_t stream, Args... args) {
+    const dim3 grid((unsigned)((H + kBlockY - 1) / kBlockY), (unsigned)((W + kBlockX - 1) / kBlockX));
+    (void)hipGetLastError();
+    kernel<<<grid, dim3(kBlockY, kBlockX), 0, stream>>>(args...);
     return hipGetLastError();
 }
 
-}  // namespace
-
-size_t work_bytes(int W, int H) {
-    const size_t n = (size_t)W * (size_t)H;
-    return (n * 56 + 255) & ~(size_t)255;
-}
-
-hipError_t enqueue(const float* d_color, const float* d_feat, int W, int H, int iterations, const Params& p,
-                   float* d_out, void* d_work, hipStream_t stream) {
-    const Planes s(d_work, W, H, false);
-    (void)hipGetLastError();   // an error left on this thread by earlier, unrelated calls is not ours
-    pre_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, s.a[0], s.nc, s.grad);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return passes_and_post<false>(s, d_color, d_feat, W, H, iterations, p.sigma_c, p.sigma_z, p.eps_a, p.eps_z, 0.0f,
-                                  d_out, stream);
-}
-
-size_t var_work_bytes(int W, int H) {
-    const size_t n = (size_t)W * (size_t)H;
-    return (n * 60 + 255) & ~(size_t)255;
-}
-
-namespace {
-
-// enqueue_var (mixed false) and enqueue_var_mixed
-hipError_t enqueue_var_with(bool mixed, const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
-                            int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
-                            hipStream_t stream) {
-    const Planes s(d_work, W, H, true);
-    const dim3 grid = grid_of(W, H);
-    (void)hipGetLastError();
-    // the pre-pass writes (I.rgb, Z) into the second ping-pong plane; the estimate, or the caller's variance
-    // in its place, repacks it into the first
-    pre_kernel<<<grid, kBlock, 0, stream>>>(d_color, d_feat, W, H, p.eps_a, s.a[1], s.nc, s.grad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (d_in_var && !mixed)
-        var_given_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, d_in_var, W, H, s.a[0], s.zp, d_out_var);
-    else
-        var_estimate_kernel<<<grid, kBlock, 0, stream>>>(s.a[1], s.nc, s.grad, W, H, p.sigma_z, p.eps_z, s.a[0], s.zp,
-                                                         d_out_var);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    if (mixed) {
-        var_select_kernel<<<grid, kBlock, 0, stream>>>(s.nc, d_in_var, W, H, s.a[0], d_out_var);
-        e = hipGetLastError();
+// `iterations` passes from s.a[0] and the post-pass; p.sigma is sigma_c (fixed) or sigma_l (variance-guided)
+template <bool kVar>
+hipError_t passes_and_post(const Planes& s, const float* d_color, const float* d_feat, int W, int H, int iterations,
+                           const FilterParams& p, float* d_out, hipStream_t stream) {
+    int cur = 0;
+    for (int i = 0; i < iterations; ++i) {
+        float sg = p.sigma;
+        if constexpr (!kVar) {
+            // sigma_c * 2^-i is an exact scaling; its square is one f32 multiplication
+            const float sc = p.sigma * (1.0f / (float)(1 << i));
+            sg = sc * sc;
+        }
+        const hipError_t e = launch(pass_kernel<kVar>, W, H, stream, s.a[cur], s.a[cur ^ 1], s.nc, s.grad, s.zp, W, H,
+                                    1 << i, sg, p.sigma_z, p.eps_z, p.eps_l);
         if (e != hipSuccess) return e;
+        cur ^= 1;
     }
-    return passes_and_post<true>(s, d_color, d_feat, W, H, iterations, p.sigma_l, p.sigma_z, p.eps_a, p.eps_z, p.eps_l,
-                                 d_out, stream);
+    return launch(post_kernel, W, H, stream, s.a[cur], s.nc, d_color, d_feat, W, H, p.eps_a, d_out);
 }
 
 }  // namespace
 
-hipError_t enqueue_var(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H, int iterations,
-                       const VarParams& p, float* d_out, float* d_out_var, void* d_work, hipStream_t stream) {
-    return enqueue_var_with(false, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+size_t work_bytes(int W, int H, bool variance) {
+    const size_t n = (size_t)W * (size_t)H;
+    return (n * (variance ? 60 : 56) + 255) & ~(size_t)255;
 }
 
-hipError_t enqueue_var_mixed(const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
-                             int iterations, const VarParams& p, float* d_out, float* d_out_var, void* d_work,
-                             hipStream_t stream) {
-    return enqueue_var_with(true, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+hipError_t enqueue_filter(Mode mode, const float* d_color, const float* d_feat, const float* d_in_var, int W, int H,
+                          int iterations, const FilterParams& p, float* d_out, float* d_out_var, void* d_work,
+                          hipStream_t stream) {
+    const bool variance = mode != Mode::kFixed;
+    const Planes s(d_work, W, H, variance);
+    // The fixed filter's pre-pass writes (I.rgb, Z) where the passes start.  In the variance-guided modes it
+    // writes into the second ping-pong plane, and the variance step repacks that into the first.
+    hipError_t e = launch(pre_kernel, W, H, stream, d_color, d_feat, W, H, p.eps_a, s.a[variance ? 1 : 0], s.nc, s.grad);
+    if (e != hipSuccess) return e;
+    if (!variance) return passes_and_post<false>(s, d_color, d_feat, W, H, iterations, p, d_out, stream);
+    if (mode == Mode::kGiven)
+        e = launch(var_given_kernel, W, H, stream, s.a[1], s.nc, d_in_var, W, H, s.a[0], s.zp, d_out_var);
+    else
+        e = launch(var_estimate_kernel, W, H, stream, s.a[1], s.nc, s.grad, mode == Mode::kMixed ? d_in_var : nullptr, W,
+                   H, p.sigma_z, p.eps_z, s.a[0], s.zp, d_out_var);
+    if (e != hipSuccess) return e;
+    return passes_and_post<true>(s, d_color, d_feat, W, H, iterations, p, d_out, stream);
 }
 
 hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
                            float eps_a, int W, int H, float* d_io_state, hipStream_t stream) {
-    (void)hipGetLastError();
-    moments_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
-                                                         reinterpret_cast<float4*>(d_io_state));
-    return hipGetLastError();
+    return launch(moments_kernel, W, H, stream, d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
+                  reinterpret_cast<float4*>(d_io_state));
 }
 
 hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
@@ -670,12 +633,9 @@ hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const flo
         cams.psh = prev_cam24[17];
         cams.pfd = prev_cam24[18];
     }
-    (void)hipGetLastError();   // an error left on this thread by earlier, unrelated calls is not ours
-    temporal_kernel<<<grid_of(W, H), kBlock, 0, stream>>>(d_color, d_feat, d_prev_feat,
-                                                reinterpret_cast<const float4*>(d_prev_state), cams, W, H,
-                                                is_static ? 1 : 0, p, reinterpret_cast<float4*>(d_state), d_out_color,
-                                                d_out_var);
-    return hipGetLastError();
+    return launch(temporal_kernel, W, H, stream, d_color, d_feat, d_prev_feat,
+                  reinterpret_cast<const float4*>(d_prev_state), cams, W, H, is_static ? 1 : 0, p,
+                  reinterpret_cast<float4*>(d_state), d_out_color, d_out_var);
 }
 
 }  // namespace prt_dn

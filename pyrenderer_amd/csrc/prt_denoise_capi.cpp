@@ -35,28 +35,26 @@ int fail(int code, const std::string& msg) {
         if (rc_ != PRT_OK) return rc_; \
     } while (0)
 
-// Makes `dev` current for its lifetime; `err` is hipSetDevice's result, which the caller checks
-// before it enqueues anything (an invalid ordinal must not run on whatever device was current).
+// The last step before an entry point enqueues anything, and the first that touches HIP: enter() checks the
+// device ordinal against the visible devices (PRT_ERR_HIP without a device, PRT_ERR_ARG out of range; an
+// invalid ordinal must not run on whatever device was current) and makes it current for the guard's lifetime.
 struct DeviceGuard {
     int prev = -1;
-    hipError_t err = hipSuccess;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        err = hipSetDevice(dev);
-    }
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
-// device ordinal against the visible devices: PRT_ERR_HIP without a device, PRT_ERR_ARG out of range
-int check_device(const std::string& who, int device) {
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
-        (void)hipGetLastError();
-        return fail(PRT_ERR_HIP, who + ": no HIP device");
+    int enter(const std::string& who, int device) {
+        int n_dev = 0;
+        if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) {
+            (void)hipGetLastError();
+            return fail(PRT_ERR_HIP, who + ": no HIP device");
+        }
+        if (device >= n_dev) return fail(PRT_ERR_ARG, who + ": no such device");
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        const hipError_t err = hipSetDevice(device);   // its failure keeps the text it has always had
+        if (err != hipSuccess) return fail(PRT_ERR_HIP, std::string("g.err: ") + hipGetErrorString(err));
+        return PRT_OK;
     }
-    if (device >= n_dev) return fail(PRT_ERR_ARG, who + ": no such device");
-    return PRT_OK;
-}
+};
 
 // Device buffers of a host-form entry point, freed when it returns.  The buffers are allocated first,
 // one after the other (after a failure nothing more is allocated and oom() tells); then upload() copies
@@ -115,13 +113,24 @@ int fail_oom(const std::string& who) {
 
 bool positive_finite(float v) { return v > 0.0f && std::isfinite(v); }
 
+// what is wrong with a frame's shape; empty when nothing is
+std::string frame_fault(int W, int H) {
+    if (W < 1 || H < 1) return "W and H must be >= 1";
+    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide) return "W and H must be <= " + std::to_string(prt_dn::kMaxSide);
+    return "";
+}
+
 // device ordinal and frame shape, shared by every entry point
 int check_frame(const std::string& who, int device, int W, int H) {
     if (device < 0) return fail(PRT_ERR_ARG, who + ": device < 0");
-    if (W < 1 || H < 1) return fail(PRT_ERR_ARG, who + ": W and H must be >= 1");
-    if (W > prt_dn::kMaxSide || H > prt_dn::kMaxSide)
-        return fail(PRT_ERR_ARG, who + ": W and H must be <= " + std::to_string(prt_dn::kMaxSide));
+    const std::string fault = frame_fault(W, H);
+    if (!fault.empty()) return fail(PRT_ERR_ARG, who + ": " + fault);
     return PRT_OK;
+}
+
+// the two *_work_bytes exports: 0 for a frame that check_frame refuses, and no error text
+int64_t work_bytes_or_0(int W, int H, bool variance) {
+    return frame_fault(W, H).empty() ? (int64_t)prt_dn::work_bytes(W, H, variance) : 0;
 }
 
 int check_iterations(const std::string& who, int iterations) {
@@ -132,37 +141,30 @@ int check_iterations(const std::string& who, int iterations) {
 
 // shape and parameter checks of the fixed filter's entry points; fills `p`
 int check_args(const std::string& who, int device, int W, int H, int iterations, const float* params4,
-               prt_dn::Params* p) {
+               prt_dn::FilterParams* p) {
     DN_TRY(check_frame(who, device, W, H));
     DN_TRY(check_iterations(who, iterations));
     if (!params4) return fail(PRT_ERR_ARG, who + ": params4 is NULL");
-    p->sigma_c = params4[0];
-    p->sigma_z = params4[1];
-    p->eps_a = params4[2];
-    p->eps_z = params4[3];
-    if (!positive_finite(p->sigma_c) || !positive_finite(p->sigma_z))
+    *p = {params4[0], params4[1], params4[2], params4[3], 0.0f};   // sigma = sigma_c; no eps_l
+    if (!positive_finite(p->sigma) || !positive_finite(p->sigma_z))
         return fail(PRT_ERR_ARG, who + ": sigma_c and sigma_z must be positive and finite");
     if (!positive_finite(p->eps_a) || !positive_finite(p->eps_z))
         return fail(PRT_ERR_ARG, who + ": eps_a and eps_z must be positive and finite");
     // the last pass divides by (sigma_c * 2^-i)^2: it must not underflow to 0 or overflow
-    const float sc_last = p->sigma_c * (1.0f / (float)(1 << (iterations > 0 ? iterations - 1 : 0)));
-    if (!positive_finite(sc_last * sc_last) || !positive_finite(p->sigma_c * p->sigma_c))
+    const float sc_last = p->sigma * (1.0f / (float)(1 << (iterations > 0 ? iterations - 1 : 0)));
+    if (!positive_finite(sc_last * sc_last) || !positive_finite(p->sigma * p->sigma))
         return fail(PRT_ERR_ARG, who + ": sigma_c squared leaves the f32 range");
     return PRT_OK;
 }
 
 // check_args for the variance-guided entry points (params5 = sigma_l, sigma_z, eps_a, eps_z, eps_l)
 int check_var_args(const std::string& who, int device, int W, int H, int iterations, const float* params5,
-                   prt_dn::VarParams* p) {
+                   prt_dn::FilterParams* p) {
     DN_TRY(check_frame(who, device, W, H));
     DN_TRY(check_iterations(who, iterations));
     if (!params5) return fail(PRT_ERR_ARG, who + ": params5 is NULL");
-    p->sigma_l = params5[0];
-    p->sigma_z = params5[1];
-    p->eps_a = params5[2];
-    p->eps_z = params5[3];
-    p->eps_l = params5[4];
-    if (!positive_finite(p->sigma_l) || !positive_finite(p->sigma_z))
+    *p = {params5[0], params5[1], params5[2], params5[3], params5[4]};   // sigma = sigma_l
+    if (!positive_finite(p->sigma) || !positive_finite(p->sigma_z))
         return fail(PRT_ERR_ARG, who + ": sigma_l and sigma_z must be positive and finite");
     if (!positive_finite(p->eps_a) || !positive_finite(p->eps_z) || !positive_finite(p->eps_l))
         return fail(PRT_ERR_ARG, who + ": eps_a, eps_z and eps_l must be positive and finite");
@@ -204,55 +206,56 @@ int check_aliasing(const std::string& who, const float* d_color, const float* d_
     return PRT_OK;
 }
 
-// where the variance-guided filter takes its variance from: its own 7 x 7 estimate, the caller's plane
-// (d_in_var is then required), or the plane where it is finite and >= 0 and the estimate elsewhere
-enum VarSource { kEstimate, kGiven, kMixed };
+using prt_dn::Mode;
 
-hipError_t enqueue_var_from(VarSource src, const float* d_color, const float* d_feat, const float* d_in_var, int W,
-                            int H, int iterations, const prt_dn::VarParams& p, float* d_out, float* d_out_var,
-                            void* d_work, hipStream_t stream) {
-    if (src == kMixed)
-        return prt_dn::enqueue_var_mixed(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
-    return prt_dn::enqueue_var(d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, stream);
+// what a mode's entry points differ in: the fixed filter has no variance planes, and only a given or a
+// mixed variance needs the caller's plane
+bool has_variance(Mode m) { return m != Mode::kFixed; }
+bool needs_plane(Mode m) { return m == Mode::kGiven || m == Mode::kMixed; }
+
+int check_filter_args(const std::string& who, Mode mode, int device, int W, int H, int iterations, const float* params,
+                      prt_dn::FilterParams* p) {
+    return has_variance(mode) ? check_var_args(who, device, W, H, iterations, params, p)
+                              : check_args(who, device, W, H, iterations, params, p);
 }
 
-// prt_denoise_var_device, prt_denoise_var_given_device and prt_denoise_var_mixed_device
-int var_device(const std::string& who, VarSource src, int device, const float* d_color, const float* d_feat,
-               const float* d_in_var, int W, int H, int iterations, const float* params5, float* d_out,
-               float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
-    prt_dn::VarParams p;
-    if (!d_color || !d_feat || (src != kEstimate && !d_in_var) || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
-    DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::var_work_bytes(W, H), "prt_denoise_var_work_bytes"));
+// the device form of all four filters: prt_denoise_device, prt_denoise_var_device, prt_denoise_var_given_device
+// and prt_denoise_var_mixed_device.  d_in_var is null where the mode needs no plane, d_out_var for the fixed filter.
+int filter_device(const std::string& who, Mode mode, int device, const float* d_color, const float* d_feat,
+                  const float* d_in_var, int W, int H, int iterations, const float* params, float* d_out,
+                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
+    prt_dn::FilterParams p;
+    if (!d_color || !d_feat || (needs_plane(mode) && !d_in_var) || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_filter_args(who, mode, device, W, H, iterations, params, &p));
+    DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::work_bytes(W, H, has_variance(mode)),
+                         has_variance(mode) ? "prt_denoise_var_work_bytes" : "prt_denoise_work_bytes"));
     DN_TRY(check_aliasing(who, d_color, d_feat, d_out, d_out_var, d_in_var));
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    DN_HIP_TRY(enqueue_var_from(src, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
-                                static_cast<hipStream_t>(stream)));
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
+    DN_HIP_TRY(prt_dn::enqueue_filter(mode, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work,
+                                      static_cast<hipStream_t>(stream)));
     return PRT_OK;
 }
 
-// prt_denoise_var, prt_denoise_var_given and prt_denoise_var_mixed
-int var_host(const std::string& who, VarSource src, int device, const float* color, const float* feat, const float* in_var,
-             int W, int H, int iterations, const float* params5, float* out, float* out_var) {
-    prt_dn::VarParams p;
-    if (!color || !feat || (src != kEstimate && !in_var) || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_var_args(who, device, W, H, iterations, params5, &p));
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
+// the host form of all four: prt_denoise, prt_denoise_var, prt_denoise_var_given and prt_denoise_var_mixed
+int filter_host(const std::string& who, Mode mode, int device, const float* color, const float* feat, const float* in_var,
+                int W, int H, int iterations, const float* params, float* out, float* out_var) {
+    prt_dn::FilterParams p;
+    if (!color || !feat || (needs_plane(mode) && !in_var) || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_filter_args(who, mode, device, W, H, iterations, params, &p));
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
     const size_t n = (size_t)W * (size_t)H;
     Staging s;
     const float* d_color = s.in(color, n * 3);
     const float* d_feat = s.in(feat, n * 8);
-    const float* d_in_var = src != kEstimate ? s.in(in_var, n) : nullptr;
+    const float* d_in_var = needs_plane(mode) ? s.in(in_var, n) : nullptr;
     float* d_out = s.out(out, n * 3);
     float* d_out_var = s.out(out_var, n);
-    void* d_work = s.bytes(prt_dn::var_work_bytes(W, H));
+    void* d_work = s.bytes(prt_dn::work_bytes(W, H, has_variance(mode)));
     if (s.oom()) return fail_oom(who);
     DN_HIP_TRY(s.upload());
-    DN_HIP_TRY(enqueue_var_from(src, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, nullptr));
+    DN_HIP_TRY(prt_dn::enqueue_filter(mode, d_color, d_feat, d_in_var, W, H, iterations, p, d_out, d_out_var, d_work, nullptr));
     DN_HIP_TRY(s.download());
     return PRT_OK;
 }
@@ -301,63 +304,32 @@ extern "C" {
 
 const char* prt_denoise_last_error(void) { return g_dn_err.c_str(); }
 
-int64_t prt_denoise_work_bytes(int W, int H) {
-    if (W < 1 || H < 1 || W > prt_dn::kMaxSide || H > prt_dn::kMaxSide) return 0;
-    return (int64_t)prt_dn::work_bytes(W, H);
-}
+int64_t prt_denoise_work_bytes(int W, int H) { return work_bytes_or_0(W, H, false); }
 
 int prt_denoise_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
                        const float* params4, float* d_out, void* d_work, int64_t work_bytes, void* stream) {
-    const std::string who("prt_denoise_device");
-    prt_dn::Params p;
-    if (!d_color || !d_feat || !d_out || !d_work) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_args(who, device, W, H, iterations, params4, &p));
-    DN_TRY(check_scratch(who, d_work, work_bytes, prt_dn::work_bytes(W, H), "prt_denoise_work_bytes"));
-    DN_TRY(check_aliasing(who, d_color, d_feat, d_out, nullptr, nullptr));
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    DN_HIP_TRY(prt_dn::enqueue(d_color, d_feat, W, H, iterations, p, d_out, d_work, static_cast<hipStream_t>(stream)));
-    return PRT_OK;
+    return filter_device("prt_denoise_device", Mode::kFixed, device, d_color, d_feat, nullptr, W, H, iterations, params4,
+                         d_out, nullptr, d_work, work_bytes, stream);
 }
 
 int prt_denoise(int device, const float* color, const float* feat, int W, int H, int iterations,
                 const float* params4, float* out) {
-    const std::string who("prt_denoise");
-    prt_dn::Params p;
-    if (!color || !feat || !out) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_args(who, device, W, H, iterations, params4, &p));
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
-    const size_t n = (size_t)W * (size_t)H;
-    Staging s;
-    const float* d_color = s.in(color, n * 3);
-    const float* d_feat = s.in(feat, n * 8);
-    float* d_out = s.out(out, n * 3);
-    void* d_work = s.bytes(prt_dn::work_bytes(W, H));
-    if (s.oom()) return fail_oom(who);
-    DN_HIP_TRY(s.upload());
-    DN_HIP_TRY(prt_dn::enqueue(d_color, d_feat, W, H, iterations, p, d_out, d_work, nullptr));
-    DN_HIP_TRY(s.download());
-    return PRT_OK;
+    return filter_host("prt_denoise", Mode::kFixed, device, color, feat, nullptr, W, H, iterations, params4, out, nullptr);
 }
 
-int64_t prt_denoise_var_work_bytes(int W, int H) {
-    if (W < 1 || H < 1 || W > prt_dn::kMaxSide || H > prt_dn::kMaxSide) return 0;
-    return (int64_t)prt_dn::var_work_bytes(W, H);
-}
+int64_t prt_denoise_var_work_bytes(int W, int H) { return work_bytes_or_0(W, H, true); }
 
 int prt_denoise_var_device(int device, const float* d_color, const float* d_feat, int W, int H, int iterations,
                            const float* params5, float* d_out, float* d_out_var, void* d_work, int64_t work_bytes,
                            void* stream) {
-    return var_device("prt_denoise_var_device", kEstimate, device, d_color, d_feat, nullptr, W, H, iterations, params5,
-                      d_out, d_out_var, d_work, work_bytes, stream);
+    return filter_device("prt_denoise_var_device", Mode::kEstimate, device, d_color, d_feat, nullptr, W, H, iterations,
+                         params5, d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var(int device, const float* color, const float* feat, int W, int H, int iterations,
                     const float* params5, float* out, float* out_var) {
-    return var_host("prt_denoise_var", kEstimate, device, color, feat, nullptr, W, H, iterations, params5, out, out_var);
+    return filter_host("prt_denoise_var", Mode::kEstimate, device, color, feat, nullptr, W, H, iterations, params5, out,
+                       out_var);
 }
 
 // ---- variance from per-pixel sample moments ----
@@ -365,14 +337,14 @@ int prt_denoise_var(int device, const float* color, const float* feat, int W, in
 int prt_denoise_var_given_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
-    return var_device("prt_denoise_var_given_device", kGiven, device, d_color, d_feat, d_in_var, W, H, iterations,
-                      params5, d_out, d_out_var, d_work, work_bytes, stream);
+    return filter_device("prt_denoise_var_given_device", Mode::kGiven, device, d_color, d_feat, d_in_var, W, H, iterations,
+                         params5, d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var_given(int device, const float* color, const float* feat, const float* in_var, int W, int H,
                           int iterations, const float* params5, float* out, float* out_var) {
-    return var_host("prt_denoise_var_given", kGiven, device, color, feat, in_var, W, H, iterations, params5, out,
-                    out_var);
+    return filter_host("prt_denoise_var_given", Mode::kGiven, device, color, feat, in_var, W, H, iterations, params5, out,
+                       out_var);
 }
 
 int prt_moments_add_device(int device, const float* d_sums, int n_frames, int64_t frame_pitch, float n_samples,
@@ -382,9 +354,8 @@ int prt_moments_add_device(int device, const float* d_sums, int n_frames, int64_
     DN_TRY(check_moments_args(who, device, n_frames, &frame_pitch, n_samples, eps_a, W, H));
     if (reinterpret_cast<uintptr_t>(d_io_state) % 16 != 0)
         return fail(PRT_ERR_ARG, who + ": d_io_state must be 16-byte aligned");
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
     DN_HIP_TRY(prt_dn::enqueue_moments(d_sums, n_frames, (size_t)frame_pitch, n_samples, d_feat, eps_a, W, H, d_io_state,
                                        static_cast<hipStream_t>(stream)));
     return PRT_OK;
@@ -395,9 +366,8 @@ int prt_moments_add(int device, const float* sums, int n_frames, int64_t frame_p
     const std::string who("prt_moments_add");
     if (!sums || !feat || !io_state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
     DN_TRY(check_moments_args(who, device, n_frames, &frame_pitch, n_samples, eps_a, W, H));
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
     const size_t n = (size_t)W * (size_t)H;
     Staging s;
     // the frames as they lie in the caller's memory, gaps of a pitch included
@@ -417,13 +387,13 @@ int prt_moments_add(int device, const float* sums, int n_frames, int64_t frame_p
 int prt_denoise_var_mixed_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream) {
-    return var_device("prt_denoise_var_mixed_device", kMixed, device, d_color, d_feat, d_in_var, W, H, iterations,
+    return filter_device("prt_denoise_var_mixed_device", Mode::kMixed, device, d_color, d_feat, d_in_var, W, H, iterations,
                       params5, d_out, d_out_var, d_work, work_bytes, stream);
 }
 
 int prt_denoise_var_mixed(int device, const float* color, const float* feat, const float* in_var, int W, int H,
                           int iterations, const float* params5, float* out, float* out_var) {
-    return var_host("prt_denoise_var_mixed", kMixed, device, color, feat, in_var, W, H, iterations, params5, out,
+    return filter_host("prt_denoise_var_mixed", Mode::kMixed, device, color, feat, in_var, W, H, iterations, params5, out,
                     out_var);
 }
 
@@ -453,9 +423,8 @@ int prt_temporal_accumulate_device(int device, const float* d_color, const float
         for (int j = 0; j < i; ++j)
             if (outs[i] == outs[j]) return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias each other");
     }
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
     DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static,
                                         p, d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
     return PRT_OK;
@@ -471,9 +440,8 @@ int prt_temporal_accumulate(int device, const float* color, const float* feat, c
     DN_TRY(check_temporal_params(who, device, W, H, params8, &p));
     DN_TRY(check_temporal_cameras(who, cam24, prev_feat, prev_cam24, prev_state, &is_static));
     if (state == prev_state) return fail(PRT_ERR_ARG, who + ": state must not alias prev_state");
-    DN_TRY(check_device(who, device));
-    DeviceGuard g(device);
-    DN_HIP_TRY(g.err);
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
     const size_t n = (size_t)W * (size_t)H;
     Staging s;
     const float* d_color = s.in(color, n * 3);

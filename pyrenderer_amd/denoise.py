@@ -185,6 +185,15 @@ def _check_fallback(variance_fallback, has_plane):
         raise ValueError("variance_fallback='spatial' needs a variance plane to fall back from")
 
 
+def _variance_entry(has_plane, variance_fallback, form=""):
+    """The variance-guided filter's entry point of `form` ("" or "_device"): prt_denoise_var without a
+    variance plane, with one prt_denoise_var_mixed for the "spatial" fallback and prt_denoise_var_given else."""
+    stem = "prt_denoise_var"
+    if has_plane:
+        stem += "_mixed" if variance_fallback == "spatial" else "_given"
+    return getattr(N.lib(), stem + form)
+
+
 def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, sigma_z=VAR_SIGMA_Z, eps_a=EPS_A,
                      eps_z=EPS_Z, eps_l=VAR_EPS_L, device=0, return_variance=False, variance=None,
                      variance_fallback="zero"):
@@ -209,13 +218,13 @@ def denoise_variance(mean, feat, *, iterations=ITERATIONS, sigma_l=VAR_SIGMA_L, 
     out = np.zeros_like(mean)
     var = np.zeros((W, H), np.float32) if return_variance else None
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
-    fn, given = N.lib().prt_denoise_var, []
+    given = []
     if variance is not None:
         plane = np.ascontiguousarray(variance, np.float32)
         if plane.shape != (W, H):
             raise ValueError(f"variance must be {(W, H)}, not {plane.shape}")
-        fn = N.lib().prt_denoise_var_mixed if variance_fallback == "spatial" else N.lib().prt_denoise_var_given
         given = [N.ptr(plane)]
+    fn = _variance_entry(variance is not None, variance_fallback)
     N.check_denoise(fn(int(device), N.ptr(mean), N.ptr(feat), *given, W, H, int(iterations), N.ptr(par), N.ptr(out),
                        N.ptr(var)))
     return (out, var) if return_variance else out
@@ -250,11 +259,8 @@ def denoise_variance_device(d_color_ptr, d_feat_ptr, W, H, d_out_ptr, d_work_ptr
     7 x 7 estimate where that plane is not finite and >= 0 (prt_denoise_var_mixed_device)."""
     _check_fallback(variance_fallback, bool(d_in_var_ptr))
     par = _params_variance(sigma_l, sigma_z, eps_a, eps_z, eps_l)
-    fn, given = N.lib().prt_denoise_var_device, []
-    if d_in_var_ptr:
-        fn = (N.lib().prt_denoise_var_mixed_device if variance_fallback == "spatial"
-              else N.lib().prt_denoise_var_given_device)
-        given = [_vp(d_in_var_ptr)]
+    fn = _variance_entry(bool(d_in_var_ptr), variance_fallback, "_device")
+    given = [_vp(d_in_var_ptr)] if d_in_var_ptr else []
     N.check_denoise(fn(int(device), _vp(d_color_ptr), _vp(d_feat_ptr), *given, int(W), int(H), int(iterations),
                        N.ptr(par), _vp(d_out_ptr), _vp(d_out_var_ptr), _vp(d_work_ptr), int(n_work_bytes),
                        _vp(stream_ptr)))

@@ -1,5 +1,5 @@
 """NumPy float32 restatement of the temporal accumulation (pyrenderer_amd/csrc/prt_denoise.hip:
-temporal_kernel) and of the mixed variance select (var_select_kernel).
+temporal_kernel) and of the mixed variance select (the in_var branch of var_estimate_kernel).
 
 A helper module like moments_ref.py.  `accumulate(color, feat, cam, prev, ...)` returns what
 prt_temporal_accumulate leaves in state, out_color and out_var, and `atrous_var_mixed(color, feat, in_var,
@@ -168,7 +168,7 @@ def accumulate(color, feat, cam, prev=None, *, alpha=0.2, alpha_m=0.2, tau_n=0.9
 
 
 def mixed(in_var, estimate, live):
-    """var_select_kernel after var_estimate_kernel: the variance plane the passes start from."""
+    """var_estimate_kernel with a plane in_var: the variance plane the passes start from."""
     t = np.ascontiguousarray(in_var, F32)
     with np.errstate(all="ignore"):
         return np.where(live & np.isfinite(t) & (t >= 0), t, estimate).astype(F32)

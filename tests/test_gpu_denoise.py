@@ -1,63 +1,16 @@
 """The a-trous denoiser on the GPU: prt_denoise against the NumPy restatement bit for bit, the
 device entry point, the feature buffers against the oracle, the quality gain, and the public API."""
-import json
-import os
-
 import numpy as np
 import pytest
 
 import atrous_ref as R
-from conftest import CORNELL_JSON, ROOT
+from denoise_cases import bits, gap_soup, hostile_inputs, reference, rmse
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 # non-default parameters for the bit-identity cases, so every term of the weight is at work
 PAR = dict(sigma_c=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3)
-
-
-def _inputs(W, H, seed):
-    """Random finite inputs with every special case the filter distinguishes: unit normals and a few
-    zero normals, a depth ramp, a block of miss pixels, albedos below eps_a, a NaN and a +inf pixel, and (from
-    100 pixels on) a NaN depth and an inf normal."""
-    rng = np.random.default_rng(seed)
-    F = np.zeros((W, H, 8), F32)
-    F[..., 0:3] = rng.uniform(0.02, 1.0, (W, H, 3))
-    # noisy irradiance around 1 times the albedo: the colour weights are neither all 0 nor all 1
-    C = (F[..., 0:3] * rng.uniform(0.4, 1.6, (W, H, 3))).astype(F32)
-    n = rng.normal(size=(W, H, 3))
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    # a few directions only, so many taps have parallel normals and non-zero weights
-    n = np.where(rng.uniform(size=(W, H, 1)) < 0.7, np.array([0.0, 0.6, 0.8]), n)
-    F[..., 3:6] = n
-    F[..., 6] = 1.5 + 0.03 * np.arange(W)[:, None] + 0.011 * np.arange(H)[None, :] + rng.uniform(0, 0.01, (W, H))
-    F[..., 7] = rng.choice([0.25, 0.5, 1.0], (W, H))
-    idx = rng.permutation(W * H)
-    for k in idx[: max(1, W * H // 20)]:        # zero normals
-        F[k // H, k % H, 3:6] = 0.0
-    for k in idx[W * H // 20: W * H // 10 + 1]:  # albedos below eps_a, one channel exactly 0
-        F[k // H, k % H, 0:3] = (1e-3, 0.0, 5e-3)
-    if W * H > 1:                                # a block of miss pixels, as features() writes them
-        x0, y0 = W // 3, H // 4
-        F[x0:x0 + max(1, W // 4), y0:y0 + max(1, H // 3)] = 0.0
-        C[x0, y0] = (0.3, 0.2, 0.1)              # the background has a colour of its own
-    bad = []
-    if W * H >= 4:
-        hits = np.argwhere(F[..., 7] > 0)
-        (ax, ay), (bx, by) = hits[len(hits) // 3], hits[2 * len(hits) // 3]
-        C[ax, ay, 1] = np.nan
-        C[bx, by, 2] = np.inf
-        bad = [(ax, ay), (bx, by)]
-    if W * H >= 100:                             # non-finite features: a NaN depth, an inf normal
-        (cx, cy), (dx, dy) = hits[len(hits) // 5], hits[4 * len(hits) // 5]
-        F[cx, cy, 6] = np.nan
-        F[dx, dy, 3] = np.inf
-        bad += [(cx, cy), (dx, dy)]
-    return C, F, bad
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 _CASES = [(1, 1, 5), (5, 3, 5), (33, 17, 4), (70, 130, 5)]
@@ -68,7 +21,7 @@ def restated():
     """Inputs and the restatement's output of every shape, computed once and left unchanged."""
     out = {}
     for W, H, n in _CASES:
-        C, F, bad = _inputs(W, H, 100 + W)
+        C, F, bad = hostile_inputs(W, H, 100 + W, "uniform")
         out[(W, H)] = (C, F, bad, n, R.atrous(C, F, n, **PAR))
     return out
 
@@ -79,18 +32,18 @@ def test_filter_equals_the_restatement_bit_for_bit(restated, W, H):
     C, F, bad, n, want = restated[(W, H)]
     got = denoise(C, F, iterations=n, **PAR)
     again = denoise(C, F, iterations=n, **PAR)
-    assert np.array_equal(_bits(got), _bits(again))
-    diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+    assert np.array_equal(bits(got), bits(again))
+    diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
     assert len(diff) == 0, (len(diff), diff[:5])
     ok = np.ones((W, H), bool)
     for x, y in bad:
         ok[x, y] = False
-        assert np.array_equal(_bits(got[x, y]), _bits(C[x, y]))
+        assert np.array_equal(bits(got[x, y]), bits(C[x, y]))
     assert np.isfinite(got[ok]).all()
     miss = ~(F[..., 7] > 0)
     if W * H > 1:
         assert miss.any() and (~miss).any()
-    assert np.array_equal(_bits(got[miss]), _bits(C[miss]))
+    assert np.array_equal(bits(got[miss]), bits(C[miss]))
     if W * H > 100:   # the filter did something: most surviving hit pixels changed
         assert np.mean(np.any(got[ok & ~miss] != C[ok & ~miss], axis=-1)) > 0.6
 
@@ -99,7 +52,7 @@ def test_filter_equals_the_restatement_bit_for_bit(restated, W, H):
 def test_iteration_counts_at_the_ends_of_the_range(restated, n):
     from pyrenderer_amd.denoise import denoise
     C, F, _, _, _ = restated[(33, 17)]
-    assert np.array_equal(_bits(denoise(C, F, iterations=n, **PAR)), _bits(R.atrous(C, F, n, **PAR)))
+    assert np.array_equal(bits(denoise(C, F, iterations=n, **PAR)), bits(R.atrous(C, F, n, **PAR)))
 
 
 def test_device_entry_point_on_a_side_stream(restated):
@@ -120,8 +73,8 @@ def test_device_entry_point_on_a_side_stream(restated):
                      stream_ptr=stream.cuda_stream, **PAR)
     stream.synchronize()
     got = d_out.cpu().numpy()
-    assert np.array_equal(_bits(got), _bits(D.denoise(C, F, iterations=n, **PAR)))
-    assert np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(bits(got), bits(D.denoise(C, F, iterations=n, **PAR)))
+    assert np.array_equal(bits(got), bits(want))
 
 
 # ---------------------------------------------------------------- features ----
@@ -134,28 +87,6 @@ class _World:
 
     def device_scene(self, device=0):
         return self.ds
-
-
-def _gap_soup(cornell, n_tri=60, seed=9):
-    """Scattered triangles in front of the Cornell camera plus the box's light, nothing else: many
-    primary rays pass between them and miss."""
-    from pyrenderer_amd.flatten import FlatScene
-    f = cornell[2]
-    rng = np.random.default_rng(seed)
-    c = np.stack([rng.uniform(-0.9, 0.9, n_tri), rng.uniform(0.05, 1.8, n_tri), rng.uniform(-0.9, 0.9, n_tri)], 1)
-    tv = (c[:, None, :] + rng.normal(0, 0.12, (n_tri, 3, 3))).astype(F32).reshape(-1, 9)
-    nn = np.cross((tv[:, 3:6] - tv[:, 0:3]).astype(np.float64), (tv[:, 6:9] - tv[:, 0:3]).astype(np.float64))
-    nn = (nn / np.linalg.norm(nn, axis=1, keepdims=True)).astype(F32)
-    lt = f.light_tri
-    tri_v = np.concatenate([tv, f.tri_v[lt]])
-    tri_n = np.concatenate([nn, f.tri_n[lt]])
-    tri_mat = np.concatenate([np.zeros(n_tri, np.int32), f.tri_mat[lt]])
-    tri_prim = np.concatenate([np.zeros(n_tri, np.int32), np.ones(len(lt), np.int32)])
-    lv = f.tri_v[lt].reshape(-1, 3)
-    lo = np.stack([tv.reshape(-1, 3).min(0), lv.min(0)])
-    hi = np.stack([tv.reshape(-1, 3).max(0), lv.max(0)])
-    return FlatScene(tri_v, tri_n, tri_mat, tri_prim, lo, hi, f.mat, n_tri + np.arange(len(lt), dtype=np.int32),
-                     f.light_off, f.direct_rgb)
 
 
 def _expected_features(ds, osc, cam, W, H, tile, samples, seed):
@@ -199,12 +130,12 @@ def test_features_equal_the_oracle_composition(cornell, gpu_scene, oracle_scene,
     if which == "cornell":
         ds, osc = gpu_scene, oracle_scene
     else:
-        flat = _gap_soup(cornell)
+        flat = gap_soup(cornell)
         ds, osc = DeviceScene(flat, 0), O.OracleScene.from_flat(flat)
     got = features(None, cam, resolution=(W, H), samples=samples, seed=seed, tile=tile, world=_World(ds))
     want = _expected_features(ds, osc, cam.convert_to_taichi_camera().packed(), W, H, tile, samples, seed)
     assert got.shape == (W, H, 8) and got.dtype == F32
-    assert np.array_equal(_bits(got), _bits(want)), np.argwhere(np.any(got != want, axis=-1))[:5]
+    assert np.array_equal(bits(got), bits(want)), np.argwhere(np.any(got != want, axis=-1))[:5]
     hit = got[..., 7] > 0
     if which == "soup":
         assert hit.any() and (~hit).any(), (int(hit.sum()), hit.size)
@@ -218,7 +149,7 @@ def test_features_equal_the_oracle_composition(cornell, gpu_scene, oracle_scene,
     from pyrenderer_amd.denoise import features_packed
     small = features_packed(ds, cam.convert_to_taichi_camera().packed(), W, H, samples=samples, seed=seed, tile=tile,
                             chunk_rays=2 * tile * tile)
-    assert np.array_equal(_bits(small), _bits(got))
+    assert np.array_equal(bits(small), bits(got))
     if which == "soup":
         ds.close()
 
@@ -232,30 +163,16 @@ def test_features_equal_the_oracle_composition(cornell, gpu_scene, oracle_scene,
 RHO = {"cornell": 0.4273, "specular": 0.4274}
 
 
-def _rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b) ** 2)))
-
-
-def _load(which):
-    from pyrenderer_amd.io_utils.read_tungsten import process_primitives, read_file
-    if which == "cornell":
-        return read_file(CORNELL_JSON)
-    d = json.load(open(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene_specular.json")))
-    return process_primitives(d)
-
-
 @pytest.mark.parametrize("which", ["cornell", "specular"])
 def test_it_denoises(which):
-    from pyrenderer_amd.core.tracing import build_world, render
+    from pyrenderer_amd.core.tracing import render
     from pyrenderer_amd.denoise import denoise, features
-    scene, cam = _load(which)
-    world = build_world(scene, (0,))
+    scene, cam, world, ref = reference(which)
     res = (128, 128)
-    ref = render(scene, cam, spp=4096, depth=8, seed=1, resolution=res, world=world)
     noisy = render(scene, cam, spp=8, depth=8, seed=2, resolution=res, world=world)
     feat = features(scene, cam, resolution=res, samples=1, seed=2, world=world)
     den = denoise(noisy, feat)
-    e_noisy, e_den = _rmse(noisy, ref), _rmse(den, ref)
+    e_noisy, e_den = rmse(noisy, ref), rmse(den, ref)
     print(f"denoise quality {which}: rmse noisy {e_noisy:.6f} denoised {e_den:.6f} ratio {e_den / e_noisy:.4f}")
     assert np.isfinite(den).all()
     assert e_den < e_noisy, (e_den, e_noisy)
@@ -271,12 +188,12 @@ def test_public_entry_points_agree(cornell):
     world = build_world(scene, (0,))
     kw = dict(depth=4, seed=3, resolution=(48, 40), world=world)
     plain = render(scene, cam, spp=4, **kw)
-    assert np.array_equal(_bits(render(scene, cam, spp=4, denoise=False, **kw)), _bits(plain))
+    assert np.array_equal(bits(render(scene, cam, spp=4, denoise=False, **kw)), bits(plain))
     a = render(scene, cam, spp=4, denoise=True, **kw)
     b = denoise(plain, features(scene, cam, resolution=(48, 40), samples=1, seed=3, world=world))
     acc = Accumulator(scene, cam, **kw)
     acc.add(3).add(1)
     c = acc.denoised()
-    assert np.array_equal(_bits(acc.mean()), _bits(plain))
-    assert np.array_equal(_bits(a), _bits(b)) and np.array_equal(_bits(a), _bits(c))
+    assert np.array_equal(bits(acc.mean()), bits(plain))
+    assert np.array_equal(bits(a), bits(b)) and np.array_equal(bits(a), bits(c))
     assert not np.array_equal(a, plain) and np.isfinite(a).all()

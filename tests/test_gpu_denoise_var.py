@@ -1,63 +1,18 @@
 """The variance-guided a-trous mode on the GPU: prt_denoise_var against the NumPy restatement bit
 for bit (image and variance estimate), the device entry point, the public API and the quality gain."""
-import json
 import os
 
 import numpy as np
 import pytest
 
 import atrous_var_ref as V
-from conftest import CORNELL_JSON, ROOT
+from denoise_cases import bits, hostile_inputs, reference, rmse
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 # non-default parameters for the bit-identity cases, so every term of the weight is at work
 PAR = dict(sigma_l=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3, eps_l=3e-3)
-
-
-def _inputs(W, H, seed):
-    """The recipe of test_gpu_denoise._inputs — unit normals and a few zero normals, a depth ramp, a
-    block of miss pixels, albedos below eps_a, a NaN and a +inf colour and (from 100 pixels on) a NaN
-    depth and an inf normal — with a noise amplitude that differs between the two halves of the frame
-    (0.05 for x < W / 2, 0.6 beyond)."""
-    rng = np.random.default_rng(seed)
-    F = np.zeros((W, H, 8), F32)
-    F[..., 0:3] = rng.uniform(0.02, 1.0, (W, H, 3))
-    amp = np.where(np.arange(W)[:, None, None] < (W + 1) // 2, 0.05, 0.6)
-    C = (F[..., 0:3] * (1.0 + amp * rng.uniform(-1.0, 1.0, (W, H, 3)))).astype(F32)
-    n = rng.normal(size=(W, H, 3))
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    n = np.where(rng.uniform(size=(W, H, 1)) < 0.7, np.array([0.0, 0.6, 0.8]), n)
-    F[..., 3:6] = n
-    F[..., 6] = 1.5 + 0.03 * np.arange(W)[:, None] + 0.011 * np.arange(H)[None, :] + rng.uniform(0, 0.01, (W, H))
-    F[..., 7] = rng.choice([0.25, 0.5, 1.0], (W, H))
-    idx = rng.permutation(W * H)
-    for k in idx[: max(1, W * H // 20)]:        # zero normals
-        F[k // H, k % H, 3:6] = 0.0
-    for k in idx[W * H // 20: W * H // 10 + 1]:  # albedos below eps_a, one channel exactly 0
-        F[k // H, k % H, 0:3] = (1e-3, 0.0, 5e-3)
-    if W * H > 1:                                # a block of miss pixels, as features() writes them
-        x0, y0 = W // 3, H // 4
-        F[x0:x0 + max(1, W // 4), y0:y0 + max(1, H // 3)] = 0.0
-        C[x0, y0] = (0.3, 0.2, 0.1)
-    bad = []
-    if W * H >= 4:
-        hits = np.argwhere(F[..., 7] > 0)
-        (ax, ay), (bx, by) = hits[len(hits) // 3], hits[2 * len(hits) // 3]
-        C[ax, ay, 1] = np.nan
-        C[bx, by, 2] = np.inf
-        bad = [(ax, ay), (bx, by)]
-    if W * H >= 100:                             # non-finite features: a NaN depth, an inf normal
-        (cx, cy), (dx, dy) = hits[len(hits) // 5], hits[4 * len(hits) // 5]
-        F[cx, cy, 6] = np.nan
-        F[dx, dy, 3] = np.inf
-        bad += [(cx, cy), (dx, dy)]
-    return C, F, bad
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 # 3 x 7 is narrower than the 7 x 7 window and the 5 x 5 stencil; 70 x 130 crosses the 64-lane and
@@ -70,7 +25,7 @@ def restated():
     """Inputs and the restatement's outputs of every shape, computed once and left unchanged."""
     out = {}
     for W, H, n in _CASES:
-        C, F, bad = _inputs(W, H, 200 + W)
+        C, F, bad = hostile_inputs(W, H, 200 + W, "halves")
         out[(W, H)] = (C, F, bad, n) + V.atrous_var(C, F, n, **PAR)
     return out
 
@@ -81,22 +36,22 @@ def test_filter_equals_the_restatement_bit_for_bit(restated, W, H):
     C, F, bad, n, want, want_var = restated[(W, H)]
     got, var = denoise_variance(C, F, iterations=n, return_variance=True, **PAR)
     again, var2 = denoise_variance(C, F, iterations=n, return_variance=True, **PAR)
-    assert np.array_equal(_bits(got), _bits(again)) and np.array_equal(_bits(var), _bits(var2))
+    assert np.array_equal(bits(got), bits(again)) and np.array_equal(bits(var), bits(var2))
     assert var.shape == (W, H) and var.dtype == F32
-    diff = np.argwhere(_bits(var) != _bits(want_var))
+    diff = np.argwhere(bits(var) != bits(want_var))
     assert len(diff) == 0, ("variance", len(diff), diff[:5])
-    diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+    diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
     assert len(diff) == 0, ("image", len(diff), diff[:5])
-    assert np.array_equal(_bits(got), _bits(denoise_variance(C, F, iterations=n, **PAR)))   # without out_var
+    assert np.array_equal(bits(got), bits(denoise_variance(C, F, iterations=n, **PAR)))   # without out_var
     ok = np.ones((W, H), bool)
     for x, y in bad:
         ok[x, y] = False
-        assert np.array_equal(_bits(got[x, y]), _bits(C[x, y])) and var[x, y] == 0
+        assert np.array_equal(bits(got[x, y]), bits(C[x, y])) and var[x, y] == 0
     assert np.isfinite(got[ok]).all() and np.isfinite(var).all() and (var >= 0).all()
     miss = ~(F[..., 7] > 0)
     if W * H > 1:
         assert miss.any() and (~miss).any()
-    assert np.array_equal(_bits(got[miss]), _bits(C[miss])) and not var[miss].any()
+    assert np.array_equal(bits(got[miss]), bits(C[miss])) and not var[miss].any()
     if W * H > 100:   # the filter did something, and the estimate is at work
         assert np.mean(np.any(got[ok & ~miss] != C[ok & ~miss], axis=-1)) > 0.6
         assert np.mean(var[ok & ~miss] > 0) > 0.6
@@ -107,8 +62,8 @@ def test_iteration_counts_at_the_ends_of_the_range(restated, n):
     from pyrenderer_amd.denoise import denoise_variance
     C, F, _, _, _, want_var = restated[(33, 17)]
     got, var = denoise_variance(C, F, iterations=n, return_variance=True, **PAR)
-    assert np.array_equal(_bits(got), _bits(V.atrous_var(C, F, n, **PAR)[0]))
-    assert np.array_equal(_bits(var), _bits(want_var))   # the estimate precedes the passes
+    assert np.array_equal(bits(got), bits(V.atrous_var(C, F, n, **PAR)[0]))
+    assert np.array_equal(bits(var), bits(want_var))   # the estimate precedes the passes
 
 
 def test_outputs_are_finite_at_the_stated_bound():
@@ -127,7 +82,7 @@ def test_outputs_are_finite_at_the_stated_bound():
         got, var = denoise_variance(C, F, iterations=5, eps_l=eps_l, return_variance=True)
         want, want_var = V.atrous_var(C, F, 5, eps_l=eps_l)
         assert np.isfinite(got).all() and not var.any()
-        assert np.array_equal(_bits(got), _bits(want)) and np.array_equal(_bits(var), _bits(want_var))
+        assert np.array_equal(bits(got), bits(want)) and np.array_equal(bits(var), bits(want_var))
 
 
 @pytest.mark.parametrize("with_var", [True, False])
@@ -152,10 +107,10 @@ def test_device_entry_point_on_a_side_stream(restated, with_var):
     stream.synchronize()
     got = d_out.cpu().numpy()
     host, host_var = D.denoise_variance(C, F, iterations=n, return_variance=True, **PAR)
-    assert np.array_equal(_bits(got), _bits(host)) and np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(bits(got), bits(host)) and np.array_equal(bits(got), bits(want))
     if with_var:
-        assert np.array_equal(_bits(d_var.cpu().numpy()), _bits(host_var))
-        assert np.array_equal(_bits(host_var), _bits(want_var))
+        assert np.array_equal(bits(d_var.cpu().numpy()), bits(host_var))
+        assert np.array_equal(bits(host_var), bits(want_var))
     else:
         assert (d_var.cpu().numpy() == -1.0).all()   # left alone
 
@@ -169,28 +124,13 @@ def test_device_entry_point_on_a_side_stream(restated, with_var):
 RHO = {("cornell", 8): 0.4719, ("specular", 8): 0.5139}
 
 
-def _rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b) ** 2)))
-
-
-def _load(which):
-    from pyrenderer_amd.io_utils.read_tungsten import process_primitives, read_file
-    if which == "cornell":
-        return read_file(CORNELL_JSON)
-    d = json.load(open(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene_specular.json")))
-    return process_primitives(d)
-
-
 @pytest.fixture(scope="module")
 def frames():
     """Per scene: the world, the 4096-spp reference (seed 1) and the one-sample features (seed 2) at 128^2."""
-    from pyrenderer_amd.core.tracing import build_world, render
     from pyrenderer_amd.denoise import features
     out = {}
     for which in ("cornell", "specular"):
-        scene, cam = _load(which)
-        world = build_world(scene, (0,))
-        ref = render(scene, cam, spp=4096, depth=8, seed=1, resolution=(128, 128), world=world)
+        scene, cam, world, ref = reference(which)
         feat = features(scene, cam, resolution=(128, 128), samples=1, seed=2, world=world)
         out[which] = (scene, cam, world, ref, feat)
     return out
@@ -203,7 +143,7 @@ def test_it_denoises(frames, which, spp):
     scene, cam, world, ref, feat = frames[which]
     noisy = render(scene, cam, spp=spp, depth=8, seed=2, resolution=(128, 128), world=world)
     den = denoise_variance(noisy, feat)
-    e_noisy, e_den = _rmse(noisy, ref), _rmse(den, ref)
+    e_noisy, e_den = rmse(noisy, ref), rmse(den, ref)
     print(f"variance-guided quality {which} {spp} spp: rmse noisy {e_noisy:.6f} denoised {e_den:.6f} "
           f"ratio {e_den / e_noisy:.4f}")
     assert np.isfinite(den).all()
@@ -226,14 +166,14 @@ def test_public_entry_points_agree(cornell):
     b = denoise_variance(plain, feat)
     acc = Accumulator(scene, cam, **kw)
     c = acc.add(4).denoised(mode="variance")
-    assert np.array_equal(_bits(acc.mean()), _bits(plain))
-    assert np.array_equal(_bits(a), _bits(b)) and np.array_equal(_bits(a), _bits(c))
+    assert np.array_equal(bits(acc.mean()), bits(plain))
+    assert np.array_equal(bits(a), bits(b)) and np.array_equal(bits(a), bits(c))
     assert not np.array_equal(a, plain) and np.isfinite(a).all()
     # parameters reach the filter, and the fixed mode is what it was
-    assert np.array_equal(_bits(acc.denoised(mode="variance", sigma_l=1.0)), _bits(denoise_variance(plain, feat, sigma_l=1.0)))
+    assert np.array_equal(bits(acc.denoised(mode="variance", sigma_l=1.0)), bits(denoise_variance(plain, feat, sigma_l=1.0)))
     fixed = render(scene, cam, spp=4, denoise=True, **kw)
-    assert np.array_equal(_bits(fixed), _bits(denoise(plain, feat)))
-    assert np.array_equal(_bits(fixed), _bits(acc.denoised())) and np.array_equal(_bits(fixed), _bits(acc.denoised(mode="fixed")))
+    assert np.array_equal(bits(fixed), bits(denoise(plain, feat)))
+    assert np.array_equal(bits(fixed), bits(acc.denoised())) and np.array_equal(bits(fixed), bits(acc.denoised(mode="fixed")))
     assert not np.array_equal(fixed, a)
     with pytest.raises(ValueError):
         acc.denoised(mode="nonsense")

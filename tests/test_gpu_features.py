@@ -3,13 +3,11 @@
 bit on every pixel and channel; the device entry point's bounds, argument errors and watchdog; and the
 device chain render -> scatter -> features -> filter against render(denoise=...)."""
 import copy
-import json
-import os
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from denoise_cases import bits, gap_soup, load_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -19,13 +17,9 @@ W0, H0 = 40, 24
 PRT_ERR_ARG = -1
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
-
-
 def _same(got, want):
     assert got.shape == want.shape and got.dtype == F32
-    diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+    diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
     assert len(diff) == 0, (len(diff), diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
 
 
@@ -37,28 +31,6 @@ def _host(ds, cam, W, H, samples, seed, first_sample=0):
 @pytest.fixture(scope="module")
 def packed(cornell):
     return cornell[1].convert_to_taichi_camera().packed()
-
-
-def _gap_soup(cornell, n_tri=60, seed=9):
-    """Scattered triangles in front of the Cornell camera plus the box's light, nothing else: many
-    primary rays pass between them and miss (the construction of tests/test_gpu_denoise.py)."""
-    from pyrenderer_amd.flatten import FlatScene
-    f = cornell[2]
-    rng = np.random.default_rng(seed)
-    c = np.stack([rng.uniform(-0.9, 0.9, n_tri), rng.uniform(0.05, 1.8, n_tri), rng.uniform(-0.9, 0.9, n_tri)], 1)
-    tv = (c[:, None, :] + rng.normal(0, 0.12, (n_tri, 3, 3))).astype(F32).reshape(-1, 9)
-    nn = np.cross((tv[:, 3:6] - tv[:, 0:3]).astype(np.float64), (tv[:, 6:9] - tv[:, 0:3]).astype(np.float64))
-    nn = (nn / np.linalg.norm(nn, axis=1, keepdims=True)).astype(F32)
-    lt = f.light_tri
-    tri_v = np.concatenate([tv, f.tri_v[lt]])
-    tri_n = np.concatenate([nn, f.tri_n[lt]])
-    tri_mat = np.concatenate([np.zeros(n_tri, np.int32), f.tri_mat[lt]])
-    tri_prim = np.concatenate([np.zeros(n_tri, np.int32), np.ones(len(lt), np.int32)])
-    lv = f.tri_v[lt].reshape(-1, 3)
-    lo = np.stack([tv.reshape(-1, 3).min(0), lv.min(0)])
-    hi = np.stack([tv.reshape(-1, 3).max(0), lv.max(0)])
-    return FlatScene(tri_v, tri_n, tri_mat, tri_prim, lo, hi, f.mat, n_tri + np.arange(len(lt), dtype=np.int32),
-                     f.light_off, f.direct_rgb)
 
 
 # ------------------------------------------------------------ bit equality ----
@@ -77,12 +49,12 @@ def test_cornell_ragged_frame(gpu_scene, packed, samples, first):
 @pytest.mark.parametrize("samples", [1, 3])
 def test_gap_soup_has_hits_and_all_zero_misses(cornell, packed, samples):
     from pyrenderer_amd.device_scene import DeviceScene
-    ds = DeviceScene(_gap_soup(cornell), 0)
+    ds = DeviceScene(gap_soup(cornell), 0)
     got = ds.features(packed, W0, H0, samples=samples, seed=7)
     _same(got, _host(ds, packed, W0, H0, samples, 7))
     hit = got[..., 7] > 0
     assert hit.any() and (~hit).any(), (int(hit.sum()), hit.size)
-    assert not _bits(got[~hit]).any()          # every miss pixel is all +0.0 bits
+    assert not bits(got[~hit]).any()          # every miss pixel is all +0.0 bits
     ds.check_faults()
     ds.close()
 
@@ -93,9 +65,7 @@ def test_specular_scene_with_a_sphere():
     the sphere (hit id >= n_tri = 36), so neither the frame nor the seed needed changing."""
     from pyrenderer_amd.device_scene import DeviceScene
     from pyrenderer_amd.flatten import flatten_scene
-    from pyrenderer_amd.io_utils.read_tungsten import process_primitives
-    d = json.load(open(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene_specular.json")))
-    scene, cam = process_primitives(d)
+    scene, cam = load_scene("specular")
     flat = flatten_scene(scene)
     pc = cam.convert_to_taichi_camera().packed()
     ds = DeviceScene(flat, 0)
@@ -147,7 +117,7 @@ def test_the_high_seed_word_reaches_the_key(gpu_scene, packed):
     seed = 2 ** 40 + 7
     got = gpu_scene.features(packed, W0, H0, seed=seed)
     _same(got, _host(gpu_scene, packed, W0, H0, 1, seed))
-    assert not np.array_equal(_bits(got), _bits(gpu_scene.features(packed, W0, H0, seed=7)))
+    assert not np.array_equal(bits(got), bits(gpu_scene.features(packed, W0, H0, seed=7)))
     gpu_scene.check_faults()
 
 
@@ -172,7 +142,7 @@ def test_degenerate_frames_stay_inside_their_buffer(gpu_scene, packed, W, H):
     got = buf.cpu().numpy().view(np.uint32)
     assert (got[:64] == NAN_BITS).all() and (got[64 + n:] == NAN_BITS).all()
     want = gpu_scene.features(packed, W, H, samples=1, seed=7)
-    assert np.array_equal(got[64:64 + n], _bits(want).reshape(-1))
+    assert np.array_equal(got[64:64 + n], bits(want).reshape(-1))
     gpu_scene.check_faults()
 
 

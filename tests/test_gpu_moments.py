@@ -1,7 +1,6 @@
 """Variance from per-pixel sample moments on the GPU: prt_moments_add and prt_denoise_var_given against
 the NumPy restatement (tests/moments_ref.py) bit for bit, the device entry points, the public API end to
 end and the quality gain."""
-import json
 import os
 
 import numpy as np
@@ -10,7 +9,9 @@ import pytest
 import atrous_ref as R
 import atrous_var_ref as V
 import moments_ref as M
-from conftest import CORNELL_JSON, ROOT
+import temporal_ref as T
+from conftest import CORNELL_JSON
+from denoise_cases import bits, mixed_inputs, reference, rmse
 
 pytestmark = pytest.mark.gpu
 
@@ -21,10 +22,6 @@ PAR = dict(sigma_l=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3, eps_l=3e-3)
 SHAPES = [(1, 1), (3, 7), (33, 17), (70, 130)]
 N_SAMPLES = 4.0
 BOUND = 2.0 ** 62   # include/prt.h: |l| <= 2^62 keeps the state finite for up to 8 frames
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 def _features(W, H, rng):
@@ -91,20 +88,20 @@ def test_moments_equal_the_restatement_bit_for_bit(restated_moments, W, H):
     for K in (1, 2, 5):
         S, F, want = restated_moments[(W, H, K)]
         got = moments_add(moments_state(W, H), S, N_SAMPLES, F, eps_a=PAR["eps_a"])
-        diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+        diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
         assert len(diff) == 0, (K, len(diff), diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
         # a non-zero frame pitch
         buf, pitch = _padded(S, 5)
         st = moments_state(W, H)
         N.check_denoise(N.lib().prt_moments_add(0, N.ptr(buf), K, pitch, N_SAMPLES, N.ptr(F), PAR["eps_a"], W, H, N.ptr(st)))
-        assert np.array_equal(_bits(st), _bits(want)), K
+        assert np.array_equal(bits(st), bits(want)), K
         # split over two calls
         if K > 1:
             st = moments_state(W, H)
             moments_add(st, S[:K // 2], N_SAMPLES, F, eps_a=PAR["eps_a"])
             assert (st[..., 0] <= K // 2).all()
             moments_add(st, S[K // 2:], N_SAMPLES, F, eps_a=PAR["eps_a"])
-            assert np.array_equal(_bits(st), _bits(want)), K
+            assert np.array_equal(bits(st), bits(want)), K
         # what the inputs exercise: the bound stays finite, the non-finite frames are skipped
         assert np.isfinite(got).all() and (got[..., 3] >= 0).all()
         assert got[W - 1, H - 1, 0] == K and (K < 2 or got[W - 1, H - 1, 2] >= BOUND * BOUND)
@@ -151,17 +148,17 @@ def test_given_variance_filter_equals_the_restatement_bit_for_bit(restated_given
     live = (F[..., 7] > 0) & np.isfinite(C).all(axis=-1)
     for n in (0, 1, 5, 8):
         got, used = denoise_variance(C, F, iterations=n, return_variance=True, variance=iv, **PAR)
-        diff = np.argwhere(_bits(used) != _bits(want[n][1]))
+        diff = np.argwhere(bits(used) != bits(want[n][1]))
         assert len(diff) == 0, ("variance", n, len(diff), diff[:5])
-        diff = np.argwhere(np.any(_bits(got) != _bits(want[n][0]), axis=-1))
+        diff = np.argwhere(np.any(bits(got) != bits(want[n][0]), axis=-1))
         assert len(diff) == 0, ("image", n, len(diff), diff[:5])
-        assert np.array_equal(_bits(got), _bits(denoise_variance(C, F, iterations=n, variance=iv, **PAR)))   # no out_var
+        assert np.array_equal(bits(got), bits(denoise_variance(C, F, iterations=n, variance=iv, **PAR)))   # no out_var
         assert np.isfinite(used).all() and (used >= 0).all() and not used[~live].any()
-        assert np.array_equal(_bits(used[live]), _bits(clean[live]))
+        assert np.array_equal(bits(used[live]), bits(clean[live]))
     # NaN, inf and -1 behave as 0
     a = denoise_variance(C, F, iterations=5, variance=iv, **PAR)
     b = denoise_variance(C, F, iterations=5, variance=clean, **PAR)
-    assert np.array_equal(_bits(a), _bits(b))
+    assert np.array_equal(bits(a), bits(b))
     if W * H > 100:   # and the plane is at work: another variance, another image
         c = denoise_variance(C, F, iterations=5, variance=clean * F32(16.0), **PAR)
         assert np.mean(np.any(a[live] != c[live], axis=-1)) > 0.5
@@ -173,14 +170,14 @@ def test_the_spatial_estimate_fed_back_reproduces_the_spatial_mode(restated_give
     C, F, _, _, _ = restated_given[(W, H)]
     img, est = denoise_variance(C, F, iterations=5, return_variance=True, **PAR)
     again, used = denoise_variance(C, F, iterations=5, return_variance=True, variance=est, **PAR)
-    assert np.array_equal(_bits(img), _bits(again)) and np.array_equal(_bits(est), _bits(used))
+    assert np.array_equal(bits(img), bits(again)) and np.array_equal(bits(est), bits(used))
     want, want_est = V.atrous_var(C, F, 5, **PAR)
-    assert np.array_equal(_bits(img), _bits(want)) and np.array_equal(_bits(est), _bits(want_est))
+    assert np.array_equal(bits(img), bits(want)) and np.array_equal(bits(est), bits(want_est))
     mz = est.copy()
     mz[0, 0] = -0.0   # the restatement passes a -0 on as -0 at a usable pixel, as +0 elsewhere
     got = denoise_variance(C, F, iterations=2, return_variance=True, variance=mz, **PAR)
     ref = M.atrous_var_given(C, F, mz, 2, **PAR)
-    assert np.array_equal(_bits(got[0]), _bits(ref[0])) and np.array_equal(_bits(got[1]), _bits(ref[1]))
+    assert np.array_equal(bits(got[0]), bits(ref[0])) and np.array_equal(bits(got[1]), bits(ref[1]))
 
 
 def test_device_entry_points_on_a_side_stream(restated_moments, restated_given):
@@ -201,7 +198,7 @@ def test_device_entry_points_on_a_side_stream(restated_moments, restated_given):
     D.moments_add_device(d_s.data_ptr() + 2 * pitch * 4, 3, N_SAMPLES, d_f.data_ptr(), W, H, d_state.data_ptr(),
                          frame_pitch=pitch, eps_a=PAR["eps_a"], stream_ptr=stream.cuda_stream)
     stream.synchronize()
-    assert np.array_equal(_bits(d_state.cpu().numpy()), _bits(want))
+    assert np.array_equal(bits(d_state.cpu().numpy()), bits(want))
     assert (d_s.cpu().numpy().reshape(K, pitch)[:, -12:] == 7.0).all()
 
     C, F, iv, _, wants = restated_given[(W, H)]
@@ -216,21 +213,22 @@ def test_device_entry_points_on_a_side_stream(restated_moments, restated_given):
                               d_out_var_ptr=d_var.data_ptr(), d_in_var_ptr=d_iv.data_ptr(), iterations=5,
                               stream_ptr=stream.cuda_stream, **PAR)
     stream.synchronize()
-    assert np.array_equal(_bits(d_out.cpu().numpy()), _bits(want_img))
-    assert np.array_equal(_bits(d_var.cpu().numpy()), _bits(want_used))
-    assert np.array_equal(_bits(d_iv.cpu().numpy()), _bits(iv))   # the input plane is left alone
+    assert np.array_equal(bits(d_out.cpu().numpy()), bits(want_img))
+    assert np.array_equal(bits(d_var.cpu().numpy()), bits(want_used))
+    assert np.array_equal(bits(d_iv.cpu().numpy()), bits(iv))   # the input plane is left alone
     d_var.fill_(-1.0)
     torch.cuda.synchronize(dev)
     D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, d_out.data_ptr(), d_work.data_ptr(), need,
                               d_in_var_ptr=d_iv.data_ptr(), iterations=5, stream_ptr=stream.cuda_stream, **PAR)
     stream.synchronize()
-    assert np.array_equal(_bits(d_out.cpu().numpy()), _bits(want_img)) and (d_var.cpu().numpy() == -1.0).all()
+    assert np.array_equal(bits(d_out.cpu().numpy()), bits(want_img)) and (d_var.cpu().numpy() == -1.0).all()
 
 
 def test_modes_alternating_on_one_scratch_leave_nothing_behind(restated_given):
-    """The modes share their launch and scratch code: given variance, fixed, spatial estimate and fixed again
-    on one NaN-filled scratch and one stream, with no host synchronisation in between.  A plane that one
-    mode left behind and the next one read would show in the bits."""
+    """The modes share their launch and scratch code: given variance, fixed, mixed (a plane with NaN gaps, whose
+    estimate kernel writes the planes the others read), spatial estimate and fixed again on one NaN-filled
+    scratch and one stream, with no host synchronisation in between.  A plane that one mode left behind and
+    the next one read would show in the bits."""
     import torch
     from pyrenderer_amd import denoise as D
     fixed_par = dict(sigma_c=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3)   # test_gpu_denoise.py's
@@ -239,27 +237,32 @@ def test_modes_alternating_on_one_scratch_leave_nothing_behind(restated_given):
     want_given = wants[5][0]
     want_fixed = R.atrous(C, F, 5, **fixed_par)
     want_spatial = V.atrous_var(C, F, 5, **PAR)[0]
+    plane = mixed_inputs(W, H, 40 + W)[2]   # test_gpu_temporal.py's: the marker on about half of the pixels
+    want_mixed = T.atrous_var_mixed(C, F, plane, 5, **PAR)[0]
     dev = torch.device("cuda:0")
     stream = torch.cuda.Stream(dev)
-    d_c, d_f, d_iv = (torch.from_numpy(a).to(dev) for a in (C, F, iv))
+    d_c, d_f, d_iv, d_plane = (torch.from_numpy(a).to(dev) for a in (C, F, iv, plane))
     need_var, need_fixed = D.work_bytes_variance(W, H), D.work_bytes(W, H)
     assert need_fixed < need_var
     d_work = torch.full((need_var,), 0xFF, dtype=torch.uint8, device=dev)
     assert d_work.data_ptr() % 16 == 0
-    outs = [torch.zeros((W, H, 3), dtype=torch.float32, device=dev) for _ in range(4)]
+    outs = [torch.zeros((W, H, 3), dtype=torch.float32, device=dev) for _ in range(5)]
     stream.wait_stream(torch.cuda.current_stream(dev))
     D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[0].data_ptr(), d_work.data_ptr(), need_var,
                               d_in_var_ptr=d_iv.data_ptr(), iterations=5, stream_ptr=stream.cuda_stream, **PAR)
     D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[1].data_ptr(), d_work.data_ptr(), need_fixed,
                      iterations=5, stream_ptr=stream.cuda_stream, **fixed_par)
     D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[2].data_ptr(), d_work.data_ptr(), need_var,
+                              d_in_var_ptr=d_plane.data_ptr(), variance_fallback="spatial", iterations=5,
+                              stream_ptr=stream.cuda_stream, **PAR)
+    D.denoise_variance_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[3].data_ptr(), d_work.data_ptr(), need_var,
                               iterations=5, stream_ptr=stream.cuda_stream, **PAR)
-    D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[3].data_ptr(), d_work.data_ptr(), need_fixed,
+    D.denoise_device(d_c.data_ptr(), d_f.data_ptr(), W, H, outs[4].data_ptr(), d_work.data_ptr(), need_fixed,
                      iterations=5, stream_ptr=stream.cuda_stream, **fixed_par)
     stream.synchronize()
-    for name, got, want in zip(("given", "fixed", "spatial", "fixed again"), outs,
-                               (want_given, want_fixed, want_spatial, want_fixed)):
-        diff = np.argwhere(np.any(_bits(got.cpu().numpy()) != _bits(want), axis=-1))
+    for name, got, want in zip(("given", "fixed", "mixed", "spatial", "fixed again"), outs,
+                               (want_given, want_fixed, want_mixed, want_spatial, want_fixed)):
+        diff = np.argwhere(np.any(bits(got.cpu().numpy()) != bits(want), axis=-1))
         assert len(diff) == 0, (name, len(diff), diff[:5])
 
 
@@ -278,19 +281,19 @@ def test_render_and_accumulator_agree_end_to_end(cornell, tmp_path):
     acc.add(n).add(n)
     # below MIN_MOMENT_BATCHES the spatial estimate is used
     assert acc.batches == 2 < D.MIN_MOMENT_BATCHES
-    assert np.array_equal(_bits(acc.denoised(mode="variance")), _bits(D.denoise_variance(acc.mean(), acc.features())))
+    assert np.array_equal(bits(acc.denoised(mode="variance")), bits(D.denoise_variance(acc.mean(), acc.features())))
     acc.add(0).add(n).add(n)
     b = acc.denoised(mode="variance")
     assert acc.samples == K * n and acc.batches == K
-    assert np.array_equal(_bits(a), _bits(b)) and np.isfinite(a).all()
+    assert np.array_equal(bits(a), bits(b)) and np.isfinite(a).all()
     sums, feat, state = render_batches(scene, cam, spp=K * n, depth=4, variance_batches=K, seed=3, resolution=(64, 64),
                                        world=world)
-    assert np.array_equal(_bits(state), _bits(acc.moments_state)) and np.array_equal(_bits(sums), _bits(acc.sums()))
-    assert np.array_equal(_bits(feat), _bits(acc.features()))
+    assert np.array_equal(bits(state), bits(acc.moments_state)) and np.array_equal(bits(sums), bits(acc.sums()))
+    assert np.array_equal(bits(feat), bits(acc.features()))
     assert (state[..., 0] == K).all()
-    assert np.array_equal(_bits(a), _bits(D.denoise_variance(acc.mean(), feat, variance=state[..., 3])))
+    assert np.array_equal(bits(a), bits(D.denoise_variance(acc.mean(), feat, variance=state[..., 3])))
     assert not np.array_equal(a, D.denoise_variance(acc.mean(), feat))   # not the spatial estimate's image
-    assert np.array_equal(_bits(acc.noise_map()), _bits(np.sqrt(state[..., 3]))) and (state[..., 3] > 0).mean() > 0.9
+    assert np.array_equal(bits(acc.noise_map()), bits(np.sqrt(state[..., 3]))) and (state[..., 3] > 0).mean() > 0.9
     # the state's mean against lum of the demodulated total mean.  In exact arithmetic both are the mean of
     # the K batch luminances l_j.  All terms are non-negative, so rounding errors stay relative: Welford's
     # mean makes 3 roundings per batch (3 K), each l_j 7 (/ n, / a, 5 in lum), the total mean K adds and
@@ -309,14 +312,14 @@ def test_render_and_accumulator_agree_end_to_end(cornell, tmp_path):
     acc.save(tmp_path / "m.npz")
     back = Accumulator.load(tmp_path / "m.npz", scene, cam, world=world)
     assert back.moments and back.batch_spp == n and back.batches == K
-    assert np.array_equal(_bits(back.moments_state), _bits(state))
-    assert np.array_equal(_bits(back.denoised(mode="variance")), _bits(a))
+    assert np.array_equal(bits(back.moments_state), bits(state))
+    assert np.array_equal(bits(back.denoised(mode="variance")), bits(a))
     old = Accumulator(scene, cam, **kw).add(K * n)
     old.save(tmp_path / "p.npz")
     assert sorted(np.load(tmp_path / "p.npz").files) == sorted(
         ["slots", "samples", "seed", "depth", "resolution", "tile", "flags", "camera", "scene_sha"])
     assert not Accumulator.load(tmp_path / "p.npz", scene, cam, world=world).moments
-    assert np.array_equal(_bits(old.mean()), _bits(plain))
+    assert np.array_equal(bits(old.mean()), bits(plain))
 
 
 def test_command_line_writes_the_variance_it_used(tmp_path):
@@ -333,12 +336,12 @@ def test_command_line_writes_the_variance_it_used(tmp_path):
     var = np.load(os.path.join(aov, "variance.npy"))
     _, _, _, _, _, hit, bad, _ = R.prepass(sums / F32(8), feat, D.EPS_A)
     assert var.shape == (32, 24) and var.dtype == F32
-    assert np.array_equal(_bits(var), _bits(M.given(state[..., 3], hit & ~bad))) and var.any()
-    assert np.array_equal(_bits(img), _bits(D.denoise_variance(sums / F32(8), feat, variance=state[..., 3])))
+    assert np.array_equal(bits(var), bits(M.given(state[..., 3], hit & ~bad))) and var.any()
+    assert np.array_equal(bits(img), bits(D.denoise_variance(sums / F32(8), feat, variance=state[..., 3])))
     # progressive: every pass is a batch
     prog = main(["--resolution", "32", "24", "--depth", "4", "--seed", "5", "--samples", "8", "--interval", "2",
                  "--denoise", "--denoise-mode", "variance", "--variance-batches", "4", "--out", ""])
-    assert np.array_equal(_bits(prog), _bits(img))
+    assert np.array_equal(bits(prog), bits(img))
 
 
 def test_command_line_render_and_accumulator_agree_on_ragged_tiles(cornell):
@@ -364,8 +367,8 @@ def test_command_line_render_and_accumulator_agree_on_ragged_tiles(cornell):
              lambda: batched.denoised(mode="variance"))):
         want = render(scene, cam, spp=8, **render_kw, **kw)
         assert want.shape == (72, 40, 3) and np.isfinite(want).all() and want[64:, :].any() and want[:, 39].any()
-        assert np.array_equal(_bits(main(argv + switches)), _bits(want)), switches
-        assert np.array_equal(_bits(route()), _bits(want)), switches
+        assert np.array_equal(bits(main(argv + switches)), bits(want)), switches
+        assert np.array_equal(bits(route()), bits(want)), switches
         images.append(want)
     for i in range(4):   # four different images: the equalities above are not one image four times
         for j in range(i):
@@ -380,40 +383,16 @@ def test_command_line_render_and_accumulator_agree_on_ragged_tiles(cornell):
 RHO = {("cornell", 8, 4): 0.4340, ("specular", 8, 4): 0.4889, ("cornell", 64, 8): 0.5332, ("specular", 64, 8): 0.6597}
 
 
-def _rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b) ** 2)))
-
-
-def _load(which):
-    from pyrenderer_amd.io_utils.read_tungsten import process_primitives, read_file
-    if which == "cornell":
-        return read_file(CORNELL_JSON)
-    d = json.load(open(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene_specular.json")))
-    return process_primitives(d)
-
-
-@pytest.fixture(scope="module")
-def references():
-    """Per scene: the world and the 4096-spp reference (seed 1) at 128^2, as test_gpu_denoise_var.py's."""
-    from pyrenderer_amd.core.tracing import build_world, render
-    out = {}
-    for which in ("cornell", "specular"):
-        scene, cam = _load(which)
-        world = build_world(scene, (0,))
-        out[which] = (scene, cam, world, render(scene, cam, spp=4096, depth=8, seed=1, resolution=(128, 128), world=world))
-    return out
-
-
 @pytest.mark.parametrize("which,spp,K", sorted(RHO))
-def test_it_denoises(references, which, spp, K):
+def test_it_denoises(which, spp, K):
     from pyrenderer_amd.core.tracing import render_batches
     from pyrenderer_amd.denoise import denoise_variance
-    scene, cam, world, ref = references[which]
+    scene, cam, world, ref = reference(which)
     sums, feat, state = render_batches(scene, cam, spp=spp, depth=8, variance_batches=K, seed=2, resolution=(128, 128),
                                        world=world)
     noisy = sums / F32(spp)
     den = denoise_variance(noisy, feat, variance=state[..., 3])
-    e_noisy, e_den = _rmse(noisy, ref), _rmse(den, ref)
+    e_noisy, e_den = rmse(noisy, ref), rmse(den, ref)
     print(f"moments quality {which} {spp} spp K {K}: rmse noisy {e_noisy:.6f} denoised {e_den:.6f} "
           f"ratio {e_den / e_noisy:.4f}")
     assert np.isfinite(den).all()

@@ -12,6 +12,7 @@ import atrous_var_ref as V
 import moments_ref as M
 import temporal_cases as TC
 import temporal_ref as T
+from denoise_cases import MARKER, bits, canaried, inner, mixed_inputs, rmse
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,6 @@ F32 = np.float32
 SHAPES = [(1, 1), (3, 7), (33, 17), (70, 130)]
 P = T.DEFAULTS
 PAR = dict(sigma_l=1.5, sigma_z=0.75, eps_a=1e-2, eps_z=2e-3, eps_l=3e-3)
-MARKER = 0x7fc00000
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
@@ -60,28 +56,28 @@ def test_kernel_equals_the_restatement_bit_for_bit(restated, W, H, kind):
     assert list(P) == ["alpha", "alpha_m", "tau_n", "tau_z", "tau_a", "eps_a", "min_history", "w_min"]
     state, color, var = _gpu(C, F, cam, prev)
     for name, got, want in (("state", state, w_state), ("colour", color, w_color), ("variance", var[..., None], w_var[..., None])):
-        diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+        diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
         assert len(diff) == 0, (name, len(diff), diff[:5], got[tuple(diff[0])], want[tuple(diff[0])])
     # the Python front end, with and without the colour
     from pyrenderer_amd import denoise as D
     s2, c2 = D.temporal_accumulate(C, F, cam, prev, **P)
-    assert np.array_equal(_bits(s2), _bits(w_state)) and np.array_equal(_bits(c2), _bits(w_color))
-    assert np.array_equal(_bits(D.temporal_accumulate(C, F, cam, prev, return_color=False, **P)), _bits(w_state))
+    assert np.array_equal(bits(s2), bits(w_state)) and np.array_equal(bits(c2), bits(w_color))
+    assert np.array_equal(bits(D.temporal_accumulate(C, F, cam, prev, return_color=False, **P)), bits(w_state))
     # what the inputs exercise
     if W * H > 500:
         bad = T.prepare(C, F, P["eps_a"])[6]   # a colour of 3e38 over an albedo below 1 overflows: bad as well
         hit = F[..., 7] > 0
         assert bad.any() and (bad & np.isfinite(C).all(-1) & np.isfinite(F).all(-1)).any() and (~hit).any() and (F[..., 0] < P["eps_a"]).any() and (np.abs(F[..., 6]) == F32(1e30)).any()
-        assert not state[bad].any() and (_bits(var[bad]) == MARKER).all()
+        assert not state[bad].any() and (bits(var[bad]) == MARKER).all()
         assert (state[~hit & ~bad, 3] == 1).all()
         if kind == "first":
-            assert (state[~bad, 3] == 1).all() and (_bits(var) == MARKER).all()
+            assert (state[~bad, 3] == 1).all() and (bits(var) == MARKER).all()
         if kind in ("static", "moved"):
             ps, pf, _ = prev
             assert (ps[..., 3] == 0).any() and (pf[..., 7] == 0).any()
             v = d["valid"]
             assert 0.3 < v.mean() < 0.8 and (state[v, 3] > 1).all() and (state[~v & ~bad, 3] == 1).all()
-            known = _bits(var) != MARKER
+            known = bits(var) != MARKER
             assert known.any() and (known <= v).all() and (var[known] >= 0).all()
             assert (state[v, 3] >= P["min_history"])[known[v]].all()
         if kind == "moved":
@@ -108,7 +104,7 @@ def test_one_row_and_one_column_frames(W, H):
         want = T.accumulate(C, F, cam, (S, F, prev_cam), **P)
         got = _gpu(C, F, cam, (S, F, prev_cam))
         for g, w in zip(got, want):
-            assert np.array_equal(_bits(g), _bits(w))
+            assert np.array_equal(bits(g), bits(w))
         assert np.array_equal(got[0][..., 3], h_want)
 
 
@@ -127,19 +123,6 @@ def test_a_static_sequence_is_a_running_mean_on_the_gpu():
     assert np.abs(state[..., 0:3] - I.mean(0)).max() <= n * 4 * 2.0 ** -24 * np.abs(I).max()
 
 
-def _canaried(torch, dev, n_floats, pad=64):
-    """A device buffer of n_floats behind and before `pad` floats of 7: (whole tensor, 16-byte aligned pointer)."""
-    buf = torch.full((n_floats + 2 * pad,), 7.0, dtype=torch.float32, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    return buf, buf.data_ptr() + pad * 4
-
-
-def _inner(buf, n_floats, pad=64):
-    a = buf.cpu().numpy()
-    assert (a[:pad] == 7.0).all() and (a[pad + n_floats:] == 7.0).all(), "a canary was overwritten"
-    return a[pad:pad + n_floats]
-
-
 def test_device_form_equals_the_host_form(restated):
     import torch
     from pyrenderer_amd import denoise as D
@@ -154,68 +137,55 @@ def test_device_form_equals_the_host_form(restated):
         if prev is not None:
             d_ps, d_pf = torch.from_numpy(prev[0]).to(dev), torch.from_numpy(prev[1]).to(dev)
             kw = dict(d_prev_feat_ptr=d_pf.data_ptr(), prev_cam=prev[2], d_prev_state_ptr=d_ps.data_ptr())
-        b_state, p_state = _canaried(torch, dev, n * 8)
-        b_color, p_color = _canaried(torch, dev, n * 3)
-        b_var, p_var = _canaried(torch, dev, n)
+        b_state, p_state = canaried(torch, dev, n * 8)
+        b_color, p_color = canaried(torch, dev, n * 3)
+        b_var, p_var = canaried(torch, dev, n)
         stream.wait_stream(torch.cuda.current_stream(dev))
         D.temporal_accumulate_device(d_c.data_ptr(), d_f.data_ptr(), cam, W, H, p_state, d_out_color_ptr=p_color,
                                      d_out_var_ptr=p_var, stream_ptr=stream.cuda_stream, **P, **kw)
         stream.synchronize()
-        assert np.array_equal(_inner(b_state, n * 8).view(np.uint32), _bits(w_state).reshape(-1)), kind
-        assert np.array_equal(_inner(b_color, n * 3).view(np.uint32), _bits(w_color).reshape(-1)), kind
-        assert np.array_equal(_inner(b_var, n).view(np.uint32), _bits(w_var).reshape(-1)), kind
-        assert np.array_equal(_bits(d_c.cpu().numpy()), _bits(C)) and np.array_equal(_bits(d_f.cpu().numpy()), _bits(F))
+        assert np.array_equal(inner(b_state, n * 8).view(np.uint32), bits(w_state).reshape(-1)), kind
+        assert np.array_equal(inner(b_color, n * 3).view(np.uint32), bits(w_color).reshape(-1)), kind
+        assert np.array_equal(inner(b_var, n).view(np.uint32), bits(w_var).reshape(-1)), kind
+        assert np.array_equal(bits(d_c.cpu().numpy()), bits(C)) and np.array_equal(bits(d_f.cpu().numpy()), bits(F))
         # the optional outputs left out: the state alone, the other buffers untouched
-        b_state2, p_state2 = _canaried(torch, dev, n * 8)
+        b_state2, p_state2 = canaried(torch, dev, n * 8)
         D.temporal_accumulate_device(d_c.data_ptr(), d_f.data_ptr(), cam, W, H, p_state2, stream_ptr=stream.cuda_stream,
                                      **P, **kw)
         stream.synchronize()
-        assert np.array_equal(_inner(b_state2, n * 8).view(np.uint32), _bits(w_state).reshape(-1)), kind
+        assert np.array_equal(inner(b_state2, n * 8).view(np.uint32), bits(w_state).reshape(-1)), kind
 
 
 # ------------------------------------------------------ prt_denoise_var_mixed ----
 
-def _mixed_inputs(W, H, seed):
-    """Colour and features as the temporal frames', and a variance plane that is the temporal marker on about
-    half of the pixels, with an inf, a -1 and a -0 among the rest."""
-    rng = np.random.default_rng(seed)
-    C, F, _, _ = TC.hostile("first", W, H, seed)
-    plane = (rng.random((W, H), dtype=F32) * F32(0.3)) ** 2
-    plane[rng.random((W, H)) < 0.5] = np.array([MARKER], np.uint32).view(F32)[0]
-    if W * H >= 4:
-        flat = plane.reshape(-1)
-        flat[0], flat[1], flat[2] = np.inf, -1.0, -0.0
-    return C, F, plane
-
-
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_mixed_variance_equals_the_restatement_and_its_two_limits(W, H):
     from pyrenderer_amd.denoise import denoise_variance
-    C, F, plane = _mixed_inputs(W, H, 40 + W)
+    C, F, plane = mixed_inputs(W, H, 40 + W)
     for n in (0, 5):
         want, want_used = T.atrous_var_mixed(C, F, plane, n, **PAR)
         got, used = denoise_variance(C, F, iterations=n, variance=plane, variance_fallback="spatial",
                                      return_variance=True, **PAR)
-        diff = np.argwhere(_bits(used) != _bits(want_used))
+        diff = np.argwhere(bits(used) != bits(want_used))
         assert len(diff) == 0, ("variance", n, len(diff), diff[:5])
-        diff = np.argwhere(np.any(_bits(got) != _bits(want), axis=-1))
+        diff = np.argwhere(np.any(bits(got) != bits(want), axis=-1))
         assert len(diff) == 0, ("image", n, len(diff), diff[:5])
-        assert np.array_equal(_bits(got), _bits(denoise_variance(C, F, iterations=n, variance=plane,
+        assert np.array_equal(bits(got), bits(denoise_variance(C, F, iterations=n, variance=plane,
                                                                  variance_fallback="spatial", **PAR)))   # no out_var
         assert np.isfinite(used).all() and (used >= 0).all()
     # all NaN: the spatial mode; all finite and >= 0: the given variance — both bit for bit, variance included
     nan = np.full((W, H), np.nan, F32)
     a = denoise_variance(C, F, variance=nan, variance_fallback="spatial", return_variance=True, **PAR)
     b = denoise_variance(C, F, return_variance=True, **PAR)
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
     full = np.where(np.isfinite(plane) & (plane >= 0), plane, F32(0.01)).astype(F32)
     a = denoise_variance(C, F, variance=full, variance_fallback="spatial", return_variance=True, **PAR)
     b = denoise_variance(C, F, variance=full, return_variance=True, **PAR)
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
     # "zero" stays today's path: the marker counts as 0
     z = denoise_variance(C, F, variance=plane, return_variance=True, **PAR)
     ref = M.atrous_var_given(C, F, plane, 5, **PAR)
-    assert np.array_equal(_bits(z[0]), _bits(ref[0])) and np.array_equal(_bits(z[1]), _bits(ref[1]))
+    assert np.array_equal(bits(z[0]), bits(ref[0])) and np.array_equal(bits(z[1]), bits(ref[1]))
     if W * H > 500:
         live = (F[..., 7] > 0) & np.isfinite(C).all(-1) & np.isfinite(F).all(-1)
         gaps = live & ~(np.isfinite(plane) & (plane >= 0))
@@ -228,11 +198,11 @@ def test_mixed_device_form_on_a_side_stream():
     dev = torch.device("cuda:0")
     stream = torch.cuda.Stream(dev)
     W, H = 70, 130
-    C, F, plane = _mixed_inputs(W, H, 40 + W)
+    C, F, plane = mixed_inputs(W, H, 40 + W)
     want, want_used = T.atrous_var_mixed(C, F, plane, 5, **PAR)
     d_c, d_f, d_iv = (torch.from_numpy(a).to(dev) for a in (C, F, plane))
-    b_out, p_out = _canaried(torch, dev, W * H * 3)
-    b_var, p_var = _canaried(torch, dev, W * H)
+    b_out, p_out = canaried(torch, dev, W * H * 3)
+    b_var, p_var = canaried(torch, dev, W * H)
     need = D.work_bytes_variance(W, H)
     d_work = torch.full((need,), 0xFF, dtype=torch.uint8, device=dev)   # exactly the spatial mode's scratch
     stream.wait_stream(torch.cuda.current_stream(dev))
@@ -240,9 +210,9 @@ def test_mixed_device_form_on_a_side_stream():
                               d_in_var_ptr=d_iv.data_ptr(), variance_fallback="spatial", iterations=5,
                               stream_ptr=stream.cuda_stream, **PAR)
     stream.synchronize()
-    assert np.array_equal(_inner(b_out, W * H * 3).view(np.uint32), _bits(want).reshape(-1))
-    assert np.array_equal(_inner(b_var, W * H).view(np.uint32), _bits(want_used).reshape(-1))
-    assert np.array_equal(_bits(d_iv.cpu().numpy()), _bits(plane))   # the input plane is left alone
+    assert np.array_equal(inner(b_out, W * H * 3).view(np.uint32), bits(want).reshape(-1))
+    assert np.array_equal(inner(b_var, W * H).view(np.uint32), bits(want_used).reshape(-1))
+    assert np.array_equal(bits(d_iv.cpu().numpy()), bits(plane))   # the input plane is left alone
 
 
 # -------------------------------------------------------------- end to end ----
@@ -252,10 +222,6 @@ def test_mixed_device_form_on_a_side_stream():
 # default parameters, measured on the MI355X.  The margin rule of
 # test_gpu_denoise.test_it_denoises: sqrt(rho).
 RHO = 0.2870
-
-
-def _rmse(a, b):
-    return float(np.sqrt(np.mean((a.astype(np.float64) - b) ** 2)))
 
 
 @pytest.fixture(scope="module")
@@ -285,7 +251,7 @@ def turntable(cornell):
 def test_turntable_keeps_its_history_and_beats_the_last_frame_alone(turntable):
     t = turntable
     print("temporal history shares, frames 0..7:", " ".join(f"{s:.4f}" for s in t["shares"]))
-    e_t, e_a = _rmse(t["temporal"], t["ref"]), _rmse(t["alone"], t["ref"])
+    e_t, e_a = rmse(t["temporal"], t["ref"]), rmse(t["alone"], t["ref"])
     print(f"temporal quality cornell 128^2 1 spp 8 frames: rmse temporal {e_t:.6f} alone {e_a:.6f} ratio {e_t / e_a:.4f}")
     assert t["shares"][0] == 0.0 and min(t["shares"][1:]) >= 0.9, t["shares"]
     assert np.isfinite(t["temporal"]).all() and np.isfinite(t["accumulated"]).all()
@@ -303,8 +269,8 @@ def test_a_jump_resets_to_this_frames_colour(turntable):
     fresh = hit & (h == 1)
     print(f"temporal jump of 40 degrees: fresh {fresh.sum()} of {hit.sum()} hit pixels")
     assert fresh.sum() > 0.05 * hit.sum() and (hit & (h > 1)).sum() > 0.05 * hit.sum()
-    assert np.array_equal(_bits(state[fresh, 0:3]), _bits(I[fresh]))
-    assert (_bits(state[fresh, 6]) == MARKER).all()
+    assert np.array_equal(bits(state[fresh, 0:3]), bits(I[fresh]))
+    assert (bits(state[fresh, 6]) == MARKER).all()
     assert np.isfinite(acc.accumulated()).all() and np.isfinite(acc.denoised()).all()
     # render_sequence is the same route: the jump's frame again, from a fresh history
     assert (h[~hit] == 1).all()
@@ -336,7 +302,7 @@ def test_render_sequence_and_a_static_accumulator(turntable):
     step = TemporalAccumulator(scene, spp=2, **kw)
     for t, c in enumerate(cams):
         step.add(c)
-        assert np.array_equal(_bits(step.accumulated()), _bits(raw[t])) and np.array_equal(_bits(step.denoised()), _bits(seq[t]))
+        assert np.array_equal(bits(step.accumulated()), bits(raw[t])) and np.array_equal(bits(step.denoised()), bits(seq[t]))
 
 
 def test_command_line_writes_a_turntable(turntable, tmp_path):
@@ -353,9 +319,9 @@ def test_command_line_writes_a_turntable(turntable, tmp_path):
     kw = dict(spp=2, depth=4, seed=5, resolution=(32, 24), world=world)
     last = main(argv + ["--temporal", "--out", str(tmp_path / "t.png")] + var)
     assert sorted(os.listdir(tmp_path)) == ["t.0000.png", "t.0001.png", "t.0002.png"]
-    assert np.array_equal(_bits(last), _bits(render_sequence(scene, cams, **kw)[-1]))
+    assert np.array_equal(bits(last), bits(render_sequence(scene, cams, **kw)[-1]))
     raw = main(argv + ["--temporal", "--out", ""])
-    assert np.array_equal(_bits(raw), _bits(render_sequence(scene, cams, denoise=False, **kw)[-1]))
+    assert np.array_equal(bits(raw), bits(render_sequence(scene, cams, denoise=False, **kw)[-1]))
     alone = main(argv + ["--out", ""] + var)       # no history: the third frame's own two samples, filtered
     assert np.isfinite(alone).all() and not np.array_equal(alone, last)
     assert sorted(os.listdir(tmp_path)) == ["t.0000.png", "t.0001.png", "t.0002.png"]

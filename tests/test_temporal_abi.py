@@ -58,7 +58,7 @@ def test_the_kernel_lives_in_an_auxiliary_unit_and_the_trace_kernels_key_is_unch
     import json
     from pyrenderer_amd import build as B
     homes = [f for f in B.SOURCES + B.HEADERS + [B.TRACE_INST] + B.AUX_SOURCES + B.AUX_HEADERS
-             if re.search(r"\btemporal_kernel\b|\bvar_select_kernel\b|\benqueue_temporal\b",
+             if re.search(r"\btemporal_kernel\b|\bvar_estimate_kernel\b|\benqueue_temporal\b",
                           open(os.path.join(B.CSRC, f)).read())]
     assert homes and set(homes) <= set(B.AUX_SOURCES + B.AUX_HEADERS), homes
     assert not set(homes) & set(B.SOURCES + B.HEADERS + [B.TRACE_INST])
@@ -236,7 +236,7 @@ def test_mixed_device_form_checks_scratch_and_aliasing_without_a_gpu():
     from pyrenderer_amd import _native as N
     L = N.lib()
     W, H = 70, 130
-    need = L.prt_denoise_var_work_bytes(W, H)   # no new scratch: the select kernel works in the estimate's planes
+    need = L.prt_denoise_var_work_bytes(W, H)   # no new scratch: the estimate's kernel selects as it writes its planes
     par = np.array(VAR_GOOD, np.float32)
 
     def dev(color=FAKE, in_var=FAKE * 7, out=FAKE * 2, var=None, work=FAKE * 3, size=need):

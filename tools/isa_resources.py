@@ -2,7 +2,8 @@
 
     python tools/isa_resources.py <outdir> [--src <tree>]      (writes <outdir>/resources.txt and the listings)
 
-Compiles the build's device units (the 8 prt_trace_inst.hip sets, prt_trace_pool.hip, prt_kernels.hip) with
+Compiles the build's device units (the 8 prt_trace_inst.hip sets, prt_trace_pool.hip, prt_kernels.hip and the
+denoiser's prt_denoise.hip) with
 build.py's flags and per-unit flags plus `--cuda-device-only -S`, and records per kernel: VGPRs, SGPRs,
 spilled VGPRs / SGPRs, scratch bytes, static LDS bytes and the instruction count.  `--src` points at another
 checkout (e.g. a worktree of the parent commit) to build the table a change is compared with; two tables
@@ -30,7 +31,7 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     csrc = os.path.join(a.src, "pyrenderer_amd", "csrc")
     units = [(f"trace_{s}_{t}", B.TRACE_INST, [f"-DPRT_STACK={s}", f"-DPRT_STATS={t}"]) for s, t in B.TRACE_SETS]
-    units += [(os.path.splitext(f)[0], f, B.UNIT_FLAGS.get(f, [])) for f in ("prt_trace_pool.hip", "prt_kernels.hip")]
+    units += [(os.path.splitext(f)[0], f, B.UNIT_FLAGS.get(f, [])) for f in ("prt_trace_pool.hip", "prt_kernels.hip", "prt_denoise.hip")]
     # the pooled kernel's units for the wider trees (a parent tree without them has no POOL_WIDE)
     units += [(f"prt_trace_pool{w}", B.POOL_UNIT, B.UNIT_FLAGS[B.POOL_UNIT] + [f"-DPRT_POOL_WIDTH={w}"])
               for w, _ in getattr(B, "POOL_WIDE", []) if a.src == ROOT]
@@ -67,7 +68,7 @@ def main():
                 counts[cur] += bool(t) and not t.startswith(".") and not t.endswith(":")
         names = subprocess.run(["c++filt"], input="\n".join(meta), capture_output=True, text=True).stdout.split("\n")
         for k, pretty in zip(meta, names):
-            pretty = re.sub(r"\(.*\)$", "", pretty.replace("prt::(anonymous namespace)::", "").replace("void ", ""))
+            pretty = re.sub(r"\(.*\)$", "", re.sub(r"prt(_dn)?::\(anonymous namespace\)::", "", pretty).replace("void ", ""))
             rows.append(f"{name} {pretty} {' '.join(meta[k].get(x, '?') for x in KEYS)} {counts.get(k, 0)}")
     table = "# unit kernel vgpr sgpr vgpr_spill sgpr_spill scratch lds insts\n" + "\n".join(sorted(rows)) + "\n"
     open(os.path.join(a.out, "resources.txt"), "w").write(table)

@@ -339,7 +339,11 @@ int prt_features_device(void* scene, const float* cam, int W, int H, int first_s
                         uint32_t flags, float* d_out, void* stream);
 /* trace-kernel variant chosen for this scene's large launches when flags select none:
  * out4 = {variant, BVH arity (4, or 8: an LDS reference kernel over the scene's eight-wide tree, env
- *         PRT_LDS_WIDTH), bit 0 scene LDS-resident | bit 1 quantised nodes,
+ *         PRT_LDS_WIDTH), bit 0 scene LDS-resident | bit 1 quantised nodes | bit 2 (4) the scene's
+ *         shade_fast: every albedo in [2^-40, 2^40] and every face normal's length in [0.5, 2], so the LDS
+ *         kernels' shading quotients run under their cheap guards; clear: under div3's | bit 3 (8) the
+ *         scene is plain: no sphere, metal or dielectric (bits 2 and 3 are the uploaded scene's own
+ *         flags, the same for every launch),
  *         LDS traversal stack entries per lane: the instantiation set, or for the pooled kernel
  *         (7 / 8) the exact bound of its tree that its stack is sized to} */
 int prt_scene_kernel(void* scene, int32_t* out4);

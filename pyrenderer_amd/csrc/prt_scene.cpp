@@ -295,7 +295,8 @@ int prt_launch_kernel(void* scene, int64_t n_items, uint32_t flags, int32_t* out
     int var = launch_variant(s, flags);
     out4[0] = var;
     out4[1] = variant_width(s, var);
-    out4[2] = (variant_uses_lds(var) ? 1 : 0) | (variant_quantized(var) ? 2 : 0);
+    out4[2] = (variant_uses_lds(var) ? 1 : 0) | (variant_quantized(var) ? 2 : 0) | (s->shade_fast ? 4 : 0) |
+              (s->plain ? 8 : 0);
     // the pooled kernel's LDS stack is sized to its tree's exact bound (P.lds_stack)
     out4[3] = variant_pool(var) ? variant_need(s, var) : variant_stack(s, var);
     return PRT_OK;

@@ -241,14 +241,16 @@ class DeviceScene:
 
     def kernel_info(self, n_items=None, flags=0):
         """Trace-kernel variant of a launch of n_items work items (default: a large one) with these
-        render flags: dict(variant, bvh_arity, lds_scene, quantized, stack)."""
+        render flags: dict(variant, bvh_arity, lds_scene, quantized, stack), and the uploaded scene's own
+        shade_fast (the cheap shading guards are valid) and plain (no sphere, metal or dielectric)."""
         out = np.zeros(4, np.int32)
         if n_items is None:
             N.check(N.lib().prt_scene_kernel(self.h, N.ptr(out)))
         else:
             N.check(N.lib().prt_launch_kernel(self.h, int(n_items), flags, N.ptr(out)))
         return dict(variant=int(out[0]), bvh_arity=int(out[1]), lds_scene=bool(out[2] & 1),
-                    quantized=bool(out[2] & 2), stack=int(out[3]))
+                    quantized=bool(out[2] & 2), stack=int(out[3]), shade_fast=bool(out[2] & 4),
+                    plain=bool(out[2] & 8))
 
     def kernel_timing(self):
         ms = ctypes.c_double(0.0)

@@ -17,7 +17,8 @@ from pyrenderer_amd.flatten import FlatScene
 from test_gpu_hits import _axis_rays, _rays
 
 # rho.rgb, emit, sided, type, ior, roughness (hard_scenes._GREY); albedos inside [2^-40, 2^40], so the
-# kernels keep their cheap shading guards (TraceParams::shade_fast) on all of these scenes
+# kernels keep their cheap shading guards (TraceParams::shade_fast) on all of these scenes; the other side,
+# and albedos on the bounds themselves, are in tests/shade_cases.py
 ROWS = {
     "glass": [0.9, 0.9, 0.9, 0, 0, 3, 1.5, 0],
     "ior2.4": [0.95, 0.9, 0.85, 0, 0, 3, 2.4, 0],

@@ -46,7 +46,8 @@ extern "C" {
  * additive, no existing entry point changed): the denoiser's four entry points at the end of this
  * header, then the three of its variance-guided mode (prt_denoise_var*), then the four of the
  * sample-moments variance (prt_moments_add*, prt_denoise_var_given*), then the four of the temporal
- * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*). */
+ * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*), then the two of adaptive sampling
+ * (prt_adaptive_update*). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -591,6 +592,58 @@ int prt_denoise_var_mixed(int device, const float* color, const float* feat, con
 int prt_denoise_var_mixed_device(int device, const float* d_color, const float* d_feat, const float* d_in_var,
                                  int W, int H, int iterations, const float* params5, float* d_out,
                                  float* d_out_var, void* d_work, int64_t work_bytes, void* stream);
+
+/* Adaptive sampling.  Added under ABI 4, purely additive.  Random streams are keyed by
+ * (seed, pixel, sample) and every render entry point takes a tile list, so batch b of a subset of tiles
+ * holds, for those tiles, exactly the bits a full-frame render of batch b would.  One fused kernel folds
+ * such a batch into the frame's radiance sums and its prt_moments_add state and scores every listed tile
+ * against a noise target; the caller stops rendering the tiles that have converged.
+ *   batch      n_tiles * tw * th x 3 f32: the radiance SUMS of n_samples samples of the tiles tile_ids, in
+ *              the slot order of prt_render_tiles (tile-major, then row ly, then column lx); slots outside
+ *              the frame hold 0 and are ignored
+ *   tile_ids   n_tiles i32, a HOST pointer in both forms (read before the call returns);
+ *              id = ty * ceil(W / tw) + tx.  n_tiles == 0 is PRT_OK and does nothing
+ *   tw, th     powers of two with tw * th in 64..2^20 (the render calls' rule);  W, H in 1..32768
+ *   feat       W x H x 8 f32, as for prt_denoise; eps_a > 0 and finite
+ *   n_samples  samples per batch, finite and >= 1 (every call on one state must use the same count)
+ *   params2    eps_r > 0 and finite (the floor of the relative error's denominator), target >= 0 (+inf
+ *              is allowed: only young pixels then hold a tile)
+ *   io_sum     W x H x 3 f32 [x][y], updated in place
+ *   io_state   W x H x 4 f32 [x][y], the state of prt_moments_add (k, mean, M2, var_mean), updated in place
+ *   records    n_tiles x 4 u32 in the order of tile_ids, written
+ * For every pixel of every listed tile that lies inside the frame, every operation one IEEE f32 operation in
+ * this association (tests/adaptive_ref.py restates it in NumPy):
+ *  1. io_sum_c = io_sum_c + S_c.
+ *  2. prt_moments_add's update for the one frame S with its closing step: c = S / n_samples;
+ *     I_c = feat[7] > 0 ? c_c / fmax(A_c, eps_a) : c_c;  l = (0.2126 I_r + 0.7152 I_g) + 0.0722 I_b;  a batch whose
+ *     l is not finite leaves k, mean and M2 as they are;  k' = k + 1;  d = l - mean;  mean' = mean + d / k';
+ *     M2' = M2 + d * (l - mean');  var_mean = k' >= 2 ? (M2' / (k' - 1)) / k' : 0, stored as 0 when not finite.
+ *  3. e = sqrt(fmax(var_mean, 0)) / (|mean'| + eps_r), a var_mean of -0 counting as +0: the relative standard
+ *     error of the demodulated luminance.
+ *  4. The pixel is young if k' < 2, and over if it is young or e > target.
+ * The record of a tile: [0] its pixels inside the frame, [1] those that are over, [2] the bits of the
+ * greatest e among those that are not young (0 if there is none), [3] those that are young.  The counts are
+ * integers and the greatest of non-negative floats is the greatest of their bit patterns as integers, so
+ * the four words do not depend on the order in which the pixels are combined: they are reproducible bit for
+ * bit.  No sum of e over a tile is offered, because it would not be.  Pixels of tiles that are not listed,
+ * and everything outside the frame, are neither read nor written by the kernel (the host form copies the
+ * whole planes up and down: such pixels come back with the bits they had).  Finiteness: prt_moments_add's
+ * statement holds for the state; with a finite state e is finite and >= +0.
+ * Host pointers, synchronous.  Bad arguments (a NULL pointer with n_tiles > 0 or a NULL params2, W or H
+ * outside 1..32768, tw or th not a power of two or tw * th outside 64..2^20, n_tiles < 0 or
+ * n_tiles * tw * th >= 2^31, a tile id out of range, a tile id listed twice — two blocks would update the
+ * same pixels —, n_samples not finite or < 1, eps_a or eps_r not positive and finite, a target that is NaN
+ * or negative) return PRT_ERR_ARG before any device is touched, with the text in prt_denoise_last_error. */
+int prt_adaptive_update(int device, const float* batch, const int32_t* tile_ids, int n_tiles, int tw, int th, int W,
+                        int H, const float* feat, float eps_a, float n_samples, const float* params2, float* io_sum,
+                        float* io_state, uint32_t* records);
+/* prt_adaptive_update on device pointers (tile_ids and params2 stay host pointers), enqueued on `stream` with
+ * no host synchronisation: d_records is zeroed on the stream, then the tile ids travel in the kernel
+ * arguments, 896 tiles to a launch.  d_io_state must be 16-byte aligned; d_io_sum, d_io_state and d_records
+ * must not overlap each other, d_batch or d_feat. */
+int prt_adaptive_update_device(int device, const float* d_batch, const int32_t* tile_ids, int n_tiles, int tw, int th,
+                               int W, int H, const float* d_feat, float eps_a, float n_samples, const float* params2,
+                               float* d_io_sum, float* d_io_state, uint32_t* d_records, void* stream);
 
 #ifdef __cplusplus
 }

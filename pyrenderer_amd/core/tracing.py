@@ -21,6 +21,9 @@ save / load to resume an accumulation.
 
 `TemporalAccumulator` / `render_sequence` render a camera path and carry the history across camera
 moves (pyrenderer_amd.denoise.temporal_accumulate, DESIGN.md §11 "Temporal accumulation").
+
+`render_adaptive` renders in batches and stops the tiles whose noise has reached a target
+(pyrenderer_amd.adaptive.AdaptiveAccumulator); that module is imported only there.
 """
 import hashlib
 import os
@@ -149,11 +152,13 @@ class _Frame:
         slots, _ = self.ds.render_tiles(self.cam, W, H, t, t, self.ids, spp, self.depth, self.seed, self.flags)
         return self.unpack(slots)
 
-    def add_samples(self, first_sample, spp, onto=None):
+    def add_samples(self, first_sample, spp, onto=None, ids=None):
         """Samples first_sample .. first_sample + spp - 1 added in sample order onto the slot sums `onto`
-        (modified in place and returned); by default onto zero sums, which makes them one batch."""
-        t, slots = self.tile, self.zero_slots() if onto is None else onto
-        return self.ds.render_tiles_accumulate(self.cam, self.W, self.H, t, t, self.ids, first_sample, spp,
+        (modified in place and returned); by default onto zero sums, which makes them one batch.  ids: the
+        tiles to render, in the slots' order (default: every tile of the frame)."""
+        t, ids = self.tile, self.ids if ids is None else np.ascontiguousarray(ids, np.int32)
+        slots = np.zeros((ids.shape[0] * t * t, 3), np.float32) if onto is None else onto
+        return self.ds.render_tiles_accumulate(self.cam, self.W, self.H, t, t, ids, first_sample, spp,
                                                self.depth, slots, self.seed, self.flags)
 
     def batches(self, spp, K):
@@ -500,6 +505,32 @@ def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, devi
         acc.add(cam)
         out.append(acc.denoised() if denoise else acc.accumulated())
     return np.stack(out).astype(np.float32)
+
+
+def render_adaptive(scene, camera, *, depth, batch_spp, max_batches, target, min_batches=2, tolerate=0.0, eps_r=None,
+                    seed=0, resolution=None, device=0, tile=64, world=None, nee="reference", denoise=False,
+                    return_samples=False):
+    """Mean linear radiance (W, H, 3) float32 rendered in batches of batch_spp samples, at most max_batches of
+    them per tile, that stops every tile once its noise has reached `target`
+    (pyrenderer_amd.adaptive.AdaptiveAccumulator, whose parameters these are): run(max_batches)
+    followed by mean(), or by denoised() for denoise=True (the fixed filter) or "variance".  With
+    return_samples=True the pair (image, (W, H) int32 samples per pixel).  One device; render() and its
+    defaults are untouched by it."""
+    if not (isinstance(denoise, (bool, np.bool_)) or (isinstance(denoise, str) and denoise == "variance")):
+        raise ValueError(f"denoise must be False, True or 'variance', not {denoise!r}")
+    if isinstance(max_batches, (bool, np.bool_)) or not isinstance(max_batches, (int, np.integer)) or max_batches < 1:
+        raise ValueError(f"max_batches must be an integer >= 1, not {max_batches!r}")
+    from .. import adaptive as A   # imports torch: only this entry point pays for it
+    kw = {} if eps_r is None else dict(eps_r=eps_r)
+    acc = A.AdaptiveAccumulator(scene, camera, depth=depth, batch_spp=batch_spp, target=target,
+                                min_batches=min_batches, tolerate=tolerate, seed=seed, resolution=resolution,
+                                device=device, tile=tile, world=world, nee=nee, **kw)
+    acc.run(int(max_batches))
+    if not denoise:
+        img = acc.mean()
+    else:
+        img = acc.denoised("variance" if isinstance(denoise, str) else "fixed")
+    return (img, acc.samples()) if return_samples else img
 
 
 def scene_fingerprint(flat):

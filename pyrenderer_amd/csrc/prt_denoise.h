@@ -87,4 +87,28 @@ hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const flo
 hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch, float n_samples, const float* d_feat,
                            float eps_a, int W, int H, float* d_io_state, hipStream_t stream);
 
+// ---- adaptive sampling ----
+constexpr int kMinTilePixels = 64, kMaxTilePixels = 1 << 20;   // tw * th, the render calls' rule
+
+struct AdaptiveParams {
+    float n_samples, eps_a, eps_r, target;
+};
+
+// Enqueue adaptive_kernel on `stream` of the current device: one batch of the tiles `tile_ids` (d_batch:
+// n_tiles * tw * th x 3 radiance sums of n_samples samples in the render calls' slot order) added onto
+// d_io_sum (W x H x 3), folded into the moments state d_io_state (W x H x 4, 16-byte aligned) by
+// moments_kernel's update for one frame, and the n_tiles x 4 words of d_records (zeroed on the stream first)
+// filled with each tile's in-frame pixels, pixels over the target, bits of the greatest relative standard
+// error among the pixels with two batches or more, and pixels with fewer.  tile_ids is a HOST pointer, read
+// before the call returns; the caller has validated it: every id inside the ceil(W / tw) x ceil(H / th)
+// grid and none twice (two blocks would race on the same pixels), tw and th powers of two with
+// tw * th in kMinTilePixels..kMaxTilePixels, n_tiles >= 1 and n_tiles * tw * th < 2^31.  Pixels of tiles not
+// listed are neither read nor written.
+//
+// Finiteness: prt_moments_add's statement holds for the state.  With a finite state the relative standard
+// error sqrt(max(var_mean, 0)) / (|mean| + eps_r) is finite and >= +0, so its bits order as the floats do.
+hipError_t enqueue_adaptive(const float* d_batch, const int32_t* tile_ids, int n_tiles, int tw, int th, int W, int H,
+                            const float* d_feat, const AdaptiveParams& p, float* d_io_sum, float* d_io_state,
+                            uint32_t* d_records, hipStream_t stream);
+
 }  // namespace prt_dn

@@ -9,7 +9,9 @@
 // y: the 16-byte loads of a tap are contiguous over a wave.  Taps come straight from global memory, except in the variance estimate
 // of the variance-guided mode, which stages its 7 x 7 windows in LDS.  The sample-moments kernels at the
 // end (moments_kernel, var_given_kernel) read and write each pixel once and take no taps;
-// temporal_kernel, the last one, gathers four taps per pixel from the previous frame's planes.
+// adaptive_kernel, which shares moments_kernel's update, is the one kernel with a mapping of its own
+// (tile chunks, its batch transposed through LDS); temporal_kernel, the last one, gathers four taps per
+// pixel from the previous frame's planes.
 #include "prt_denoise.h"
 
 namespace prt_dn {
@@ -365,6 +367,32 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void var_given_kernel(const float
     store_repacked(p, ip, var, iv, zp, out_var);
 }
 
+// ---- the moments update, shared by moments_kernel and adaptive_kernel ----
+
+// the demodulated luminance of the mean of a batch of n samples with the radiance sums S
+__device__ __forceinline__ float batch_luminance(const Rgb& S, float n, bool hit, const Rgb& a) {
+    Rgb i = {S.r / n, S.g / n, S.b / n};
+    if (hit) i = demodulate(i, a);
+    return lum(i.r, i.g, i.b);
+}
+
+// Welford's update with one batch luminance; one that is not finite is skipped
+__device__ __forceinline__ void welford_add(float& k, float& mean, float& m2, float l) {
+    if (!finite_f(l)) return;
+    k = k + 1.0f;
+    const float d = l - mean;
+    mean = mean + d / k;
+    m2 = m2 + d * (l - mean);
+}
+
+// the closing step: the variance of the mean over the k batches seen, 0 below two and where it is not finite
+__device__ __forceinline__ float variance_of_mean(float k, float m2) {
+    float vm = 0.0f;
+    if (k >= 2.0f) vm = (m2 / (k - 1.0f)) / k;
+    if (!finite_f(vm)) vm = 0.0f;
+    return vm;
+}
+
 // running Welford update of the demodulated luminance of the batch means over n_frames frames of
 // radiance sums; state (k, mean, M2, var_mean) per pixel, one 16-byte load and store
 __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* __restrict__ sums, int n_frames,
@@ -379,21 +407,109 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void moments_kernel(const float* 
     const Rgb a = albedo_floor(f, eps_a);
     const float4 s = state[p];
     float k = s.x, mean = s.y, m2 = s.z;
-    for (int fr = 0; fr < n_frames; ++fr) {
-        const float* S = sums + (size_t)fr * frame_pitch + p * 3;
-        Rgb i = {S[0] / n, S[1] / n, S[2] / n};
-        if (hit) i = demodulate(i, a);
-        const float l = lum(i.r, i.g, i.b);
-        if (!finite_f(l)) continue;
-        k = k + 1.0f;
-        const float d = l - mean;
-        mean = mean + d / k;
-        m2 = m2 + d * (l - mean);
+    for (int fr = 0; fr < n_frames; ++fr)
+        welford_add(k, mean, m2, batch_luminance(load_rgb(sums + (size_t)fr * frame_pitch + p * 3), n, hit, a));
+    state[p] = make_float4(k, mean, m2, variance_of_mean(k, m2));
+}
+
+// ---- adaptive sampling (tests/adaptive_ref.py restates it) ----
+// One batch of a list of tiles folded into the frame's sums and moments, and every listed tile scored
+// against the noise target.  The batch comes in the render calls' slot order (tile-major, then row ly, then
+// column lx: x-contiguous), the frame planes are [x][y] (y-contiguous): a block takes one chunk of one
+// tile, kChunk pixels as cx x cy, reads the chunk's rows of the batch along x (coalesced) into LDS, and
+// turns to lanes along y for the planes, cy pixels (16 B of state each) contiguous per column.  The rows
+// are padded by one float, so the transposed read has an odd stride.
+//
+// The tile ids travel in the kernel arguments, kTilesPerLaunch to a launch: the unit keeps no device
+// buffer of its own and enqueues no copy from host memory that would have to outlive the call.
+constexpr int kChunk = 256;             // pixels of a chunk, threads of a block
+constexpr int kChunkFloats = 1024;      // the most a chunk's padded rows take: cx = 1, cy = 256
+constexpr int kTilesPerLaunch = 896;    // 3584 of the 4096 bytes of kernel arguments
+
+struct TileIds {
+    int32_t id[kTilesPerLaunch];
+};
+
+// the shapes of tile and chunk as shifts, and the frame
+struct AdaptiveShape {
+    int W, H, tiles_x, log_tw, log_th, log_cx, log_cy;
+};
+
+__global__ __launch_bounds__(kChunk) void adaptive_kernel(const float* __restrict__ batch, const TileIds ids,
+                                                          int first_tile, const AdaptiveShape g,
+                                                          const float* __restrict__ feat, const AdaptiveParams P,
+                                                          float* __restrict__ io_sum, float4* __restrict__ io_state,
+                                                          uint32_t* __restrict__ records) {
+    __shared__ float s_batch[kChunkFloats];
+    __shared__ uint32_t s_rec[4];
+    const int tid = (int)threadIdx.x;
+    const int log_nx = g.log_tw - g.log_cx, log_chunks = log_nx + (g.log_th - g.log_cy);
+    const int tile = (int)(blockIdx.x >> log_chunks), chunk = (int)(blockIdx.x & ((1u << log_chunks) - 1u));
+    const int id = ids.id[tile];
+    // the chunk's origin in the tile and in the frame
+    const int lx0 = (chunk & ((1 << log_nx) - 1)) << g.log_cx, ly0 = (chunk >> log_nx) << g.log_cy;
+    const int x0 = ((id % g.tiles_x) << g.log_tw) + lx0, y0 = ((id / g.tiles_x) << g.log_th) + ly0;
+    if (x0 >= g.W || y0 >= g.H) return;   // the whole chunk lies outside the frame (the whole block returns)
+    if (tid < 4) s_rec[tid] = 0u;
+
+    // 1. the chunk's rows of the batch, lanes along x; slots outside the frame are not read
+    const int row_floats = 3 << g.log_cx, pitch = row_floats + 1;
+    const size_t slot0 = ((size_t)(first_tile + tile) << (g.log_tw + g.log_th)) + ((size_t)ly0 << g.log_tw) + (size_t)lx0;
+    for (int i = tid; i < (row_floats << g.log_cy); i += kChunk) {
+        const int row = (i >> g.log_cx) / 3, col = i - row * row_floats;
+        if (x0 + col / 3 < g.W && y0 + row < g.H)
+            s_batch[row * pitch + col] = batch[(slot0 + ((size_t)row << g.log_tw)) * 3 + (size_t)col];
     }
-    float vm = 0.0f;
-    if (k >= 2.0f) vm = (m2 / (k - 1.0f)) / k;
-    if (!finite_f(vm)) vm = 0.0f;
-    state[p] = make_float4(k, mean, m2, vm);
+    __syncthreads();
+
+    // 2. the pixel of this lane, lanes along y
+    const int lx = tid >> g.log_cy, ly = tid & ((1 << g.log_cy) - 1);
+    const int x = x0 + lx, y = y0 + ly;
+    const bool in = tid < (1 << (g.log_cx + g.log_cy)) && x < g.W && y < g.H;
+    bool young = false, over = false;
+    uint32_t e_bits = 0u;
+    if (in) {
+        const size_t p = (size_t)x * (size_t)g.H + (size_t)y;
+        const float* sb = s_batch + ly * pitch + lx * 3;
+        const Rgb S = load_rgb(sb);
+        const Rgb sum = load_rgb(io_sum + p * 3);
+        store_rgb(io_sum + p * 3, {sum.r + S.r, sum.g + S.g, sum.b + S.b});
+        const float* f = feat + p * 8;
+        const bool hit = f[7] > 0.0f;
+        const Rgb a = albedo_floor(f, P.eps_a);
+        const float4 s = io_state[p];
+        float k = s.x, mean = s.y, m2 = s.z;
+        welford_add(k, mean, m2, batch_luminance(S, P.n_samples, hit, a));
+        const float vm = variance_of_mean(k, m2);
+        io_state[p] = make_float4(k, mean, m2, vm);
+        // 3. the relative standard error; fmaxf(vm, 0) with the zero's sign settled: a -0 counts as +0
+        const float e = sqrtf(vm > 0.0f ? vm : 0.0f) / (fabsf(mean) + P.eps_r);
+        young = k < 2.0f;
+        over = young || e > P.target;
+        if (!young) e_bits = __float_as_uint(e);
+    }
+
+    // 4. the tile's record: counts by ballot, the maximum of the non-negative floats as an integer maximum of
+    //    their bits; one LDS atomic per wave, one global atomic per block and word
+    const unsigned long long m_in = __ballot(in), m_over = __ballot(over), m_young = __ballot(young);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)e_bits, off);
+        e_bits = o > e_bits ? o : e_bits;
+    }
+    if ((tid & 63) == 0) {
+        atomicAdd(&s_rec[0], (uint32_t)__popcll(m_in));
+        atomicAdd(&s_rec[1], (uint32_t)__popcll(m_over));
+        atomicMax(&s_rec[2], e_bits);
+        atomicAdd(&s_rec[3], (uint32_t)__popcll(m_young));
+    }
+    __syncthreads();
+    if (tid < 4) {
+        uint32_t* r = records + (size_t)(first_tile + tile) * 4 + tid;
+        const uint32_t v = s_rec[tid];
+        if (tid == 2) atomicMax(r, v);
+        else atomicAdd(r, v);
+    }
 }
 
 // ---- temporal accumulation (DESIGN.md §11 "Temporal accumulation"; tests/temporal_ref.py restates it) ----
@@ -616,6 +732,35 @@ hipError_t enqueue_moments(const float* d_sums, int n_frames, size_t frame_pitch
                            float eps_a, int W, int H, float* d_io_state, hipStream_t stream) {
     return launch(moments_kernel, W, H, stream, d_sums, n_frames, frame_pitch, n_samples, d_feat, W, H, eps_a,
                   reinterpret_cast<float4*>(d_io_state));
+}
+
+hipError_t enqueue_adaptive(const float* d_batch, const int32_t* tile_ids, int n_tiles, int tw, int th, int W, int H,
+                            const float* d_feat, const AdaptiveParams& p, float* d_io_sum, float* d_io_state,
+                            uint32_t* d_records, hipStream_t stream) {
+    AdaptiveShape g = {};
+    g.W = W;
+    g.H = H;
+    g.tiles_x = (W + tw - 1) / tw;
+    g.log_tw = __builtin_ctz((unsigned)tw);
+    g.log_th = __builtin_ctz((unsigned)th);
+    // the chunk: up to 16 pixels along x and the rest of the kChunk along y, widened along x where the tile is flat
+    const int log_chunk = __builtin_ctz((unsigned)kChunk);
+    g.log_cx = g.log_tw < 4 ? g.log_tw : 4;
+    g.log_cy = g.log_th < log_chunk - g.log_cx ? g.log_th : log_chunk - g.log_cx;
+    if (g.log_tw < log_chunk - g.log_cy) g.log_cx = g.log_tw;
+    else g.log_cx = log_chunk - g.log_cy;
+    const int log_chunks = (g.log_tw - g.log_cx) + (g.log_th - g.log_cy);
+    (void)hipGetLastError();
+    hipError_t e = hipMemsetAsync(d_records, 0, (size_t)n_tiles * 4 * sizeof(uint32_t), stream);
+    TileIds ids;
+    for (int first = 0; first < n_tiles && e == hipSuccess; first += kTilesPerLaunch) {
+        const int n = n_tiles - first < kTilesPerLaunch ? n_tiles - first : kTilesPerLaunch;
+        for (int i = 0; i < kTilesPerLaunch; ++i) ids.id[i] = i < n ? tile_ids[first + i] : 0;
+        adaptive_kernel<<<dim3((unsigned)n << log_chunks), dim3(kChunk), 0, stream>>>(
+            d_batch, ids, first, g, d_feat, p, d_io_sum, reinterpret_cast<float4*>(d_io_state), d_records);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,

@@ -5,6 +5,7 @@
 // before any HIP call, so a rejected call never touches a device.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -184,6 +185,43 @@ int check_moments_args(const std::string& who, int device, int n_frames, int64_t
     if (!std::isfinite(n_samples) || n_samples < 1.0f)
         return fail(PRT_ERR_ARG, who + ": n_samples must be finite and >= 1");
     if (!positive_finite(eps_a)) return fail(PRT_ERR_ARG, who + ": eps_a must be positive and finite");
+    return PRT_OK;
+}
+
+// Checks of the adaptive entry points that come before the tile list is read: the frame, the tile shape (the
+// render calls' rule), the samples per batch and params2 = eps_r, target; fills `p`.
+int check_adaptive_params(const std::string& who, int device, int n_tiles, int tw, int th, int W, int H, float eps_a,
+                          float n_samples, const float* params2, prt_dn::AdaptiveParams* p) {
+    DN_TRY(check_frame(who, device, W, H));
+    if (tw < 1 || th < 1 || (tw & (tw - 1)) || (th & (th - 1)) || (int64_t)tw * th < prt_dn::kMinTilePixels ||
+        (int64_t)tw * th > prt_dn::kMaxTilePixels)
+        return fail(PRT_ERR_ARG, who + ": tw and th must be powers of two with tw * th in 64..2^20");
+    if (n_tiles < 0) return fail(PRT_ERR_ARG, who + ": n_tiles must be >= 0");
+    if ((int64_t)n_tiles * tw * th >= ((int64_t)1 << 31))
+        return fail(PRT_ERR_ARG, who + ": n_tiles * tw * th must stay below 2^31 slots");
+    if (!std::isfinite(n_samples) || n_samples < 1.0f)
+        return fail(PRT_ERR_ARG, who + ": n_samples must be finite and >= 1");
+    if (!positive_finite(eps_a)) return fail(PRT_ERR_ARG, who + ": eps_a must be positive and finite");
+    if (!params2) return fail(PRT_ERR_ARG, who + ": params2 is NULL");
+    *p = {n_samples, eps_a, params2[0], params2[1]};
+    if (!positive_finite(p->eps_r)) return fail(PRT_ERR_ARG, who + ": eps_r must be positive and finite");
+    if (!(p->target >= 0.0f)) return fail(PRT_ERR_ARG, who + ": target must be >= 0 (+inf is allowed), not NaN");
+    return PRT_OK;
+}
+
+// The tile list of an adaptive call: every id inside the frame's tile grid and none listed twice.  No index is
+// formed from an id before this has passed.
+int check_tile_list(const std::string& who, const int32_t* tile_ids, int n_tiles, int tw, int th, int W, int H) {
+    const int64_t n_grid = (int64_t)((W + tw - 1) / tw) * (int64_t)((H + th - 1) / th);
+    for (int i = 0; i < n_tiles; ++i)
+        if (tile_ids[i] < 0 || tile_ids[i] >= n_grid)
+            return fail(PRT_ERR_ARG, who + ": tile id out of range: " + std::to_string(tile_ids[i]));
+    std::vector<int32_t> sorted(tile_ids, tile_ids + n_tiles);
+    std::sort(sorted.begin(), sorted.end());
+    const auto twice = std::adjacent_find(sorted.begin(), sorted.end());
+    if (twice != sorted.end())
+        return fail(PRT_ERR_ARG, who + ": tile id listed twice: " + std::to_string(*twice) +
+                                       " (two blocks would update the same pixels)");
     return PRT_OK;
 }
 
@@ -455,6 +493,54 @@ int prt_temporal_accumulate(int device, const float* color, const float* feat, c
     DN_HIP_TRY(s.upload());
     DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
                                         d_state, d_out_color, d_out_var, nullptr));
+    DN_HIP_TRY(s.download());
+    return PRT_OK;
+}
+
+// ---- adaptive sampling ----
+
+int prt_adaptive_update_device(int device, const float* d_batch, const int32_t* tile_ids, int n_tiles, int tw, int th,
+                               int W, int H, const float* d_feat, float eps_a, float n_samples, const float* params2,
+                               float* d_io_sum, float* d_io_state, uint32_t* d_records, void* stream) {
+    const std::string who("prt_adaptive_update_device");
+    prt_dn::AdaptiveParams p;
+    DN_TRY(check_adaptive_params(who, device, n_tiles, tw, th, W, H, eps_a, n_samples, params2, &p));
+    if (n_tiles == 0) return PRT_OK;
+    if (!d_batch || !tile_ids || !d_feat || !d_io_sum || !d_io_state || !d_records)
+        return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    if (reinterpret_cast<uintptr_t>(d_io_state) % 16 != 0)
+        return fail(PRT_ERR_ARG, who + ": d_io_state must be 16-byte aligned");
+    DN_TRY(check_tile_list(who, tile_ids, n_tiles, tw, th, W, H));
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
+    DN_HIP_TRY(prt_dn::enqueue_adaptive(d_batch, tile_ids, n_tiles, tw, th, W, H, d_feat, p, d_io_sum, d_io_state,
+                                        d_records, static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+int prt_adaptive_update(int device, const float* batch, const int32_t* tile_ids, int n_tiles, int tw, int th, int W,
+                        int H, const float* feat, float eps_a, float n_samples, const float* params2, float* io_sum,
+                        float* io_state, uint32_t* records) {
+    const std::string who("prt_adaptive_update");
+    prt_dn::AdaptiveParams p;
+    DN_TRY(check_adaptive_params(who, device, n_tiles, tw, th, W, H, eps_a, n_samples, params2, &p));
+    if (n_tiles == 0) return PRT_OK;
+    if (!batch || !tile_ids || !feat || !io_sum || !io_state || !records) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_tile_list(who, tile_ids, n_tiles, tw, th, W, H));
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
+    const size_t n = (size_t)W * (size_t)H;
+    Staging s;
+    // the planes travel whole: the pixels of tiles not listed come back with the bits they went up with
+    const float* d_batch = s.in(batch, (size_t)n_tiles * (size_t)tw * (size_t)th * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    float* d_sum = s.inout(io_sum, n * 3);
+    float* d_state = s.inout(io_state, n * 4);
+    uint32_t* d_records = static_cast<uint32_t*>(s.bytes((size_t)n_tiles * 4 * sizeof(uint32_t), nullptr, records));
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(prt_dn::enqueue_adaptive(d_batch, tile_ids, n_tiles, tw, th, W, H, d_feat, p, d_sum, d_state, d_records,
+                                        nullptr));
     DN_HIP_TRY(s.download());
     return PRT_OK;
 }

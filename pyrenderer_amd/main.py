@@ -10,6 +10,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd --samples 8 --denoise --denoise-mode variance    # width from the image's own noise
     python -m pyrenderer_amd --samples 64 --denoise --denoise-mode variance --variance-batches 8   # ... from sample moments
     python -m pyrenderer_amd --samples 2 --frames 24 --orbit 2 --temporal --denoise --denoise-mode variance   # turntable
+    python -m pyrenderer_amd --adaptive 0.05 --batch-spp 8 --max-samples 256              # until the noise is below 5 %
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
 no CPU fallback.
@@ -79,7 +80,20 @@ def parse(argv=None):
                     help="with --frames: carry the previous frame's colour and luminance moments into the next "
                          "camera (temporal accumulation); filtered with --denoise --denoise-mode variance, or "
                          "written as accumulated without --denoise")
+    ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
+                    help="adaptive sampling: render in batches of --batch-spp and stop every 64 x 64 tile once the "
+                         "relative standard error of its pixels' demodulated luminance is at most TARGET; needs "
+                         "--batch-spp and --max-samples (--samples is not used); one device, one image")
+    ap.add_argument("--batch-spp", type=int, default=None, metavar="N", help="with --adaptive: samples per batch")
+    ap.add_argument("--max-samples", type=int, default=None, metavar="M",
+                    help="with --adaptive: the most samples a pixel gets, a multiple of --batch-spp")
+    ap.add_argument("--min-batches", type=int, default=None, metavar="B",
+                    help="with --adaptive: batches every tile gets before it may stop (default 2, the least)")
+    ap.add_argument("--tolerate", type=float, default=None, metavar="F",
+                    help="with --adaptive: the share of a tile's pixels, in [0, 1), that may stay over TARGET "
+                         "(default 0)")
     args = ap.parse_args(argv)
+    _check_adaptive(ap, args)
     if args.denoise_iterations is not None:
         if not 0 <= args.denoise_iterations <= 8:
             ap.error(f"--denoise-iterations must be in 0..8, not {args.denoise_iterations}")
@@ -118,6 +132,51 @@ def parse(argv=None):
         # rounds <= 4 took a .npy FILE here; a directory named out.npy would silently replace it
         ap.error(f"--hdr takes a directory (hdr.npy and spp.npy are written into it), not a .npy file: {args.hdr}")
     return args
+
+
+def _check_adaptive(ap, args):
+    """--adaptive and its companions: complete, in range, and combined with nothing that renders otherwise."""
+    companions = (("--batch-spp", args.batch_spp), ("--max-samples", args.max_samples),
+                  ("--min-batches", args.min_batches), ("--tolerate", args.tolerate))
+    if args.adaptive is None:
+        for flag, value in companions:
+            if value is not None:
+                ap.error(f"{flag} needs --adaptive TARGET")
+        return
+    clash = [flag for flag, given in (("--devices", len(args.devices) != 1), ("--interval", args.interval > 0),
+                                      ("--variance-batches", args.variance_batches), ("--temporal", args.temporal),
+                                      ("--frames", args.frames), ("--state", args.state)) if given]
+    if clash:
+        ap.error(f"--adaptive renders one image in batches on one device and keeps its own moments: it cannot be "
+                 f"combined with {', '.join(clash)}")
+    if args.batch_spp is None or args.max_samples is None:
+        ap.error("--adaptive needs --batch-spp N and --max-samples M")
+    args.min_batches = 2 if args.min_batches is None else args.min_batches
+    args.tolerate = 0.0 if args.tolerate is None else args.tolerate
+    try:
+        from .adaptive import check_sampler   # the sampler's own rules; imports torch
+        check_sampler(args.batch_spp, args.adaptive, args.min_batches, args.tolerate, 1.0)
+    except ValueError as e:
+        ap.error(f"--adaptive: {e}")
+    if args.max_samples < args.batch_spp or args.max_samples % args.batch_spp:
+        ap.error(f"--adaptive: --max-samples ({args.max_samples}) must be a positive multiple of --batch-spp "
+                 f"({args.batch_spp})")
+
+
+def render_adaptively(args, scene, camera, W, H):
+    """--adaptive: an AdaptiveAccumulator run to --max-samples, with the share of the samples it spent printed."""
+    from .adaptive import AdaptiveAccumulator
+    acc = AdaptiveAccumulator(scene, camera, depth=args.depth, batch_spp=args.batch_spp, target=args.adaptive,
+                              min_batches=args.min_batches, tolerate=args.tolerate, seed=args.seed,
+                              resolution=(W, H), device=args.devices[0], nee=args.nee)
+    max_batches = args.max_samples // args.batch_spp
+    acc.run(max_batches)
+    per_tile = acc.batches_per_tile
+    print(f"adaptive: target {args.adaptive:g}, {acc.batches} of {max_batches} batches of {args.batch_spp} spp; "
+          f"{100.0 * acc.spent(max_batches):.1f} % of {args.max_samples} spp per pixel spent "
+          f"(tiles: {int(per_tile.min())}..{int(per_tile.max())} batches, {int(acc.active.sum())} of "
+          f"{per_tile.shape[0]} still over the target)", flush=True)
+    return acc
 
 
 def write_aov(directory, feat):
@@ -181,7 +240,12 @@ def main(argv=None):
     if args.frames:
         return render_frames(args, scene, camera, W, H)
     t0 = time.perf_counter()
-    if args.interval > 0 or args.state:
+    adaptive_samples = None
+    if args.adaptive is not None:
+        acc = render_adaptively(args, scene, camera, W, H)
+        adaptive_samples = acc.samples()
+        sums, samples, mean, denoised = acc.sums(), adaptive_samples, acc.mean(), acc.denoised
+    elif args.interval > 0 or args.state:
         if len(args.devices) != 1:
             raise SystemExit("progressive rendering (--interval/--state) runs on one device")
         state = Accumulator.state_path(args.state) if args.state else None
@@ -227,7 +291,9 @@ def main(argv=None):
         mean = _mean(sums, samples)
         denoised = functools.partial(frame.filter, mean, variance=variance)
     if args.aov:
-        write_aov(args.aov, frame.features())
+        write_aov(args.aov, acc.features() if adaptive_samples is not None else frame.features())
+        if adaptive_samples is not None:
+            np.save(os.path.join(args.aov, "samples.npy"), adaptive_samples)
     if args.denoise:
         it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
         mean, var = denoised(args.denoise_mode, iterations=it, return_variance=True)
@@ -235,8 +301,9 @@ def main(argv=None):
             np.save(os.path.join(args.aov, "variance.npy"), var)
     dt = time.perf_counter() - t0
     _write(args, sums, samples, mean)
-    print(f"{W}x{H} x {args.samples} spp, depth {args.depth}: {dt:.2f} s "
-          f"({W * H * args.samples / dt / 1e6:.1f} Msamples/s incl. scene build), mean RGB {mean.mean(axis=(0, 1))}")
+    spent = args.samples if adaptive_samples is None else round(float(adaptive_samples.mean()), 2)
+    print(f"{W}x{H} x {spent} spp, depth {args.depth}: {dt:.2f} s "
+          f"({W * H * spent / dt / 1e6:.1f} Msamples/s incl. scene build), mean RGB {mean.mean(axis=(0, 1))}")
     return mean
 
 

@@ -6,6 +6,7 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
     python tools/denoise_time.py --mode variance --sizes 512 4096   # the variance-guided mode (prt_denoise_var_device)
     python tools/denoise_time.py --mode given --sizes 512 4096      # ... with a given variance plane (prt_denoise_var_given_device)
     python tools/denoise_time.py --mode moments --sizes 512 4096    # prt_moments_add_device over --frames frames (default 8)
+    python tools/denoise_time.py --mode adaptive --sizes 512 4096   # prt_adaptive_update_device, tile 64: every tile, and every other one
     python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
     python tools/denoise_time.py --mode features --sizes 512 4096   # prt_features_device (1 and 8 samples); host wall clock of both compositions at 512^2
     python tools/denoise_time.py --temporal --sizes 512 4096        # prt_temporal_accumulate_device, and beside it the filter with and without the spatial fallback
@@ -21,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak
+HBM_COPY_GBS = 6290.0   # ... and what a float4 copy reaches of it
 
 
 def main():
@@ -29,7 +31,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "batching", "features"),
+    ap.add_argument("--mode", choices=("fixed", "variance", "given", "moments", "adaptive", "batching", "features"),
                     default="fixed")
     ap.add_argument("--frames", type=int, default=8, help="--mode moments: n_frames per call")
     ap.add_argument("--temporal", action="store_true",
@@ -62,6 +64,9 @@ def main():
         d_out = torch.empty((size, size, 3), dtype=torch.float32, device=dev)
         if a.mode == "moments":
             time_moments(a, size, c, d_f, stream)
+            continue
+        if a.mode == "adaptive":
+            time_adaptive(a, size, c, d_f, stream)
             continue
         variance = a.mode in ("variance", "given")
         d_iv = torch.from_numpy(D.denoise_variance(c, f, iterations=0, return_variance=True)[1]).to(dev) if a.mode == "given" else None
@@ -157,6 +162,48 @@ def time_moments(a, size, c, d_f, stream):
                           max_ms=round(ms[-1], 4), reps=a.reps, bytes_total=total,
                           implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
                           hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))), flush=True)
+
+
+def time_adaptive(a, size, c, d_f, stream, tile=64):
+    """prt_adaptive_update_device on one batch (the 8-spp mean times 8): the full tile list, and every other
+    tile of the frame (a checkerboard of the tile grid, in ascending order).  The yardstick is the traffic the
+    kernel must move per listed pixel, 12 B of batch, 28 B of sums and state read and 28 B written and 16 of the
+    32 B of features (84 B), over the HBM rates of MI355X_MICROARCH.md: the 8 TB/s peak and the 6.29 TB/s a
+    float4 copy measures."""
+    import torch
+    from pyrenderer_amd.adaptive import adaptive_update_device
+    dev = d_f.device
+    tx, ty = (size + tile - 1) // tile, (size + tile - 1) // tile
+    every = np.arange(tx * ty, dtype=np.int32)
+    lists = (("full", every), ("half", every[((every % tx) + (every // tx)) % 2 == 0]))
+    d_frame = torch.from_numpy(c).to(dev) * 8.0
+    d_sum = torch.zeros((size, size, 3), dtype=torch.float32, device=dev)
+    d_state = torch.zeros((size, size, 4), dtype=torch.float32, device=dev)
+    for name, ids in lists:
+        # the batch in slot order: tile-major, then row ly, then column lx (frames are [x][y])
+        pad = torch.zeros((tx * tile, ty * tile, 3), dtype=torch.float32, device=dev)
+        pad[:size, :size] = d_frame
+        slots = pad.reshape(tx, tile, ty, tile, 3).permute(2, 0, 3, 1, 4).reshape(tx * ty, tile * tile * 3)
+        d_b = slots[torch.from_numpy(ids.astype(np.int64)).to(dev)].contiguous()
+        d_rec = torch.zeros((len(ids), 4), dtype=torch.int32, device=dev)
+        del pad, slots
+        torch.cuda.synchronize(dev)
+
+        def run():
+            adaptive_update_device(d_b.data_ptr(), ids, tile, tile, size, size, d_f.data_ptr(), 8.0, d_sum.data_ptr(),
+                                   d_state.data_ptr(), d_rec.data_ptr(), target=0.05, stream_ptr=stream.cuda_stream)
+
+        ms = _median_ms(run, stream, a.warmup, a.reps)
+        med = ms[len(ms) // 2]
+        rec = d_rec.cpu().numpy()
+        n = int(rec[:, 0].sum())   # the listed pixels inside the frame
+        total = n * (12 + 28 + 28 + 16)
+        print(json.dumps(dict(what="adaptive_update_time", size=size, tile=tile, tiles=name, n_tiles=len(ids),
+                              listed_pixels=n, median_ms=round(med, 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4),
+                              reps=a.reps, bytes_total=total, implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
+                              hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              hbm_copy_fraction=round(total / (med * 1e-3) / 1e9 / HBM_COPY_GBS, 4))), flush=True)
+        del d_b, d_rec
 
 
 def time_temporal(a, scene, cam, world):

@@ -47,7 +47,8 @@ extern "C" {
  * header, then the three of its variance-guided mode (prt_denoise_var*), then the four of the
  * sample-moments variance (prt_moments_add*, prt_denoise_var_given*), then the four of the temporal
  * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*), then the two of adaptive sampling
- * (prt_adaptive_update*). */
+ * (prt_adaptive_update*), then the two of temporal accumulation across moving objects
+ * (prt_temporal_accumulate_motion*). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -524,7 +525,8 @@ int prt_denoise_var_given_device(int device, const float* d_color, const float* 
 /* Temporal accumulation.  Added under ABI 4, purely additive.  The previous frame's
  * integrated demodulated colour and luminance moments are reprojected through the first-hit features
  * into this frame's camera and blended with this frame: a source of colour and of variance for the
- * variance-guided filter while the camera moves.  Static geometry, pinhole cameras, one device.
+ * variance-guided filter while the camera moves.  Static geometry (prt_temporal_accumulate_motion below takes
+ * moving objects), pinhole cameras, one device.
  *
  * State: W x H x PRT_TEMPORAL_CHANNELS f32 [x][y], two float4 per pixel: I.rgb (integrated demodulated
  * colour), h (history length, in frames), m1, m2 (integrated first and second moment of the demodulated
@@ -582,6 +584,48 @@ int prt_temporal_accumulate_device(int device, const float* d_color, const float
                                    const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
                                    int W, int H, const float* params8, float* d_state, float* d_out_color,
                                    float* d_out_var, void* stream);
+/* Temporal accumulation across moving objects (DESIGN.md §11 "Moving objects").  Added under ABI 4, purely
+ * additive: prt_temporal_accumulate and its device form are unchanged.  Rigid per-object motion and SVGF's
+ * mesh-id test; pinhole cameras, one device.  prt_temporal_accumulate's arguments, plus:
+ *   ids        W x H i32 [x][y]: this frame's object id per pixel (any int32; e.g. -1 at a miss)
+ *   prev_ids   the previous frame's plane; NULL together with prev_feat, prev_cam24 and prev_state
+ *   motion     n_objects x 12 f32: per object a row-major 3 x 4 matrix M that takes a world position of THIS
+ *              frame to the same material point's world position in the PREVIOUS frame.  A device pointer in
+ *              the device form; the host form copies it.  NULL is allowed only when n_objects == 0
+ *   n_objects  0..1048576
+ * The contract is prt_temporal_accumulate's steps 1-8 with these changes, every operation one IEEE f32
+ * operation in this association (tests/temporal_motion_ref.py restates it in NumPy):
+ *  Id and row.  An id is valid when 0 <= id < n_objects.  Any other id (-1, too large, INT_MIN) has no row: its
+ *     pixel reprojects as the static path does and no table entry is read for it.  A valid id whose row holds
+ *     an entry that is not finite means "no previous pose": the pixel takes step 2, decided before anything is
+ *     projected.
+ *  3'. X_i = E_i + Z * d_i as in step 3.  For a valid id Xp_i = ((M[i][0] X_0 + M[i][1] X_1) + M[i][2] X_2) + M[i][3]
+ *     and Np_i = (M[i][0] N_0 + M[i][1] N_1) + M[i][2] N_2; otherwise Xp = X and Np = N.  rel_i = Xp_i - Eprev_i;
+ *     the rest of steps 3 and 4 is unchanged.
+ *  5'. A tap additionally needs prev_ids[q] == ids[p], a plain int32 comparison that also applies to invalid
+ *     ids.  The normal test uses Np, the depth test the r obtained from Xp.
+ *  8'. The one-tap shortcut (q = p, w = 1, r = Z) is decided per pixel: it applies when the two camera records
+ *     are bytewise equal AND the id is invalid or its row is bytewise (1,0,0,0, 0,1,0,0, 0,0,1,0).  A row that
+ *     is the identity but for a -0 goes the long way.  A static camera watching one moving object still gives
+ *     exact running means everywhere else.
+ * Finiteness: prt_temporal_accumulate's statement holds.  A finite row times a finite position may overflow;
+ * the resulting inf or NaN fails step 4 (a comparison with a NaN is false) before any index is formed, and the
+ * pixel takes step 2.
+ * Bad arguments (those of prt_temporal_accumulate; ids NULL; prev_ids not NULL together with the rest of prev_*;
+ * n_objects < 0 or > 1048576; motion NULL with n_objects > 0) return PRT_ERR_ARG before any device is touched,
+ * with the text in prt_denoise_last_error. */
+int prt_temporal_accumulate_motion(int device, const float* color, const float* feat, const float* cam24,
+                                   const float* prev_feat, const float* prev_cam24, const float* prev_state,
+                                   const int32_t* ids, const int32_t* prev_ids, const float* motion, int n_objects,
+                                   int W, int H, const float* params8, float* state, float* out_color, float* out_var);
+/* ... on device pointers (cam24 and prev_cam24 stay host pointers), enqueued on `stream` with no host
+ * synchronisation.  prt_temporal_accumulate_device's alignment and aliasing rules hold, with d_ids, d_prev_ids
+ * and d_motion among the inputs. */
+int prt_temporal_accumulate_motion_device(int device, const float* d_color, const float* d_feat, const float* cam24,
+                                          const float* d_prev_feat, const float* prev_cam24,
+                                          const float* d_prev_state, const int32_t* d_ids, const int32_t* d_prev_ids,
+                                          const float* d_motion, int n_objects, int W, int H, const float* params8,
+                                          float* d_state, float* d_out_color, float* d_out_var, void* stream);
 /* prt_denoise_var_given with a spatial fallback: the 7 x 7 estimate of prt_denoise_var runs first, then
  * in_var replaces it at every pixel that is not set aside where it is finite and >= 0 (-0 included);
  * anywhere else — NaN (the temporal marker), inf, a negative value — the estimate stays.  out_var (may be

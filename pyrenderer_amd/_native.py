@@ -136,6 +136,10 @@ EXPORTS = {
     "prt_denoise_var_mixed_device": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _i64, _vp]),
     "prt_temporal_accumulate": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "prt_temporal_accumulate_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "prt_temporal_accumulate_motion": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp,
+                                            _vp]),
+    "prt_temporal_accumulate_motion_device": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp,
+                                                   _vp, _vp, _vp]),
     "prt_adaptive_update": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp,
                                  _vp]),
     "prt_adaptive_update_device": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, ctypes.c_float, ctypes.c_float, _vp,

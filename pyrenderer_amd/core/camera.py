@@ -41,6 +41,18 @@ class PackedCamera:
         self.sensor_dim = np.array([sensor_width, sensor_height, focus_dist, aperture], np.float32)
         self.origin = cols[:, 3].astype(np.float32)
 
+    @classmethod
+    def from_record(cls, record):
+        """The camera of a packed 24-float record (packed()'s inverse)."""
+        rec = np.ascontiguousarray(record, np.float32)
+        if rec.shape != (24,):
+            raise ValueError(f"a packed camera record holds 24 floats, not {rec.shape}")
+        cam = cls.__new__(cls)
+        cam.iview_cols = rec[:16].reshape(4, 4).copy()
+        cam.sensor_dim = rec[16:20].copy()
+        cam.origin = cam.iview_cols[:, 3].copy()
+        return cam
+
     def packed(self):
         out = np.zeros(24, np.float32)
         out[:16] = self.iview_cols.reshape(-1)

@@ -402,7 +402,10 @@ class TemporalAccumulator:
     `temporal_params` are temporal_accumulate's keyword parameters (alpha, alpha_m, tau_n, tau_z, tau_a,
     eps_a, min_history, w_min).  resolution: (W, H); None takes the first camera's, and every later camera
     must then have the same.  A camera with an aperture is a ValueError: a thin lens has no unique
-    reprojection.  Static geometry, one device, no save / load."""
+    reprojection.  One device, no save / load.  Geometry is static unless add() is given the frame's scene:
+    the history then follows rigidly moving primitives (DESIGN.md §11 "Moving objects").  Moving lights, and
+    the shading changes a moving object casts on static surfaces (its shadow, its reflection), keep their
+    history and lag behind by about 1 / alpha frames: SVGF's known limit."""
 
     def __init__(self, scene, *, depth, spp, seed=0, resolution=None, device=0, tile=64, world=None, nee="reference",
                  **temporal_params):
@@ -420,10 +423,19 @@ class TemporalAccumulator:
         self.params = dict(temporal_params)
         self.frames = 0      # frames rendered: the next one starts at sample frames * spp
         self.frame = None    # the last frame's _Frame
-        self._mean = self._color = self._state = self._prev = None
+        self._mean = self._color = self._state = self._prev = self._ids = None
+        self._moving = False             # a scene has been passed to add(): the history follows moving objects
+        self._own_world = world is None  # a world built here is released when a frame's scene replaces it
 
-    def add(self, camera):
-        """Render the next frame with `camera` and fold it into the history."""
+    def add(self, camera, scene=None):
+        """Render the next frame with `camera` and fold it into the history.
+
+        scene: None (default) renders the accumulator's scene; a sequence that never passes one is the static
+        world of prt_temporal_accumulate.  With a scene, this frame is rendered in a world built from it, and
+        from then on the history follows moving objects (prt_temporal_accumulate_motion): the motion table
+        comes from the previous frame's scene (pyrenderer_amd.denoise.motion_rows: the same primitives in the
+        same order, e.g. pyrenderer_amd.scenes.moved), the object-id planes of both frames are kept, and the
+        previous frame's device scene is released.  Passing the scene the last frame used builds nothing."""
         from .. import denoise as D
         if camera.aperture > 0:
             raise ValueError("TemporalAccumulator needs a pinhole camera: a thin lens (aperture > 0) has no unique "
@@ -433,17 +445,50 @@ class TemporalAccumulator:
             self.resolution = res
         elif self._from_camera and res != self.resolution:
             raise ValueError(f"the resolution cannot change within a sequence: {res} after {self.resolution}")
+        motion = None
+        if scene is not None or self._moving:
+            scene = self.scene if scene is None else scene
+            # raises before anything is built or rendered
+            motion = D.motion_rows(scene if self.scene is None else self.scene, scene)
+        stale = None
+        if scene is not None and scene is not self.scene:
+            stale, self.world, self._own_world = (self.world if self._own_world else None), None, True
+            self.scene = scene
         if self.world is None:
             self.world = build_world(self.scene, (self.device,))
+            self._own_world = True
         f = _Frame.of(self.scene, camera, depth=self.depth, seed=self.seed, resolution=self.resolution,
                       devices=(self.device,), tile=self.tile, world=self.world, nee=self.nee)
         mean = _mean(f.unpack(f.add_samples(self.frames * self.spp, self.spp)), self.spp)
         feat = f.features()
-        state, color = D.temporal_accumulate(mean, feat, f.cam, self._prev, device=self.device, **self.params)
+        if motion is None:
+            state, color = D.temporal_accumulate(mean, feat, f.cam, self._prev, device=self.device, **self.params)
+            self._ids = None
+            self._prev = (state, feat, f.cam)
+        else:
+            ids = D.object_ids(f.ds, f.cam, f.W, f.H)
+            prev = self._prev
+            if prev is not None and len(prev) == 3:   # the frames so far were static: their id plane is due now
+                prev = (*prev, self.object_ids())
+            state, color = D.temporal_accumulate(mean, feat, f.cam, prev, device=self.device, ids=ids, motion=motion,
+                                                 **self.params)
+            self._moving, self._ids = True, ids
+            self._prev = (state, feat, f.cam, ids)
         self.frame, self._mean, self._color, self._state = f, mean, color, state
-        self._prev = (state, feat, f.cam)
+        if stale is not None:   # the previous frame's world: nothing reads it any more
+            for ds in stale.device_scenes.values():
+                ds.close()
         self.frames += 1
         return self
+
+    def object_ids(self):
+        """The last frame's object-id plane, (W, H) int32 (pyrenderer_amd.denoise.object_ids): the plane the
+        accumulation used, or for a static sequence one composed on demand."""
+        self._need_frame()
+        if self._ids is None:
+            from .. import denoise as D
+            self._ids = D.object_ids(self.frame.ds, self.frame.cam, self.frame.W, self.frame.H)
+        return self._ids
 
     def _need_frame(self):
         if self.frame is None:
@@ -489,20 +534,29 @@ class TemporalAccumulator:
 
 
 def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, device=0, tile=64, world=None,
-                    nee="reference", denoise="variance", **temporal_params):
+                    nee="reference", denoise="variance", scenes=None, **temporal_params):
     """The frames of a camera path with temporal accumulation, (n, W, H, 3) float32: frame t is
     TemporalAccumulator.add(cameras[t]) followed by denoised() (denoise="variance", the default) or
-    accumulated() (denoise=False).  Anything else is a ValueError."""
+    accumulated() (denoise=False).  Anything else is a ValueError.  scenes: None (default) is the static
+    `scene`; one scene per camera makes frame t add(cameras[t], scenes[t]), the history following the
+    primitives that move between them."""
     if not ((isinstance(denoise, str) and denoise == "variance") or denoise is False):
         raise ValueError(f"denoise must be 'variance' or False, not {denoise!r}")
     cameras = list(cameras)
     if not cameras:
         raise ValueError("render_sequence needs at least one camera")
+    if scenes is not None:
+        scenes = list(scenes)
+        if len(scenes) != len(cameras):
+            raise ValueError(f"scenes must hold one scene per camera: {len(scenes)} for {len(cameras)} cameras")
     acc = TemporalAccumulator(scene, depth=depth, spp=spp, seed=seed, resolution=resolution, device=device, tile=tile,
                               world=world, nee=nee, **temporal_params)
     out = []
-    for cam in cameras:
-        acc.add(cam)
+    for t, cam in enumerate(cameras):
+        if scenes is None:
+            acc.add(cam)
+        else:
+            acc.add(cam, scenes[t])
         out.append(acc.denoised() if denoise else acc.accumulated())
     return np.stack(out).astype(np.float32)
 

@@ -73,6 +73,26 @@ hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const flo
                             const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
                             hipStream_t stream);
 
+// enqueue_temporal with per-object motion (temporal_kernel<true>; tests/temporal_motion_ref.py restates it).
+// d_ids / d_prev_ids: W x H int32 [x][y], this frame's and the previous frame's object id per pixel (d_prev_ids
+// null on the first frame, with the other prev pointers).  d_motion: n_objects x 12 floats, per object the
+// row-major 3 x 4 matrix that takes a world position of this frame to the same material point's position in
+// the previous frame; null only when n_objects is 0.  An id outside 0..n_objects-1 has no row: its pixel
+// reprojects as enqueue_temporal's does and no table entry is read for it.  A row with an entry that is not
+// finite means "no previous pose": the pixel starts afresh.  A tap counts only if its previous id equals the
+// pixel's id.  cameras_equal: the two records are bytewise equal; a pixel then takes its own previous state
+// alone if its id has no row or the row is bytewise the identity.
+//
+// Finiteness: enqueue_temporal's statement holds; a finite row times a finite position may overflow to inf or
+// NaN, which fails the range test of the projection (a comparison with a NaN is false) before any index is
+// formed, so the pixel starts afresh.
+constexpr int kMaxObjects = 1 << 20;
+hipError_t enqueue_temporal_motion(const float* d_color, const float* d_feat, const float* cam24,
+                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
+                                   const int32_t* d_ids, const int32_t* d_prev_ids, const float* d_motion, int n_objects,
+                                   int W, int H, bool cameras_equal, const TemporalParams& p, float* d_state,
+                                   float* d_out_color, float* d_out_var, hipStream_t stream);
+
 // ---- variance from per-pixel sample moments ----
 
 // Running Welford update of the demodulated luminance over n_frames frames of per-pixel radiance sums

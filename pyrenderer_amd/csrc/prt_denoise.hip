@@ -11,7 +11,7 @@
 // end (moments_kernel, var_given_kernel) read and write each pixel once and take no taps;
 // adaptive_kernel, which shares moments_kernel's update, is the one kernel with a mapping of its own
 // (tile chunks, its batch transposed through LDS); temporal_kernel, the last one, gathers four taps per
-// pixel from the previous frame's planes.
+// pixel from the previous frame's planes, with or without per-object motion.
 #include "prt_denoise.h"
 
 namespace prt_dn {
@@ -512,7 +512,8 @@ __global__ __launch_bounds__(kChunk) void adaptive_kernel(const float* __restric
     }
 }
 
-// ---- temporal accumulation (DESIGN.md §11 "Temporal accumulation"; tests/temporal_ref.py restates it) ----
+// ---- temporal accumulation (DESIGN.md §11 "Temporal accumulation" and "Moving objects"; tests/temporal_ref.py
+// restates the static instantiation, tests/temporal_motion_ref.py the one with per-object motion) ----
 // The previous frame's integrated demodulated colour and luminance moments, reprojected through the first-hit
 // features into this frame's camera (the temporal half of SVGF, Schied et al. 2017).  The state is two float4
 // per pixel: (I.rgb, h) and (m1, m2, var, 0).  The four bilinear taps of a pixel come straight from global
@@ -530,10 +531,23 @@ struct Cameras {
     float psw, psh, pfd;
 };
 
+// per-object motion (kMotion): the two id planes, the table of 3 x 4 rows and its length; all null / 0 without
+struct Motion {
+    const int32_t* ids;
+    const int32_t* prev_ids;
+    const float* rows;
+    int n_objects;
+};
+
+// kMotion false is the static world: `mo` is not read and every pixel goes the way `cams_equal` says.  kMotion
+// true carries the first hit of a pixel whose object id has a row into the previous frame's world before it is
+// projected, turns its normal along, and asks every tap for the same id (SVGF's mesh-id test); the one-tap
+// shortcut of equal cameras is then decided per pixel.
+template <bool kMotion>
 __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
     const float* __restrict__ color, const float* __restrict__ feat, const float* __restrict__ prev_feat,
-    const float4* __restrict__ prev_state, const Cameras cams, int W, int H, int is_static, const TemporalParams P,
-    float4* __restrict__ state, float* __restrict__ out_color, float* __restrict__ out_var) {
+    const float4* __restrict__ prev_state, const Cameras cams, int W, int H, int cams_equal, const TemporalParams P,
+    const Motion mo, float4* __restrict__ state, float* __restrict__ out_color, float* __restrict__ out_var) {
     int x, y;
     if (!pixel_of_lane(W, H, x, y)) return;
     const size_t p = (size_t)x * (size_t)H + (size_t)y;
@@ -558,8 +572,30 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
     // 2. without history: the state a miss, the first frame and every rejected reprojection end in
     float n0 = i0, n1 = i1, n2 = i2, nh = 1.0f, nm1 = l, nm2 = l * l, nv = marker;
 
-    if (hit && prev_state) {
+    // the object's row: none for an id outside the table (the static path), "no previous pose" when an entry is
+    // not finite, and the one-tap shortcut only while it is bytewise the identity
+    bool is_static = cams_equal != 0, has_row = false, no_pose = false;
+    int id = 0;
+    float M[12];
+    if constexpr (kMotion) {
+        id = mo.ids[p];
+        if (hit && prev_state && id >= 0 && id < mo.n_objects) {
+            const float* row = mo.rows + (size_t)id * 12;
+            bool identity = true;
+#pragma unroll
+            for (int j = 0; j < 12; ++j) {
+                M[j] = row[j];
+                no_pose = no_pose || !finite_f(M[j]);
+                identity = identity && __float_as_uint(M[j]) == (j % 5 == 0 ? 0x3f800000u : 0u);
+            }
+            has_row = true;
+            is_static = is_static && identity;
+        }
+    }
+
+    if (hit && prev_state && !no_pose) {
         // 3. project the first hit into the previous camera
+        float Np[3] = {F[3], F[4], F[5]};
         float r = F[6], px = (float)x, py = (float)y;
         bool in_range = true;
         if (!is_static) {
@@ -573,9 +609,25 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
                 f[i] = (((rx * c[0] + ry * c[1]) + rz * c[2]) + c[3]) - E[i];
             }
             const float ln = sqrtf((f[0] * f[0] + f[1] * f[1]) + f[2] * f[2]);
-            float rel[3];
+            float X[3], rel[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) rel[i] = (E[i] + F[6] * (f[i] / ln)) - cams.prev[4 * i + 3];
+            for (int i = 0; i < 3; ++i) X[i] = E[i] + F[6] * (f[i] / ln);
+            if constexpr (kMotion) {
+                if (has_row) {
+                    // this frame's world position and normal in the previous frame's world
+                    float Xp[3];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        const float* m = M + 4 * i;
+                        Xp[i] = ((m[0] * X[0] + m[1] * X[1]) + m[2] * X[2]) + m[3];
+                        Np[i] = (m[0] * F[3] + m[1] * F[4]) + m[2] * F[5];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) X[i] = Xp[i];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) rel[i] = X[i] - cams.prev[4 * i + 3];
             r = sqrtf((rel[0] * rel[0] + rel[1] * rel[1]) + rel[2] * rel[2]);
             const float a = (rel[0] * cams.prev[0] + rel[1] * cams.prev[4]) + rel[2] * cams.prev[8];
             const float b = (rel[0] * cams.prev[1] + rel[1] * cams.prev[5]) + rel[2] * cams.prev[9];
@@ -612,11 +664,14 @@ __global__ __launch_bounds__(kBlockX* kBlockY) void temporal_kernel(
                     const int qy = ty[jy];
                     if (qy < 0 || qy >= H || (is_static && (jx | jy))) continue;
                     const size_t q = (size_t)qx * (size_t)H + (size_t)qy;
+                    if constexpr (kMotion) {
+                        if (mo.prev_ids[q] != id) continue;   // another object stood there
+                    }
                     const float4 h0 = prev_state[q * 2];
                     if (!(h0.w > 0.0f)) continue;
                     const float* G = prev_feat + q * 8;
                     if (!(G[7] > 0.0f)) continue;
-                    const float nd = (F[3] * G[3] + F[4] * G[4]) + F[5] * G[5];
+                    const float nd = (Np[0] * G[3] + Np[1] * G[4]) + Np[2] * G[5];
                     if (!(nd >= P.tau_n)) continue;
                     if (!(fabsf(G[6] - r) <= P.tau_z * r)) continue;
                     const float da = fmaxf(fmaxf(fabsf(G[0] - F[0]), fabsf(G[1] - F[1])), fabsf(G[2] - F[2]));
@@ -763,10 +818,9 @@ hipError_t enqueue_adaptive(const float* d_batch, const int32_t* tile_ids, int n
     return e;
 }
 
-hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
-                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
-                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
-                            hipStream_t stream) {
+namespace {
+
+Cameras camera_parts(const float* cam24, const float* prev_cam24) {
     Cameras cams = {};
     for (int i = 0; i < 12; ++i) cams.cur[i] = cam24[i];
     cams.sw = cam24[16];
@@ -778,8 +832,29 @@ hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const flo
         cams.psh = prev_cam24[17];
         cams.pfd = prev_cam24[18];
     }
-    return launch(temporal_kernel, W, H, stream, d_color, d_feat, d_prev_feat,
-                  reinterpret_cast<const float4*>(d_prev_state), cams, W, H, is_static ? 1 : 0, p,
+    return cams;
+}
+
+}  // namespace
+
+hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
+                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
+                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
+                            hipStream_t stream) {
+    return launch(temporal_kernel<false>, W, H, stream, d_color, d_feat, d_prev_feat,
+                  reinterpret_cast<const float4*>(d_prev_state), camera_parts(cam24, prev_cam24), W, H,
+                  is_static ? 1 : 0, p, Motion{nullptr, nullptr, nullptr, 0}, reinterpret_cast<float4*>(d_state),
+                  d_out_color, d_out_var);
+}
+
+hipError_t enqueue_temporal_motion(const float* d_color, const float* d_feat, const float* cam24,
+                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
+                                   const int32_t* d_ids, const int32_t* d_prev_ids, const float* d_motion, int n_objects,
+                                   int W, int H, bool cameras_equal, const TemporalParams& p, float* d_state,
+                                   float* d_out_color, float* d_out_var, hipStream_t stream) {
+    return launch(temporal_kernel<true>, W, H, stream, d_color, d_feat, d_prev_feat,
+                  reinterpret_cast<const float4*>(d_prev_state), camera_parts(cam24, prev_cam24), W, H,
+                  cameras_equal ? 1 : 0, p, Motion{d_ids, d_prev_ids, d_motion, n_objects},
                   reinterpret_cast<float4*>(d_state), d_out_color, d_out_var);
 }
 

@@ -336,6 +336,113 @@ int check_temporal_cameras(const std::string& who, const float* cam24, const voi
     return PRT_OK;
 }
 
+// the motion arguments of prt_temporal_accumulate_motion and its device form; the plain entry points pass none
+struct MotionArgs {
+    const int32_t* ids;
+    const int32_t* prev_ids;
+    const float* motion;
+    int n_objects;
+};
+
+// NULL pointers, parameters, cameras and, with motion, the id planes and the table: everything the two forms of
+// a temporal entry point check alike
+int check_temporal_args(const std::string& who, const MotionArgs* m, int device, const float* color, const float* feat,
+                        const float* cam24, const float* prev_feat, const float* prev_cam24, const float* prev_state,
+                        int W, int H, const float* params8, const float* state, prt_dn::TemporalParams* p,
+                        bool* is_static) {
+    if (!color || !feat || !cam24 || !state || (m && !m->ids)) return fail(PRT_ERR_ARG, who + ": NULL pointer");
+    DN_TRY(check_temporal_params(who, device, W, H, params8, p));
+    DN_TRY(check_temporal_cameras(who, cam24, prev_feat, prev_cam24, prev_state, is_static));
+    if (!m) return PRT_OK;
+    if ((m->prev_ids != nullptr) != (prev_state != nullptr))
+        return fail(PRT_ERR_ARG, who + ": prev_ids must be NULL together with prev_feat, prev_cam24 and prev_state or not at all");
+    if (m->n_objects < 0 || m->n_objects > prt_dn::kMaxObjects)
+        return fail(PRT_ERR_ARG, who + ": n_objects must be in 0.." + std::to_string(prt_dn::kMaxObjects));
+    if (m->n_objects > 0 && !m->motion) return fail(PRT_ERR_ARG, who + ": motion is NULL with n_objects > 0");
+    return PRT_OK;
+}
+
+hipError_t enqueue_temporal_any(const MotionArgs* m, const float* d_color, const float* d_feat, const float* cam24,
+                                const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state, int W, int H,
+                                bool is_static, const prt_dn::TemporalParams& p, float* d_state, float* d_out_color,
+                                float* d_out_var, hipStream_t stream) {
+    if (!m)
+        return prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
+                                        d_state, d_out_color, d_out_var, stream);
+    return prt_dn::enqueue_temporal_motion(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, m->ids,
+                                           m->prev_ids, m->n_objects > 0 ? m->motion : nullptr, m->n_objects, W, H,
+                                           is_static, p, d_state, d_out_color, d_out_var, stream);
+}
+
+// the device form of both temporal entry points; `m` holds device pointers
+int temporal_device(const std::string& who, const MotionArgs* m, int device, const float* d_color, const float* d_feat,
+                    const float* cam24, const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
+                    int W, int H, const float* params8, float* d_state, float* d_out_color, float* d_out_var,
+                    void* stream) {
+    prt_dn::TemporalParams p;
+    bool is_static = false;
+    DN_TRY(check_temporal_args(who, m, device, d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H,
+                               params8, d_state, &p, &is_static));
+    if (reinterpret_cast<uintptr_t>(d_state) % 16 != 0 || reinterpret_cast<uintptr_t>(d_prev_state) % 16 != 0)
+        return fail(PRT_ERR_ARG, who + ": d_state and d_prev_state must be 16-byte aligned");
+    if (m && (reinterpret_cast<uintptr_t>(m->ids) % 4 != 0 || reinterpret_cast<uintptr_t>(m->prev_ids) % 4 != 0 ||
+              reinterpret_cast<uintptr_t>(m->motion) % 4 != 0))
+        return fail(PRT_ERR_ARG, who + ": d_ids, d_prev_ids and d_motion must be 4-byte aligned");
+    // every output against every input and against the other outputs
+    const void* ins[] = {d_color, d_feat, d_prev_feat, d_prev_state, m ? m->ids : nullptr, m ? m->prev_ids : nullptr,
+                         m ? m->motion : nullptr};
+    const void* outs[] = {d_state, d_out_color, d_out_var};
+    for (int i = 0; i < 3; ++i) {
+        if (!outs[i]) continue;
+        for (const void* in : ins)
+            if (outs[i] == in)
+                return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias an input (d_state "
+                                               "not d_prev_state: taps read neighbours)");
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias each other");
+    }
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
+    DN_HIP_TRY(enqueue_temporal_any(m, d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
+                                    d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
+    return PRT_OK;
+}
+
+// the host form of both; `m` holds host pointers, its planes and table are staged like the rest
+int temporal_host(const std::string& who, const MotionArgs* m, int device, const float* color, const float* feat,
+                  const float* cam24, const float* prev_feat, const float* prev_cam24, const float* prev_state, int W,
+                  int H, const float* params8, float* state, float* out_color, float* out_var) {
+    prt_dn::TemporalParams p;
+    bool is_static = false;
+    DN_TRY(check_temporal_args(who, m, device, color, feat, cam24, prev_feat, prev_cam24, prev_state, W, H, params8, state,
+                               &p, &is_static));
+    if (state == prev_state) return fail(PRT_ERR_ARG, who + ": state must not alias prev_state");
+    DeviceGuard g;
+    DN_TRY(g.enter(who, device));
+    const size_t n = (size_t)W * (size_t)H;
+    Staging s;
+    const float* d_color = s.in(color, n * 3);
+    const float* d_feat = s.in(feat, n * 8);
+    const float* d_prev_feat = prev_feat ? s.in(prev_feat, n * 8) : nullptr;
+    const float* d_prev_state = prev_state ? s.in(prev_state, n * prt_dn::kTemporalChannels) : nullptr;
+    MotionArgs d_m = {nullptr, nullptr, nullptr, 0};
+    if (m) {
+        d_m.ids = static_cast<const int32_t*>(s.bytes(n * sizeof(int32_t), m->ids));
+        if (m->prev_ids) d_m.prev_ids = static_cast<const int32_t*>(s.bytes(n * sizeof(int32_t), m->prev_ids));
+        if (m->n_objects > 0) d_m.motion = s.in(m->motion, (size_t)m->n_objects * 12);
+        d_m.n_objects = m->n_objects;
+    }
+    float* d_state = s.out(state, n * prt_dn::kTemporalChannels);
+    float* d_out_color = s.out(out_color, n * 3);
+    float* d_out_var = s.out(out_var, n);
+    if (s.oom()) return fail_oom(who);
+    DN_HIP_TRY(s.upload());
+    DN_HIP_TRY(enqueue_temporal_any(m ? &d_m : nullptr, d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H,
+                                    is_static, p, d_state, d_out_color, d_out_var, nullptr));
+    DN_HIP_TRY(s.download());
+    return PRT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -441,60 +548,34 @@ int prt_temporal_accumulate_device(int device, const float* d_color, const float
                                    const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
                                    int W, int H, const float* params8, float* d_state, float* d_out_color,
                                    float* d_out_var, void* stream) {
-    const std::string who("prt_temporal_accumulate_device");
-    prt_dn::TemporalParams p;
-    bool is_static = false;
-    if (!d_color || !d_feat || !cam24 || !d_state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_temporal_params(who, device, W, H, params8, &p));
-    DN_TRY(check_temporal_cameras(who, cam24, d_prev_feat, prev_cam24, d_prev_state, &is_static));
-    if (reinterpret_cast<uintptr_t>(d_state) % 16 != 0 || reinterpret_cast<uintptr_t>(d_prev_state) % 16 != 0)
-        return fail(PRT_ERR_ARG, who + ": d_state and d_prev_state must be 16-byte aligned");
-    // every output against every input and against the other outputs
-    const void* ins[] = {d_color, d_feat, d_prev_feat, d_prev_state};
-    const void* outs[] = {d_state, d_out_color, d_out_var};
-    for (int i = 0; i < 3; ++i) {
-        if (!outs[i]) continue;
-        for (const void* in : ins)
-            if (outs[i] == in)
-                return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias an input (d_state "
-                                               "not d_prev_state: taps read neighbours)");
-        for (int j = 0; j < i; ++j)
-            if (outs[i] == outs[j]) return fail(PRT_ERR_ARG, who + ": d_state, d_out_color and d_out_var must not alias each other");
-    }
-    DeviceGuard g;
-    DN_TRY(g.enter(who, device));
-    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static,
-                                        p, d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
-    return PRT_OK;
+    return temporal_device("prt_temporal_accumulate_device", nullptr, device, d_color, d_feat, cam24, d_prev_feat,
+                           prev_cam24, d_prev_state, W, H, params8, d_state, d_out_color, d_out_var, stream);
 }
 
 int prt_temporal_accumulate(int device, const float* color, const float* feat, const float* cam24,
                             const float* prev_feat, const float* prev_cam24, const float* prev_state, int W, int H,
                             const float* params8, float* state, float* out_color, float* out_var) {
-    const std::string who("prt_temporal_accumulate");
-    prt_dn::TemporalParams p;
-    bool is_static = false;
-    if (!color || !feat || !cam24 || !state) return fail(PRT_ERR_ARG, who + ": NULL pointer");
-    DN_TRY(check_temporal_params(who, device, W, H, params8, &p));
-    DN_TRY(check_temporal_cameras(who, cam24, prev_feat, prev_cam24, prev_state, &is_static));
-    if (state == prev_state) return fail(PRT_ERR_ARG, who + ": state must not alias prev_state");
-    DeviceGuard g;
-    DN_TRY(g.enter(who, device));
-    const size_t n = (size_t)W * (size_t)H;
-    Staging s;
-    const float* d_color = s.in(color, n * 3);
-    const float* d_feat = s.in(feat, n * 8);
-    const float* d_prev_feat = prev_feat ? s.in(prev_feat, n * 8) : nullptr;
-    const float* d_prev_state = prev_state ? s.in(prev_state, n * prt_dn::kTemporalChannels) : nullptr;
-    float* d_state = s.out(state, n * prt_dn::kTemporalChannels);
-    float* d_out_color = s.out(out_color, n * 3);
-    float* d_out_var = s.out(out_var, n);
-    if (s.oom()) return fail_oom(who);
-    DN_HIP_TRY(s.upload());
-    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
-                                        d_state, d_out_color, d_out_var, nullptr));
-    DN_HIP_TRY(s.download());
-    return PRT_OK;
+    return temporal_host("prt_temporal_accumulate", nullptr, device, color, feat, cam24, prev_feat, prev_cam24,
+                         prev_state, W, H, params8, state, out_color, out_var);
+}
+
+int prt_temporal_accumulate_motion_device(int device, const float* d_color, const float* d_feat, const float* cam24,
+                                          const float* d_prev_feat, const float* prev_cam24,
+                                          const float* d_prev_state, const int32_t* d_ids, const int32_t* d_prev_ids,
+                                          const float* d_motion, int n_objects, int W, int H, const float* params8,
+                                          float* d_state, float* d_out_color, float* d_out_var, void* stream) {
+    const MotionArgs m = {d_ids, d_prev_ids, d_motion, n_objects};
+    return temporal_device("prt_temporal_accumulate_motion_device", &m, device, d_color, d_feat, cam24, d_prev_feat,
+                           prev_cam24, d_prev_state, W, H, params8, d_state, d_out_color, d_out_var, stream);
+}
+
+int prt_temporal_accumulate_motion(int device, const float* color, const float* feat, const float* cam24,
+                                   const float* prev_feat, const float* prev_cam24, const float* prev_state,
+                                   const int32_t* ids, const int32_t* prev_ids, const float* motion, int n_objects,
+                                   int W, int H, const float* params8, float* state, float* out_color, float* out_var) {
+    const MotionArgs m = {ids, prev_ids, motion, n_objects};
+    return temporal_host("prt_temporal_accumulate_motion", &m, device, color, feat, cam24, prev_feat, prev_cam24,
+                         prev_state, W, H, params8, state, out_color, out_var);
 }
 
 // ---- adaptive sampling ----

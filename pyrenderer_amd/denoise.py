@@ -3,7 +3,8 @@
 `features()` computes per-pixel albedo / shading normal / depth / hit fraction of the render's own
 primary rays in one HIP kernel (prt_features; `features_device()` leaves them on the device);
 `denoise()` runs the HIP filter of pyrenderer_amd/csrc/prt_denoise.hip (prt_denoise); `temporal_accumulate()`
-carries a frame's integrated colour and luminance moments into the next camera (prt_temporal_accumulate).
+carries a frame's integrated colour and luminance moments into the next camera (prt_temporal_accumulate), and
+with `object_ids()` and `motion_rows()` across rigidly moving objects (prt_temporal_accumulate_motion).
 There is no CPU fallback.
 """
 import ctypes
@@ -347,9 +348,109 @@ def temporal_state(W, H):
     return np.zeros((int(W), int(H), TEMPORAL_CHANNELS), np.float32)
 
 
+IDENTITY_ROW = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0], np.float32)
+MAX_OBJECTS = 1 << 20        # prt_temporal_accumulate_motion's limit on the motion table
+RIGID_TOL = 1e-9             # float64 bound on |R^T R - 1| (per entry) and |det R - 1| of a rigid motion
+
+
+def object_ids(ds, cam_packed, W, H):
+    """The object-id plane of a frame, (W, H) int32 [x][y]: the index in scene.primitives of the closest hit of
+    the pixel-centre ray PackedCamera.gen_ray((x + 0.5) / (W - 1), (y + 0.5) / (H - 1)), the one temporal_kernel
+    restates, in T_MIN..T_MAX; -1 at a miss.  Composed through the host from ds.closest_hits, flat.tri_prim and
+    flat.sph_prim (one ray record up and one hit id down per pixel; DESIGN.md §11 has the cost).  With W == 1
+    or H == 1 no pixel-centre ray exists: all -1, and nothing is traced."""
+    from .core.camera import PackedCamera
+    W, H = int(W), int(H)
+    ids = np.full((W, H), -1, np.int32)
+    if W == 1 or H == 1:
+        return ids
+    f = np.float32
+    u = (np.arange(W, dtype=f) + f(0.5)) / f(W - 1)
+    v = (np.arange(H, dtype=f) + f(0.5)) / f(H - 1)
+    o, d = PackedCamera.from_record(cam_packed).gen_ray(u[:, None], v[None, :])
+    flat = ds.flat
+    for x0 in range(0, W, max(1, CHUNK_RAYS // H)):
+        x1 = min(W, x0 + max(1, CHUNK_RAYS // H))
+        hid, _ = ds.closest_hits(o[x0:x1].reshape(-1, 3), d[x0:x1].reshape(-1, 3), T_MIN, T_MAX)
+        hid = hid.astype(np.int64)
+        tri, sph = (hid >= 0) & (hid < flat.n_tri), hid >= flat.n_tri
+        out = np.full(hid.shape, -1, np.int32)
+        out[tri] = flat.tri_prim[hid[tri]]
+        out[sph] = flat.sph_prim[hid[sph] - flat.n_tri]
+        ids[x0:x1] = out.reshape(x1 - x0, H)
+    return ids
+
+
+def _same_primitive(a, b):
+    if type(a) is not type(b) or getattr(a, "type_name", "") != getattr(b, "type_name", ""):
+        return False
+    if hasattr(a, "faces") != hasattr(b, "faces") or (hasattr(a, "faces") and len(a.faces) != len(b.faces)):
+        return False
+    return a.bsdf is b.bsdf or np.array_equal(a.bsdf.pack(), b.bsdf.pack())
+
+
+def motion_rows(prev_scene, scene):
+    """The motion table of a frame, (n_primitives, 12) float32: per primitive of `scene` the row-major 3 x 4
+    matrix that takes a world position of this frame to the same material point's position in `prev_scene`.
+    The two scenes must list the same primitives in the same order (type, face count, BSDF); anything else is a
+    ValueError.  Mesh primitives: T_prev @ inv(T_cur) in float64 from trans_mat; spheres: the translation of the
+    centre.  A primitive whose transform did not change gets the exact identity row, not a computed one.  A
+    pair that is not rigid (the 3 x 3 part not orthonormal with determinant +1 within RIGID_TOL in float64, a
+    singular transform, a sphere whose radius changed) or that has no transform to compare (a MeshBatch whose
+    vertices changed) gets a NaN row: "no previous pose", its pixels start afresh."""
+    a, b = list(prev_scene.primitives), list(scene.primitives)
+    if len(a) != len(b):
+        raise ValueError(f"the scenes list {len(a)} and {len(b)} primitives: motion needs the same primitives in "
+                         f"the same order")
+    rows = np.tile(IDENTITY_ROW, (len(b), 1))
+    for i, (p, c) in enumerate(zip(a, b)):
+        if not _same_primitive(p, c):
+            raise ValueError(f"primitive {i} differs between the scenes (type, face count or BSDF): motion needs "
+                             f"the same primitives in the same order")
+        if getattr(c, "type_name", "") == "sphere":
+            if p.radius != c.radius:
+                rows[i] = np.nan
+            elif not np.array_equal(p.center, c.center):
+                rows[i, [3, 7, 11]] = np.asarray(p.center, np.float64) - np.asarray(c.center, np.float64)
+            continue
+        if not hasattr(c, "trans_mat"):
+            if not np.array_equal(p.vertices, c.vertices):
+                rows[i] = np.nan
+            continue
+        tp, tc = np.asarray(p.trans_mat, np.float64), np.asarray(c.trans_mat, np.float64)
+        if np.array_equal(tp, tc):
+            continue
+        try:
+            m = tp @ np.linalg.inv(tc)
+        except np.linalg.LinAlgError:
+            rows[i] = np.nan
+            continue
+        r = m[:3, :3]
+        rigid = (np.isfinite(m).all() and np.abs(r.T @ r - np.eye(3)).max() <= RIGID_TOL
+                 and abs(np.linalg.det(r) - 1.0) <= RIGID_TOL)
+        rows[i] = m[:3].reshape(12) if rigid else np.nan
+    return rows.astype(np.float32)
+
+
+def _motion_args(ids, motion, W, H):
+    """(ids, motion, n_objects) of a call with per-object motion, as contiguous arrays."""
+    if motion is None:
+        raise ValueError("ids need a motion table: motion=(n_objects, 12) float32 rows (motion_rows), which may be empty")
+    ids = np.ascontiguousarray(ids, np.int32)
+    if ids.shape != (W, H):
+        raise ValueError(f"ids must be {(W, H)}, not {ids.shape}")
+    motion = np.ascontiguousarray(motion, np.float32)
+    if motion.ndim != 2 or motion.shape[1] != 12:
+        raise ValueError(f"motion must be (n_objects, 12), not {motion.shape}")
+    if motion.shape[0] > MAX_OBJECTS:
+        raise ValueError(f"motion holds {motion.shape[0]} rows, more than {MAX_OBJECTS}")
+    return ids, motion, motion.shape[0]
+
+
 def temporal_accumulate(mean, feat, cam, prev=None, *, alpha=TEMPORAL_ALPHA, alpha_m=TEMPORAL_ALPHA_M,
                         tau_n=TEMPORAL_TAU_N, tau_z=TEMPORAL_TAU_Z, tau_a=TEMPORAL_TAU_A, eps_a=EPS_A,
-                        min_history=TEMPORAL_MIN_HISTORY, w_min=TEMPORAL_W_MIN, device=0, return_color=True):
+                        min_history=TEMPORAL_MIN_HISTORY, w_min=TEMPORAL_W_MIN, device=0, return_color=True,
+                        ids=None, motion=None):
     """One frame of temporal accumulation.  `mean` (W, H, 3), `feat` (W, H, 8) and `cam` (the packed 24-float
     record) are this frame's; prev = (state, feat, cam) is the previous frame's, None on the first.  The
     previous state is reprojected through this frame's first hits into the previous camera, tested for
@@ -357,24 +458,48 @@ def temporal_accumulate(mean, feat, cam, prev=None, *, alpha=TEMPORAL_ALPHA, alp
     (W, H, 8) state and the integrated colour (W, H, 3), re-modulated; just the state with
     return_color=False.  state[..., 3] is the history length, state[..., 6] the variance of the integrated
     luminance, NaN where the history is shorter than min_history: denoise_variance(colour, feat,
-    variance=state[..., 6], variance_fallback="spatial") filters the result."""
+    variance=state[..., 6], variance_fallback="spatial") filters the result.
+
+    ids, motion: None (default) is the static world above (prt_temporal_accumulate).  With `ids` (W, H) int32
+    (object_ids) and `motion` (n_objects, 12) float32 (motion_rows), prev is (state, feat, cam, ids) and the
+    history follows moving objects (prt_temporal_accumulate_motion): a pixel whose id has a row is carried by
+    it into the previous frame's world before it is projected, and a tap counts only where the previous id
+    equals the pixel's."""
     mean, feat, W, H = _frame_and_features(mean, feat)
     cam = _camera_record(cam, "cam")
     par = _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min)
-    p_state = p_feat = p_cam = None
+    moving = ids is not None
+    if motion is not None and not moving:
+        raise ValueError("a motion table needs the frame's ids (object_ids)")
+    if moving:
+        ids, motion, n_objects = _motion_args(ids, motion, W, H)
+    p_state = p_feat = p_cam = p_ids = None
     if prev is not None:
-        p_state, p_feat, p_cam = prev
+        if len(prev) != (4 if moving else 3):
+            raise ValueError("prev must be (state, feat, cam, ids) with ids and (state, feat, cam) without, not "
+                             f"{len(prev)} items")
+        p_state, p_feat, p_cam = prev[:3]
         p_state = np.ascontiguousarray(p_state, np.float32)
         p_feat = np.ascontiguousarray(p_feat, np.float32)
         if p_state.shape != (W, H, TEMPORAL_CHANNELS) or p_feat.shape != (W, H, FEATURE_CHANNELS):
             raise ValueError(f"prev must hold a {(W, H, TEMPORAL_CHANNELS)} state and {(W, H, FEATURE_CHANNELS)} "
                              f"features (the resolution cannot change), not {p_state.shape} and {p_feat.shape}")
         p_cam = _camera_record(p_cam, "prev's camera")
+        if moving:
+            p_ids = np.ascontiguousarray(prev[3], np.int32)
+            if p_ids.shape != (W, H):
+                raise ValueError(f"prev's ids must be {(W, H)}, not {p_ids.shape}")
     state = temporal_state(W, H)
     color = np.zeros_like(mean) if return_color else None
-    N.check_denoise(N.lib().prt_temporal_accumulate(int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam), N.ptr(p_feat),
-                                                    N.ptr(p_cam), N.ptr(p_state), W, H, N.ptr(par), N.ptr(state),
-                                                    N.ptr(color), None))
+    if moving:
+        N.check_denoise(N.lib().prt_temporal_accumulate_motion(
+            int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam), N.ptr(p_feat), N.ptr(p_cam), N.ptr(p_state), N.ptr(ids),
+            N.ptr(p_ids), N.ptr(motion) if n_objects else None, n_objects, W, H, N.ptr(par), N.ptr(state), N.ptr(color),
+            None))
+    else:
+        N.check_denoise(N.lib().prt_temporal_accumulate(int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam),
+                                                        N.ptr(p_feat), N.ptr(p_cam), N.ptr(p_state), W, H, N.ptr(par),
+                                                        N.ptr(state), N.ptr(color), None))
     return (state, color) if return_color else state
 
 
@@ -382,15 +507,30 @@ def temporal_accumulate_device(d_color_ptr, d_feat_ptr, cam, W, H, d_state_ptr, 
                                d_prev_state_ptr=None, d_out_color_ptr=None, d_out_var_ptr=None, alpha=TEMPORAL_ALPHA,
                                alpha_m=TEMPORAL_ALPHA_M, tau_n=TEMPORAL_TAU_N, tau_z=TEMPORAL_TAU_Z,
                                tau_a=TEMPORAL_TAU_A, eps_a=EPS_A, min_history=TEMPORAL_MIN_HISTORY,
-                               w_min=TEMPORAL_W_MIN, device=0, stream_ptr=None):
+                               w_min=TEMPORAL_W_MIN, device=0, stream_ptr=None, d_ids_ptr=None, d_prev_ids_ptr=None,
+                               d_motion_ptr=None, n_objects=None):
     """prt_temporal_accumulate_device: temporal_accumulate on device pointers, enqueued on `stream_ptr` without
     a host synchronisation.  `cam` and `prev_cam` are host records; the state planes (W x H x 8 floats) must
     be 16-byte aligned and distinct; `d_out_var_ptr` (W x H floats) receives the variance plane, the
-    `d_in_var_ptr` of denoise_variance_device(..., variance_fallback="spatial")."""
+    `d_in_var_ptr` of denoise_variance_device(..., variance_fallback="spatial").
+
+    With `d_ids_ptr` (W x H int32) the call is prt_temporal_accumulate_motion_device: `d_prev_ids_ptr` goes with
+    the other previous planes, `d_motion_ptr` is the device table of `n_objects` rows of 12 floats (it may be
+    None only with n_objects=0)."""
     cam = _camera_record(cam, "cam")
     p_cam = None if prev_cam is None else _camera_record(prev_cam, "prev_cam")
     par = _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min)
-    N.check_denoise(N.lib().prt_temporal_accumulate_device(
+    if not d_ids_ptr:
+        if d_prev_ids_ptr or d_motion_ptr or n_objects is not None:
+            raise ValueError("d_prev_ids_ptr, d_motion_ptr and n_objects need the frame's d_ids_ptr")
+        N.check_denoise(N.lib().prt_temporal_accumulate_device(
+            int(device), _vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam), _vp(d_prev_feat_ptr), N.ptr(p_cam),
+            _vp(d_prev_state_ptr), int(W), int(H), N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr),
+            _vp(stream_ptr)))
+        return
+    if n_objects is None:
+        raise ValueError("ids need a motion table: n_objects (which may be 0) and d_motion_ptr")
+    N.check_denoise(N.lib().prt_temporal_accumulate_motion_device(
         int(device), _vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam), _vp(d_prev_feat_ptr), N.ptr(p_cam),
-        _vp(d_prev_state_ptr), int(W), int(H), N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr),
-        _vp(stream_ptr)))
+        _vp(d_prev_state_ptr), _vp(d_ids_ptr), _vp(d_prev_ids_ptr), _vp(d_motion_ptr), int(n_objects), int(W), int(H),
+        N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr), _vp(stream_ptr)))

@@ -13,7 +13,7 @@ from .mathematics.constants import DIRECT_LIGHT_RGB
 
 class FlatScene:
     def __init__(self, tri_v, tri_n, tri_mat, tri_prim, prim_lo, prim_hi, mat, light_tri, light_off,
-                 direct_rgb=DIRECT_LIGHT_RGB, sph=None, sph_mat=None):
+                 direct_rgb=DIRECT_LIGHT_RGB, sph=None, sph_mat=None, sph_prim=None):
         self.tri_v = np.ascontiguousarray(tri_v, np.float32).reshape(-1, 9)
         self.tri_n = np.ascontiguousarray(tri_n, np.float32).reshape(-1, 3)
         self.tri_mat = np.ascontiguousarray(tri_mat, np.int32)
@@ -26,6 +26,9 @@ class FlatScene:
         self.direct_rgb = np.ascontiguousarray(direct_rgb, np.float32)
         self.sph = np.zeros((0, 4), np.float32) if sph is None else np.ascontiguousarray(sph, np.float32).reshape(-1, 4)
         self.sph_mat = np.zeros(0, np.int32) if sph_mat is None else np.ascontiguousarray(sph_mat, np.int32)
+        # sphere k's index in scene.primitives (tri_prim's counterpart; -1 where the caller gave none)
+        self.sph_prim = (np.full(self.sph.shape[0], -1, np.int32) if sph_prim is None
+                         else np.ascontiguousarray(sph_prim, np.int32))
 
     @property
     def n_tri(self):
@@ -40,7 +43,7 @@ def flatten_scene(scene):
     """Scene (core.scene.Scene) → FlatScene."""
     mats, mat_index = [], {}
     tri_v, tri_n, tri_mat, tri_prim, prim_lo, prim_hi = [], [], [], [], [], []
-    sph, sph_mat = [], []
+    sph, sph_mat, sph_prim = [], [], []
     light_tri, light_off = [], [0]
     base = 0
     for pid, prim in enumerate(scene.primitives):
@@ -55,6 +58,7 @@ def flatten_scene(scene):
         if getattr(prim, "type_name", "") == "sphere":
             sph.append([*np.asarray(prim.center, np.float32), np.float32(prim.radius)])
             sph_mat.append(m)
+            sph_prim.append(pid)
             continue
         v32 = np.asarray(prim.vertices, np.float32)
         f = np.asarray(prim.faces, np.int64)
@@ -73,4 +77,5 @@ def flatten_scene(scene):
                      np.concatenate(tri_mat) if tri_mat else np.zeros(0), np.concatenate(tri_prim) if tri_prim else np.zeros(0),
                      np.stack(prim_lo), np.stack(prim_hi), np.asarray(mats, np.float32), np.asarray(light_tri, np.int32),
                      np.asarray(light_off, np.int32), DIRECT_LIGHT_RGB,
-                     np.asarray(sph, np.float32) if sph else None, np.asarray(sph_mat, np.int32) if sph_mat else None)
+                     np.asarray(sph, np.float32) if sph else None, np.asarray(sph_mat, np.int32) if sph_mat else None,
+                     np.asarray(sph_prim, np.int32) if sph_prim else None)

@@ -10,6 +10,7 @@ samples/s print, finish() tone map, out.png every 100 passes; main.py:107-125's
     python -m pyrenderer_amd --samples 8 --denoise --denoise-mode variance    # width from the image's own noise
     python -m pyrenderer_amd --samples 64 --denoise --denoise-mode variance --variance-batches 8   # ... from sample moments
     python -m pyrenderer_amd --samples 2 --frames 24 --orbit 2 --temporal --denoise --denoise-mode variance   # turntable
+    python -m pyrenderer_amd --samples 2 --frames 24 --spin 5 6 --temporal --denoise --denoise-mode variance    # a box turns
     python -m pyrenderer_amd --adaptive 0.05 --batch-spp 8 --max-samples 256              # until the noise is below 5 %
 
 Every sample runs through libprt's HIP path (core.tracing.render / Accumulator); there is
@@ -80,6 +81,10 @@ def parse(argv=None):
                     help="with --frames: carry the previous frame's colour and luminance moments into the next "
                          "camera (temporal accumulation); filtered with --denoise --denoise-mode variance, or "
                          "written as accumulated without --denoise")
+    ap.add_argument("--spin", nargs=2, default=None, metavar=("PRIM", "DEG"),
+                    help="with --frames: turn primitive PRIM (its index in the scene) by DEG degrees per frame about "
+                         "the vertical axis through the centre of its bounding box; with --temporal the history "
+                         "follows it (per-object motion and an object-id test); usable with --orbit 0")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
                     help="adaptive sampling: render in batches of --batch-spp and stop every 64 x 64 tile once the "
                          "relative standard error of its pixels' demodulated luminance is at most TARGET; needs "
@@ -113,8 +118,15 @@ def parse(argv=None):
             ap.error("--variance-batches with --state needs --interval (every pass is a batch)")
     if args.frames < 0:
         ap.error(f"--frames must be >= 0, not {args.frames}")
+    if args.spin is not None:
+        try:
+            args.spin = (int(args.spin[0]), float(args.spin[1]))
+        except ValueError:
+            ap.error(f"--spin takes a primitive index and degrees per frame, not {args.spin[0]!r} {args.spin[1]!r}")
+        if args.spin[0] < 0 or not np.isfinite(args.spin[1]):
+            ap.error(f"--spin needs a primitive index >= 0 and finite degrees, not {args.spin[0]} {args.spin[1]}")
     if not args.frames:
-        for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal)):
+        for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal), ("--spin", args.spin)):
             if given:
                 ap.error(f"{flag} needs --frames N")
     else:
@@ -145,7 +157,7 @@ def _check_adaptive(ap, args):
         return
     clash = [flag for flag, given in (("--devices", len(args.devices) != 1), ("--interval", args.interval > 0),
                                       ("--variance-batches", args.variance_batches), ("--temporal", args.temporal),
-                                      ("--frames", args.frames), ("--state", args.state)) if given]
+                                      ("--frames", args.frames), ("--state", args.state), ("--spin", args.spin)) if given]
     if clash:
         ap.error(f"--adaptive renders one image in batches on one device and keeps its own moments: it cannot be "
                  f"combined with {', '.join(clash)}")
@@ -204,8 +216,15 @@ def frame_path(out, t):
 
 
 def render_frames(args, scene, camera, W, H):
-    """--frames N --orbit DEG [--temporal]: one image per camera; returns the last frame's mean."""
+    """--frames N --orbit DEG [--spin PRIM DEG] [--temporal]: one image per camera; returns the last frame's mean."""
     from .core.tracing import build_world
+    scenes = None
+    if args.spin is not None:
+        from .scenes import spun
+        try:
+            scenes = spun(scene, args.spin[0], args.spin[1], args.frames)
+        except ValueError as e:
+            raise SystemExit(f"--spin: {e}")
     world = build_world(scene, (args.devices[0],))
     it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
     acc = None
@@ -217,9 +236,16 @@ def render_frames(args, scene, camera, W, H):
         cam = orbit(camera, t * args.orbit)
         t0 = time.perf_counter()
         if acc is not None:
-            acc.add(cam)
+            if scenes is None:
+                acc.add(cam)
+            else:
+                acc.add(cam, scenes[t])
             mean = acc.denoised(iterations=it) if args.denoise else acc.accumulated()
         else:
+            if scenes is not None and t > 0:   # every frame stands alone, in its own world
+                for ds in world.device_scenes.values():
+                    ds.close()
+                world = build_world(scenes[t], (args.devices[0],))
             frame = _Frame.of(scene, cam, depth=args.depth, seed=args.seed, resolution=(W, H),
                               devices=(args.devices[0],), world=world, nee=args.nee)
             mean = _mean(frame.unpack(frame.add_samples(t * args.samples, args.samples)), args.samples)

@@ -9,7 +9,8 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
     python tools/denoise_time.py --mode adaptive --sizes 512 4096   # prt_adaptive_update_device, tile 64: every tile, and every other one
     python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
     python tools/denoise_time.py --mode features --sizes 512 4096   # prt_features_device (1 and 8 samples); host wall clock of both compositions at 512^2
-    python tools/denoise_time.py --temporal --sizes 512 4096        # prt_temporal_accumulate_device, and beside it the filter with and without the spatial fallback
+    python tools/denoise_time.py --temporal --sizes 512 4096        # prt_temporal_accumulate_device, its motion form, and beside them the filter with and without the spatial fallback
+    python tools/denoise_time.py --temporal --ab-lib abtmp/libprt_parent.so   # ... and the plain entry point of another build of the library, alternating
 """
 import argparse
 import json
@@ -37,6 +38,10 @@ def main():
     ap.add_argument("--temporal", action="store_true",
                     help="time the temporal accumulation (a camera turned by 2 degrees) and the variance-guided filter "
                          "that follows it")
+    ap.add_argument("--ab-lib", metavar="PATH",
+                    help="--temporal: another build of libprt.so whose prt_temporal_accumulate_device is timed in "
+                         "alternation with this build's, --ab-rounds times each")
+    ap.add_argument("--ab-rounds", type=int, default=3)
     a = ap.parse_args()
     import torch
     from pyrenderer_amd import denoise as D
@@ -250,7 +255,30 @@ def time_temporal(a, scene, cam, world):
             D.denoise_variance_device(d_col.data_ptr(), d_feats[1].data_ptr(), size, size, d_out.data_ptr(),
                                       d_work.data_ptr(), need, iterations=a.iterations, stream_ptr=stream.cuda_stream, **kw)
 
-        legs = (("temporal_time", temporal, n * 156),
+        # the motion leg: the middle third of the frame (a band in x) carries a non-identity row, a turn of one
+        # degree about the vertical axis through the box's centre and a shift of 1 cm; both id planes are the band
+        band = ((np.arange(size) * 3) // size == 1).astype(np.int32)
+        d_ids = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(band[:, None], (size, size)))).to(dev)
+        t = np.radians(1.0)
+        rows = np.tile(D.IDENTITY_ROW, (3, 1))
+        rot = np.array([[np.cos(t), 0, np.sin(t)], [0, 1, 0], [-np.sin(t), 0, np.cos(t)]])
+        centre = np.array([0.0, 1.0, 0.0])
+        rows[1] = np.concatenate([rot, (centre - rot @ centre + (0.01, 0.0, 0.0))[:, None]], 1).reshape(12)
+        d_rows = torch.from_numpy(rows.astype(np.float32)).to(dev)
+        torch.cuda.synchronize(dev)
+
+        def temporal_motion():
+            D.temporal_accumulate_device(d_c.data_ptr(), d_feats[1].data_ptr(), recs[1], size, size, d_states[1].data_ptr(),
+                                         d_prev_feat_ptr=d_feats[0].data_ptr(), prev_cam=recs[0],
+                                         d_prev_state_ptr=d_states[0].data_ptr(), d_out_color_ptr=d_col.data_ptr(),
+                                         d_out_var_ptr=d_var.data_ptr(), min_history=1.0, stream_ptr=stream.cuda_stream,
+                                         d_ids_ptr=d_ids.data_ptr(), d_prev_ids_ptr=d_ids.data_ptr(),
+                                         d_motion_ptr=d_rows.data_ptr(), n_objects=3)
+
+        if a.ab_lib:
+            time_temporal_ab(a, size, temporal, stream, dev, d_c, d_feats, recs, d_states, d_col, d_var)
+        legs = (("temporal_motion_time", temporal_motion, n * 164),
+                ("temporal_time", temporal, n * 156),
                 ("denoise_var_time", filt, None),
                 ("denoise_var_mixed_time", lambda: filt(d_in_var_ptr=d_var.data_ptr(), variance_fallback="spatial"), None))
         valid = None
@@ -259,7 +287,9 @@ def time_temporal(a, scene, cam, world):
             med = ms[len(ms) // 2]
             row = dict(what=what, size=size, median_ms=round(med, 4), min_ms=round(ms[0], 4), max_ms=round(ms[-1], 4),
                        reps=a.reps)
-            if what == "temporal_time":
+            if what in ("temporal_time", "temporal_motion_time"):
+                # the motion form reads 4 B of id and, shared between neighbours like the other tap planes, 4 B of
+                # previous id on top; the 36 B table stays in cache
                 # compulsory traffic: colour 12, features 32, the previous state 32 and features 32 read (each tap
                 # plane once: neighbouring pixels share their taps), state 32, colour 12 and variance 4 written
                 st = d_states[1].cpu().numpy()
@@ -268,10 +298,39 @@ def time_temporal(a, scene, cam, world):
                 row.update(bytes_total=total, implied_gbs=round(total / (med * 1e-3) / 1e9, 1),
                            hbm_peak_fraction=round(total / (med * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                            hit_pixels_with_history=round(valid, 4))
+                if what == "temporal_motion_time":
+                    row.update(pixels_with_a_row=round(float(band.mean()), 4))
             else:
                 row.update(iterations=a.iterations)
             print(json.dumps(row), flush=True)
-        del d_c, d_feats, d_states, d_col, d_var, d_out, d_work
+        del d_c, d_feats, d_states, d_col, d_var, d_out, d_work, d_ids, d_rows
+
+
+def time_temporal_ab(a, size, this_build, stream, dev, d_c, d_feats, recs, d_states, d_col, d_var):
+    """The plain prt_temporal_accumulate_device of this build and of the build at a.ab_lib on the same buffers,
+    a.ab_rounds times each in alternation: whether a change to the unit left the plain kernel's time alone."""
+    import ctypes
+    from pyrenderer_amd import _native as N
+    from pyrenderer_amd import denoise as D
+    other = ctypes.CDLL(os.path.abspath(a.ab_lib))
+    fn = other.prt_temporal_accumulate_device
+    fn.restype, fn.argtypes = N.EXPORTS["prt_temporal_accumulate_device"]
+    par = np.array([D.TEMPORAL_ALPHA, D.TEMPORAL_ALPHA_M, D.TEMPORAL_TAU_N, D.TEMPORAL_TAU_Z, D.TEMPORAL_TAU_A, D.EPS_A,
+                    1.0, D.TEMPORAL_W_MIN], np.float32)
+    vp = ctypes.c_void_p
+
+    def other_build():
+        rc = fn(0, vp(d_c.data_ptr()), vp(d_feats[1].data_ptr()), N.ptr(recs[1]), vp(d_feats[0].data_ptr()), N.ptr(recs[0]),
+                vp(d_states[0].data_ptr()), size, size, N.ptr(par), vp(d_states[1].data_ptr()), vp(d_col.data_ptr()),
+                vp(d_var.data_ptr()), vp(stream.cuda_stream))
+        assert rc == 0, rc
+
+    for r in range(a.ab_rounds):
+        for build, run in (("this", this_build), ("other", other_build)):
+            ms = _median_ms(run, stream, a.warmup, a.reps)
+            print(json.dumps(dict(what="temporal_time_ab", build=build, lib=os.path.basename(a.ab_lib) if build == "other" else "libprt.so",
+                                  round=r, size=size, median_ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4),
+                                  max_ms=round(ms[-1], 4), reps=a.reps)), flush=True)
 
 
 def time_features(a, cam, world):

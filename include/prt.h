@@ -594,7 +594,7 @@ int prt_temporal_accumulate_device(int device, const float* d_color, const float
  *              the device form; the host form copies it.  NULL is allowed only when n_objects == 0
  *   n_objects  0..1048576
  * The contract is prt_temporal_accumulate's steps 1-8 with these changes, every operation one IEEE f32
- * operation in this association (tests/temporal_motion_ref.py restates it in NumPy):
+ * operation in this association (tests/temporal_ref.py restates them as its `ids` clauses):
  *  Id and row.  An id is valid when 0 <= id < n_objects.  Any other id (-1, too large, INT_MIN) has no row: its
  *     pixel reprojects as the static path does and no table entry is read for it.  A valid id whose row holds
  *     an entry that is not finite means "no previous pose": the pixel takes step 2, decided before anything is

@@ -461,19 +461,14 @@ class TemporalAccumulator:
                       devices=(self.device,), tile=self.tile, world=self.world, nee=self.nee)
         mean = _mean(f.unpack(f.add_samples(self.frames * self.spp, self.spp)), self.spp)
         feat = f.features()
-        if motion is None:
-            state, color = D.temporal_accumulate(mean, feat, f.cam, self._prev, device=self.device, **self.params)
-            self._ids = None
-            self._prev = (state, feat, f.cam)
-        else:
-            ids = D.object_ids(f.ds, f.cam, f.W, f.H)
-            prev = self._prev
-            if prev is not None and len(prev) == 3:   # the frames so far were static: their id plane is due now
-                prev = (*prev, self.object_ids())
-            state, color = D.temporal_accumulate(mean, feat, f.cam, prev, device=self.device, ids=ids, motion=motion,
-                                                 **self.params)
-            self._moving, self._ids = True, ids
-            self._prev = (state, feat, f.cam, ids)
+        moving = motion is not None
+        ids = D.object_ids(f.ds, f.cam, f.W, f.H) if moving else None
+        prev = self._prev
+        if prev is not None and moving:   # the last frame's plane: kept, or due now after a static frame
+            prev = (*prev, self.object_ids())
+        state, color = D.temporal_accumulate(mean, feat, f.cam, prev, device=self.device, ids=ids, motion=motion,
+                                             **self.params)
+        self._moving, self._prev, self._ids = moving, (state, feat, f.cam), ids
         self.frame, self._mean, self._color, self._state = f, mean, color, state
         if stale is not None:   # the previous frame's world: nothing reads it any more
             for ds in stale.device_scenes.values():
@@ -553,10 +548,7 @@ def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, devi
                               world=world, nee=nee, **temporal_params)
     out = []
     for t, cam in enumerate(cameras):
-        if scenes is None:
-            acc.add(cam)
-        else:
-            acc.add(cam, scenes[t])
+        acc.add(cam, None if scenes is None else scenes[t])
         out.append(acc.denoised() if denoise else acc.accumulated())
     return np.stack(out).astype(np.float32)
 

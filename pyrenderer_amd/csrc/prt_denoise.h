@@ -56,42 +56,43 @@ struct TemporalParams {
     float alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min;
 };
 
+// Per-object motion.  ids / prev_ids: W x H int32 [x][y], this frame's and the previous frame's object id per
+// pixel (prev_ids null on the first frame, with the other prev pointers).  rows: n_objects x 12 floats, per
+// object the row-major 3 x 4 matrix that takes a world position of this frame to the same material point's
+// position in the previous frame; not read when n_objects is 0, where it may be null.
+constexpr int kMaxObjects = 1 << 20;
+struct Motion {
+    const int32_t* ids;
+    const int32_t* prev_ids;
+    const float* rows;
+    int n_objects;
+};
+
 // Enqueue temporal_kernel on `stream` of the current device: this frame's mean radiance d_color (W x H x 3)
 // and features d_feat (W x H x 8) blended into the previous frame's state, reprojected from the previous
-// camera.  cam24 / prev_cam24 are HOST pointers to the 24-float records (read before the call returns);
-// d_prev_feat, prev_cam24 and d_prev_state are all null on the first frame.  is_static: the two records are
-// bytewise equal, every pixel reads its own previous state.  d_state and d_prev_state hold W x H x 8 floats,
+// camera (tests/temporal_ref.py restates it).  cam24 / prev_cam24 are HOST pointers to the 24-float records
+// (read before the call returns); d_prev_feat, prev_cam24 and d_prev_state are all null on the first frame.
+// cameras_equal: the two records are bytewise equal.  d_state and d_prev_state hold W x H x 8 floats,
 // 16-byte aligned, and must not be the same plane (taps read neighbours); d_out_color (W x H x 3,
 // re-modulated) and d_out_var (W x H, the state's variance plane) may be null.
+//
+// motion: null is the static world (temporal_kernel<false>): with equal cameras every pixel reads its own
+// previous state.  Otherwise its device pointers go to temporal_kernel<true>, the table's only when n_objects
+// > 0.  An id outside 0..n_objects-1 has no row: its pixel reprojects as the static world's does and no table
+// entry is read for it.  A row with an entry that is not finite means "no previous pose": the pixel starts
+// afresh.  A tap counts only if its previous id equals the pixel's id.  With equal cameras a pixel takes its
+// own previous state alone if its id has no row or the row is bytewise the identity.
 //
 // Finiteness: a pixel that takes part has finite colour, demodulated colour and features.  Its state is
 // finite while |I_c| <= 2^62: the luminance and its square, the blends between two such values and the
 // variance then stay in range.  The variance plane holds a quiet NaN wherever the history is shorter
-// than min_history: prt_denoise_var_mixed reads it as "estimate here".
+// than min_history: prt_denoise_var_mixed reads it as "estimate here".  A finite row times a finite position
+// may overflow to inf or NaN, which fails the range test of the projection (a comparison with a NaN is false)
+// before any index is formed, so the pixel starts afresh.
 hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
-                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
-                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
-                            hipStream_t stream);
-
-// enqueue_temporal with per-object motion (temporal_kernel<true>; tests/temporal_motion_ref.py restates it).
-// d_ids / d_prev_ids: W x H int32 [x][y], this frame's and the previous frame's object id per pixel (d_prev_ids
-// null on the first frame, with the other prev pointers).  d_motion: n_objects x 12 floats, per object the
-// row-major 3 x 4 matrix that takes a world position of this frame to the same material point's position in
-// the previous frame; null only when n_objects is 0.  An id outside 0..n_objects-1 has no row: its pixel
-// reprojects as enqueue_temporal's does and no table entry is read for it.  A row with an entry that is not
-// finite means "no previous pose": the pixel starts afresh.  A tap counts only if its previous id equals the
-// pixel's id.  cameras_equal: the two records are bytewise equal; a pixel then takes its own previous state
-// alone if its id has no row or the row is bytewise the identity.
-//
-// Finiteness: enqueue_temporal's statement holds; a finite row times a finite position may overflow to inf or
-// NaN, which fails the range test of the projection (a comparison with a NaN is false) before any index is
-// formed, so the pixel starts afresh.
-constexpr int kMaxObjects = 1 << 20;
-hipError_t enqueue_temporal_motion(const float* d_color, const float* d_feat, const float* cam24,
-                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
-                                   const int32_t* d_ids, const int32_t* d_prev_ids, const float* d_motion, int n_objects,
-                                   int W, int H, bool cameras_equal, const TemporalParams& p, float* d_state,
-                                   float* d_out_color, float* d_out_var, hipStream_t stream);
+                            const float* prev_cam24, const float* d_prev_state, const Motion* motion, int W, int H,
+                            bool cameras_equal, const TemporalParams& p, float* d_state, float* d_out_color,
+                            float* d_out_var, hipStream_t stream);
 
 // ---- variance from per-pixel sample moments ----
 

@@ -513,7 +513,7 @@ __global__ __launch_bounds__(kChunk) void adaptive_kernel(const float* __restric
 }
 
 // ---- temporal accumulation (DESIGN.md §11 "Temporal accumulation" and "Moving objects"; tests/temporal_ref.py
-// restates the static instantiation, tests/temporal_motion_ref.py the one with per-object motion) ----
+// restates both instantiations, the one with per-object motion as its `ids` clauses) ----
 // The previous frame's integrated demodulated colour and luminance moments, reprojected through the first-hit
 // features into this frame's camera (the temporal half of SVGF, Schied et al. 2017).  The state is two float4
 // per pixel: (I.rgb, h) and (m1, m2, var, 0).  The four bilinear taps of a pixel come straight from global
@@ -529,14 +529,6 @@ struct Cameras {
     float sw, sh, fd;
     float prev[12];
     float psw, psh, pfd;
-};
-
-// per-object motion (kMotion): the two id planes, the table of 3 x 4 rows and its length; all null / 0 without
-struct Motion {
-    const int32_t* ids;
-    const int32_t* prev_ids;
-    const float* rows;
-    int n_objects;
 };
 
 // kMotion false is the static world: `mo` is not read and every pixel goes the way `cams_equal` says.  kMotion
@@ -838,24 +830,17 @@ Cameras camera_parts(const float* cam24, const float* prev_cam24) {
 }  // namespace
 
 hipError_t enqueue_temporal(const float* d_color, const float* d_feat, const float* cam24, const float* d_prev_feat,
-                            const float* prev_cam24, const float* d_prev_state, int W, int H, bool is_static,
-                            const TemporalParams& p, float* d_state, float* d_out_color, float* d_out_var,
-                            hipStream_t stream) {
-    return launch(temporal_kernel<false>, W, H, stream, d_color, d_feat, d_prev_feat,
+                            const float* prev_cam24, const float* d_prev_state, const Motion* motion, int W, int H,
+                            bool cameras_equal, const TemporalParams& p, float* d_state, float* d_out_color,
+                            float* d_out_var, hipStream_t stream) {
+    Motion mo = {nullptr, nullptr, nullptr, 0};
+    if (motion) {
+        mo = *motion;
+        if (mo.n_objects == 0) mo.rows = nullptr;   // no rows, no table: whatever the caller's pointer held
+    }
+    return launch(!motion ? temporal_kernel<false> : temporal_kernel<true>, W, H, stream, d_color, d_feat, d_prev_feat,
                   reinterpret_cast<const float4*>(d_prev_state), camera_parts(cam24, prev_cam24), W, H,
-                  is_static ? 1 : 0, p, Motion{nullptr, nullptr, nullptr, 0}, reinterpret_cast<float4*>(d_state),
-                  d_out_color, d_out_var);
-}
-
-hipError_t enqueue_temporal_motion(const float* d_color, const float* d_feat, const float* cam24,
-                                   const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
-                                   const int32_t* d_ids, const int32_t* d_prev_ids, const float* d_motion, int n_objects,
-                                   int W, int H, bool cameras_equal, const TemporalParams& p, float* d_state,
-                                   float* d_out_color, float* d_out_var, hipStream_t stream) {
-    return launch(temporal_kernel<true>, W, H, stream, d_color, d_feat, d_prev_feat,
-                  reinterpret_cast<const float4*>(d_prev_state), camera_parts(cam24, prev_cam24), W, H,
-                  cameras_equal ? 1 : 0, p, Motion{d_ids, d_prev_ids, d_motion, n_objects},
-                  reinterpret_cast<float4*>(d_state), d_out_color, d_out_var);
+                  cameras_equal ? 1 : 0, p, mo, reinterpret_cast<float4*>(d_state), d_out_color, d_out_var);
 }
 
 }  // namespace prt_dn

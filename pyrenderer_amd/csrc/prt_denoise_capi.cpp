@@ -96,8 +96,11 @@ public:
         bufs_.push_back({d, from, to, n_bytes});
         return d;
     }
-    const float* in(const float* host, size_t count) { return static_cast<float*>(bytes(count * sizeof(float), host)); }
-    // a null `host` is an output nobody asked for: nothing is allocated
+    // an input of no floats (an empty motion table, whose `host` may be null) and an output nobody asked for
+    // (a null `host`): nothing is allocated
+    const float* in(const float* host, size_t count) {
+        return count ? static_cast<float*>(bytes(count * sizeof(float), host)) : nullptr;
+    }
     float* out(float* host, size_t count) {
         return host ? static_cast<float*>(bytes(count * sizeof(float), nullptr, host)) : nullptr;
     }
@@ -336,17 +339,9 @@ int check_temporal_cameras(const std::string& who, const float* cam24, const voi
     return PRT_OK;
 }
 
-// the motion arguments of prt_temporal_accumulate_motion and its device form; the plain entry points pass none
-struct MotionArgs {
-    const int32_t* ids;
-    const int32_t* prev_ids;
-    const float* motion;
-    int n_objects;
-};
-
 // NULL pointers, parameters, cameras and, with motion, the id planes and the table: everything the two forms of
 // a temporal entry point check alike
-int check_temporal_args(const std::string& who, const MotionArgs* m, int device, const float* color, const float* feat,
+int check_temporal_args(const std::string& who, const prt_dn::Motion* m, int device, const float* color, const float* feat,
                         const float* cam24, const float* prev_feat, const float* prev_cam24, const float* prev_state,
                         int W, int H, const float* params8, const float* state, prt_dn::TemporalParams* p,
                         bool* is_static) {
@@ -358,24 +353,12 @@ int check_temporal_args(const std::string& who, const MotionArgs* m, int device,
         return fail(PRT_ERR_ARG, who + ": prev_ids must be NULL together with prev_feat, prev_cam24 and prev_state or not at all");
     if (m->n_objects < 0 || m->n_objects > prt_dn::kMaxObjects)
         return fail(PRT_ERR_ARG, who + ": n_objects must be in 0.." + std::to_string(prt_dn::kMaxObjects));
-    if (m->n_objects > 0 && !m->motion) return fail(PRT_ERR_ARG, who + ": motion is NULL with n_objects > 0");
+    if (m->n_objects > 0 && !m->rows) return fail(PRT_ERR_ARG, who + ": motion is NULL with n_objects > 0");
     return PRT_OK;
 }
 
-hipError_t enqueue_temporal_any(const MotionArgs* m, const float* d_color, const float* d_feat, const float* cam24,
-                                const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state, int W, int H,
-                                bool is_static, const prt_dn::TemporalParams& p, float* d_state, float* d_out_color,
-                                float* d_out_var, hipStream_t stream) {
-    if (!m)
-        return prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
-                                        d_state, d_out_color, d_out_var, stream);
-    return prt_dn::enqueue_temporal_motion(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, m->ids,
-                                           m->prev_ids, m->n_objects > 0 ? m->motion : nullptr, m->n_objects, W, H,
-                                           is_static, p, d_state, d_out_color, d_out_var, stream);
-}
-
 // the device form of both temporal entry points; `m` holds device pointers
-int temporal_device(const std::string& who, const MotionArgs* m, int device, const float* d_color, const float* d_feat,
+int temporal_device(const std::string& who, const prt_dn::Motion* m, int device, const float* d_color, const float* d_feat,
                     const float* cam24, const float* d_prev_feat, const float* prev_cam24, const float* d_prev_state,
                     int W, int H, const float* params8, float* d_state, float* d_out_color, float* d_out_var,
                     void* stream) {
@@ -386,11 +369,11 @@ int temporal_device(const std::string& who, const MotionArgs* m, int device, con
     if (reinterpret_cast<uintptr_t>(d_state) % 16 != 0 || reinterpret_cast<uintptr_t>(d_prev_state) % 16 != 0)
         return fail(PRT_ERR_ARG, who + ": d_state and d_prev_state must be 16-byte aligned");
     if (m && (reinterpret_cast<uintptr_t>(m->ids) % 4 != 0 || reinterpret_cast<uintptr_t>(m->prev_ids) % 4 != 0 ||
-              reinterpret_cast<uintptr_t>(m->motion) % 4 != 0))
+              reinterpret_cast<uintptr_t>(m->rows) % 4 != 0))
         return fail(PRT_ERR_ARG, who + ": d_ids, d_prev_ids and d_motion must be 4-byte aligned");
     // every output against every input and against the other outputs
     const void* ins[] = {d_color, d_feat, d_prev_feat, d_prev_state, m ? m->ids : nullptr, m ? m->prev_ids : nullptr,
-                         m ? m->motion : nullptr};
+                         m ? m->rows : nullptr};
     const void* outs[] = {d_state, d_out_color, d_out_var};
     for (int i = 0; i < 3; ++i) {
         if (!outs[i]) continue;
@@ -403,13 +386,13 @@ int temporal_device(const std::string& who, const MotionArgs* m, int device, con
     }
     DeviceGuard g;
     DN_TRY(g.enter(who, device));
-    DN_HIP_TRY(enqueue_temporal_any(m, d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H, is_static, p,
-                                    d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
+    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, m, W, H, is_static,
+                                        p, d_state, d_out_color, d_out_var, static_cast<hipStream_t>(stream)));
     return PRT_OK;
 }
 
 // the host form of both; `m` holds host pointers, its planes and table are staged like the rest
-int temporal_host(const std::string& who, const MotionArgs* m, int device, const float* color, const float* feat,
+int temporal_host(const std::string& who, const prt_dn::Motion* m, int device, const float* color, const float* feat,
                   const float* cam24, const float* prev_feat, const float* prev_cam24, const float* prev_state, int W,
                   int H, const float* params8, float* state, float* out_color, float* out_var) {
     prt_dn::TemporalParams p;
@@ -425,11 +408,11 @@ int temporal_host(const std::string& who, const MotionArgs* m, int device, const
     const float* d_feat = s.in(feat, n * 8);
     const float* d_prev_feat = prev_feat ? s.in(prev_feat, n * 8) : nullptr;
     const float* d_prev_state = prev_state ? s.in(prev_state, n * prt_dn::kTemporalChannels) : nullptr;
-    MotionArgs d_m = {nullptr, nullptr, nullptr, 0};
+    prt_dn::Motion d_m = {nullptr, nullptr, nullptr, 0};
     if (m) {
         d_m.ids = static_cast<const int32_t*>(s.bytes(n * sizeof(int32_t), m->ids));
         if (m->prev_ids) d_m.prev_ids = static_cast<const int32_t*>(s.bytes(n * sizeof(int32_t), m->prev_ids));
-        if (m->n_objects > 0) d_m.motion = s.in(m->motion, (size_t)m->n_objects * 12);
+        d_m.rows = s.in(m->rows, (size_t)m->n_objects * 12);
         d_m.n_objects = m->n_objects;
     }
     float* d_state = s.out(state, n * prt_dn::kTemporalChannels);
@@ -437,8 +420,8 @@ int temporal_host(const std::string& who, const MotionArgs* m, int device, const
     float* d_out_var = s.out(out_var, n);
     if (s.oom()) return fail_oom(who);
     DN_HIP_TRY(s.upload());
-    DN_HIP_TRY(enqueue_temporal_any(m ? &d_m : nullptr, d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, W, H,
-                                    is_static, p, d_state, d_out_color, d_out_var, nullptr));
+    DN_HIP_TRY(prt_dn::enqueue_temporal(d_color, d_feat, cam24, d_prev_feat, prev_cam24, d_prev_state, m ? &d_m : nullptr,
+                                        W, H, is_static, p, d_state, d_out_color, d_out_var, nullptr));
     DN_HIP_TRY(s.download());
     return PRT_OK;
 }
@@ -564,7 +547,7 @@ int prt_temporal_accumulate_motion_device(int device, const float* d_color, cons
                                           const float* d_prev_state, const int32_t* d_ids, const int32_t* d_prev_ids,
                                           const float* d_motion, int n_objects, int W, int H, const float* params8,
                                           float* d_state, float* d_out_color, float* d_out_var, void* stream) {
-    const MotionArgs m = {d_ids, d_prev_ids, d_motion, n_objects};
+    const prt_dn::Motion m = {d_ids, d_prev_ids, d_motion, n_objects};
     return temporal_device("prt_temporal_accumulate_motion_device", &m, device, d_color, d_feat, cam24, d_prev_feat,
                            prev_cam24, d_prev_state, W, H, params8, d_state, d_out_color, d_out_var, stream);
 }
@@ -573,7 +556,7 @@ int prt_temporal_accumulate_motion(int device, const float* color, const float* 
                                    const float* prev_feat, const float* prev_cam24, const float* prev_state,
                                    const int32_t* ids, const int32_t* prev_ids, const float* motion, int n_objects,
                                    int W, int H, const float* params8, float* state, float* out_color, float* out_var) {
-    const MotionArgs m = {ids, prev_ids, motion, n_objects};
+    const prt_dn::Motion m = {ids, prev_ids, motion, n_objects};
     return temporal_host("prt_temporal_accumulate_motion", &m, device, color, feat, cam24, prev_feat, prev_cam24,
                          prev_state, W, H, params8, state, out_color, out_var);
 }

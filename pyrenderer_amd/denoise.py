@@ -447,6 +447,20 @@ def _motion_args(ids, motion, W, H):
     return ids, motion, motion.shape[0]
 
 
+def _temporal_entry(moving, form=""):
+    """The temporal entry point of `form` ("" or "_device"): prt_temporal_accumulate for the static world,
+    prt_temporal_accumulate_motion with an id plane."""
+    return getattr(N.lib(), "prt_temporal_accumulate" + ("_motion" if moving else "") + form)
+
+
+def _temporal_call(form, device, frame, prev, motion, W, H, par, outs):
+    """The one argument list of the four entry points.  frame = (colour, features, camera record) and prev =
+    (features, camera record, state) as pointers; motion = (ids, prev ids, table, n_objects) or None for the
+    static world; outs = (state, colour, variance), then the stream in the device form."""
+    N.check_denoise(_temporal_entry(motion is not None, form)(int(device), *frame, *prev, *(motion or ()), int(W), int(H),
+                                                               N.ptr(par), *outs))
+
+
 def temporal_accumulate(mean, feat, cam, prev=None, *, alpha=TEMPORAL_ALPHA, alpha_m=TEMPORAL_ALPHA_M,
                         tau_n=TEMPORAL_TAU_N, tau_z=TEMPORAL_TAU_Z, tau_a=TEMPORAL_TAU_A, eps_a=EPS_A,
                         min_history=TEMPORAL_MIN_HISTORY, w_min=TEMPORAL_W_MIN, device=0, return_color=True,
@@ -491,15 +505,9 @@ def temporal_accumulate(mean, feat, cam, prev=None, *, alpha=TEMPORAL_ALPHA, alp
                 raise ValueError(f"prev's ids must be {(W, H)}, not {p_ids.shape}")
     state = temporal_state(W, H)
     color = np.zeros_like(mean) if return_color else None
-    if moving:
-        N.check_denoise(N.lib().prt_temporal_accumulate_motion(
-            int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam), N.ptr(p_feat), N.ptr(p_cam), N.ptr(p_state), N.ptr(ids),
-            N.ptr(p_ids), N.ptr(motion) if n_objects else None, n_objects, W, H, N.ptr(par), N.ptr(state), N.ptr(color),
-            None))
-    else:
-        N.check_denoise(N.lib().prt_temporal_accumulate(int(device), N.ptr(mean), N.ptr(feat), N.ptr(cam),
-                                                        N.ptr(p_feat), N.ptr(p_cam), N.ptr(p_state), W, H, N.ptr(par),
-                                                        N.ptr(state), N.ptr(color), None))
+    table = (N.ptr(ids), N.ptr(p_ids), N.ptr(motion) if n_objects else None, n_objects) if moving else None
+    _temporal_call("", device, (N.ptr(mean), N.ptr(feat), N.ptr(cam)), (N.ptr(p_feat), N.ptr(p_cam), N.ptr(p_state)),
+                   table, W, H, par, (N.ptr(state), N.ptr(color), None))
     return (state, color) if return_color else state
 
 
@@ -520,17 +528,13 @@ def temporal_accumulate_device(d_color_ptr, d_feat_ptr, cam, W, H, d_state_ptr, 
     cam = _camera_record(cam, "cam")
     p_cam = None if prev_cam is None else _camera_record(prev_cam, "prev_cam")
     par = _params_temporal(alpha, alpha_m, tau_n, tau_z, tau_a, eps_a, min_history, w_min)
-    if not d_ids_ptr:
-        if d_prev_ids_ptr or d_motion_ptr or n_objects is not None:
-            raise ValueError("d_prev_ids_ptr, d_motion_ptr and n_objects need the frame's d_ids_ptr")
-        N.check_denoise(N.lib().prt_temporal_accumulate_device(
-            int(device), _vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam), _vp(d_prev_feat_ptr), N.ptr(p_cam),
-            _vp(d_prev_state_ptr), int(W), int(H), N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr),
-            _vp(stream_ptr)))
-        return
-    if n_objects is None:
-        raise ValueError("ids need a motion table: n_objects (which may be 0) and d_motion_ptr")
-    N.check_denoise(N.lib().prt_temporal_accumulate_motion_device(
-        int(device), _vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam), _vp(d_prev_feat_ptr), N.ptr(p_cam),
-        _vp(d_prev_state_ptr), _vp(d_ids_ptr), _vp(d_prev_ids_ptr), _vp(d_motion_ptr), int(n_objects), int(W), int(H),
-        N.ptr(par), _vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr), _vp(stream_ptr)))
+    table = None
+    if d_ids_ptr:
+        if n_objects is None:
+            raise ValueError("ids need a motion table: n_objects (which may be 0) and d_motion_ptr")
+        table = (_vp(d_ids_ptr), _vp(d_prev_ids_ptr), _vp(d_motion_ptr), int(n_objects))
+    elif d_prev_ids_ptr or d_motion_ptr or n_objects is not None:
+        raise ValueError("d_prev_ids_ptr, d_motion_ptr and n_objects need the frame's d_ids_ptr")
+    _temporal_call("_device", device, (_vp(d_color_ptr), _vp(d_feat_ptr), N.ptr(cam)),
+                   (_vp(d_prev_feat_ptr), N.ptr(p_cam), _vp(d_prev_state_ptr)), table, W, H, par,
+                   (_vp(d_state_ptr), _vp(d_out_color_ptr), _vp(d_out_var_ptr), _vp(stream_ptr)))

@@ -236,10 +236,7 @@ def render_frames(args, scene, camera, W, H):
         cam = orbit(camera, t * args.orbit)
         t0 = time.perf_counter()
         if acc is not None:
-            if scenes is None:
-                acc.add(cam)
-            else:
-                acc.add(cam, scenes[t])
+            acc.add(cam, None if scenes is None else scenes[t])
             mean = acc.denoised(iterations=it) if args.denoise else acc.accumulated()
         else:
             if scenes is not None and t > 0:   # every frame stands alone, in its own world

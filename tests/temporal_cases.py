@@ -72,6 +72,24 @@ def random_state(rng, W, H, max_h=6):
     return S
 
 
+def on_gpu(params, C, F, cam, prev, ids=None, motion=None):
+    """(state, out_color, out_var) of prt_temporal_accumulate, with `ids` of prt_temporal_accumulate_motion (prev
+    then holds the previous ids, and motion=None is an empty table), straight through the C ABI; the outputs
+    are pre-filled with 7.  params: the eight parameters by name, in the ABI's order."""
+    from pyrenderer_amd import _native as N
+    W, H = C.shape[:2]
+    par = np.array(list(params.values()), F32)
+    state, color, var = np.full((W, H, 8), 7, F32), np.full((W, H, 3), 7, F32), np.full((W, H), 7, F32)
+    ps, pf, pc, *pi = prev if prev is not None else (None,) * (3 if ids is None else 4)
+    moving, stem = (), "prt_temporal_accumulate"
+    if ids is not None:
+        n = 0 if motion is None else motion.shape[0]
+        moving, stem = (N.ptr(ids), N.ptr(pi[0]), N.ptr(motion) if n else None, n), stem + "_motion"
+    N.check_denoise(getattr(N.lib(), stem)(0, N.ptr(C), N.ptr(F), N.ptr(cam), N.ptr(pf), N.ptr(pc), N.ptr(ps), *moving,
+                                           W, H, N.ptr(par), N.ptr(state), N.ptr(color), N.ptr(var)))
+    return state, color, var
+
+
 KINDS = ("first", "static", "moved", "behind")
 
 

@@ -36,17 +36,8 @@ def restated():
 
 
 def _gpu(C, F, cam, prev, **kw):
-    """(state, out_color, out_var) of prt_temporal_accumulate, the outputs pre-filled with 7."""
-    from pyrenderer_amd import _native as N
-    W, H = C.shape[:2]
-    par = np.array([P[k] for k in ("alpha", "alpha_m", "tau_n", "tau_z", "tau_a", "eps_a", "min_history", "w_min")], F32)
-    for k, v in kw.items():
-        par[list(P).index(k)] = v
-    state, color, var = np.full((W, H, 8), 7, F32), np.full((W, H, 3), 7, F32), np.full((W, H), 7, F32)
-    ps, pf, pc = prev if prev is not None else (None, None, None)
-    N.check_denoise(N.lib().prt_temporal_accumulate(0, N.ptr(C), N.ptr(F), N.ptr(cam), N.ptr(pf), N.ptr(pc), N.ptr(ps),
-                                                    W, H, N.ptr(par), N.ptr(state), N.ptr(color), N.ptr(var)))
-    return state, color, var
+    """(state, out_color, out_var) of prt_temporal_accumulate with P, but for the parameters in `kw`."""
+    return TC.on_gpu({**P, **kw}, C, F, cam, prev)
 
 
 @pytest.mark.parametrize("kind", TC.KINDS)

@@ -1,5 +1,5 @@
 """Temporal accumulation across moving objects on the GPU: prt_temporal_accumulate_motion against the NumPy
-restatement (tests/temporal_motion_ref.py) bit for bit, the device entry point, the object-id plane, and a
+restatement (tests/temporal_ref.py with ids) bit for bit, the device entry point, the object-id plane, and a
 Cornell box whose short box turns, end to end.
 
 Measured on the MI355X for the end-to-end sequence below (Cornell 128^2, 1 spp, depth 8, the scene's static camera,
@@ -12,7 +12,6 @@ import pytest
 
 import temporal_cases as TC
 import temporal_motion_cases as MC
-import temporal_motion_ref as MR
 import temporal_ref as T
 from denoise_cases import bits, canaried, inner, rmse
 
@@ -34,22 +33,13 @@ def restated():
         for kind in MC.KINDS:
             C, F, cam, ids, motion, prev = MC.hostile(kind, W, H)
             out[(W, H, kind)] = (C, F, cam, ids, motion, prev,
-                                 MR.accumulate(C, F, cam, ids, motion, prev, diagnostics=True, **P))
+                                 T.accumulate(C, F, cam, prev, ids=ids, motion=motion, diagnostics=True, **P))
     return out
 
 
 def _gpu(C, F, cam, ids, motion, prev):
-    """(state, out_color, out_var) of prt_temporal_accumulate_motion, the outputs pre-filled with 7."""
-    from pyrenderer_amd import _native as N
-    W, H = C.shape[:2]
-    par = np.array([P[k] for k in NAMES], F32)
-    state, color, var = np.full((W, H, 8), 7, F32), np.full((W, H, 3), 7, F32), np.full((W, H), 7, F32)
-    ps, pf, pc, pi = prev if prev is not None else (None, None, None, None)
-    n = 0 if motion is None else motion.shape[0]
-    N.check_denoise(N.lib().prt_temporal_accumulate_motion(
-        0, N.ptr(C), N.ptr(F), N.ptr(cam), N.ptr(pf), N.ptr(pc), N.ptr(ps), N.ptr(ids), N.ptr(pi),
-        N.ptr(motion) if n else None, n, W, H, N.ptr(par), N.ptr(state), N.ptr(color), N.ptr(var)))
-    return state, color, var
+    """(state, out_color, out_var) of prt_temporal_accumulate_motion."""
+    return TC.on_gpu(P, C, F, cam, prev, ids, motion)
 
 
 def _same(got, want, what=""):
@@ -144,7 +134,7 @@ def test_device_form_on_a_side_stream(restated):
             assert np.array_equal(b_pids.cpu().numpy(), h_pids)
             assert np.array_equal(bits(d_ps.cpu().numpy()), bits(prev[0]))
         # an empty table with a NULL pointer: every id is without a row, the id test stays
-        want = MR.accumulate(C, F, cam, ids, None, prev, **P)
+        want = T.accumulate(C, F, cam, prev, ids=ids, **P)
         b_state2, p_state2 = canaried(torch, dev, n * 8)
         D.temporal_accumulate_device(d_c.data_ptr(), d_f.data_ptr(), cam, W, H, p_state2, stream_ptr=stream.cuda_stream,
                                      d_ids_ptr=p_ids, d_motion_ptr=None, n_objects=0, **P, **kw)

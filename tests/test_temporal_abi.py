@@ -10,35 +10,15 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from temporal_abi_cases import FAKE, GOOD, ILLEGAL as _ILLEGAL, PARAM_NAMES, call as _call, cam as _cam
 
 NAMES = ("prt_temporal_accumulate", "prt_temporal_accumulate_device", "prt_denoise_var_mixed",
          "prt_denoise_var_mixed_device")
-PARAM_NAMES = ("alpha", "alpha_m", "tau_n", "tau_z", "tau_a", "eps_a", "min_history", "w_min")
-GOOD = (0.2, 0.2, 0.9, 0.02, 0.05, 1e-2, 4.0, 0.25)
 VAR_GOOD = (1.0, 2.0, 1e-2, 1e-2, 1e-2)   # sigma_l, sigma_z, eps_a, eps_z, eps_l
 VAR_PARAM_NAMES = ("sigma_l", "sigma_z", "eps_a", "eps_z", "eps_l")
-FAKE = 4096   # a device "pointer" that is never dereferenced: the checks fail first
-# every parameter at each value that is illegal for it
-_ILLEGAL = {
-    "alpha": {"neg": -0.1, "above": 1.5, "nan": np.nan, "inf": np.inf},
-    "alpha_m": {"neg": -0.1, "above": 1.5, "nan": np.nan, "inf": np.inf},
-    "tau_n": {"below": -1.5, "above": 1.5, "nan": np.nan, "inf": np.inf},
-    "tau_z": {"0": 0.0, "neg": -1.0, "nan": np.nan, "inf": np.inf},
-    "tau_a": {"neg": -1.0, "nan": np.nan, "inf": np.inf},
-    "eps_a": {"0": 0.0, "neg": -1.0, "nan": np.nan, "inf": np.inf},
-    "min_history": {"0": 0.0, "half": 0.5, "neg": -1.0, "nan": np.nan, "inf": np.inf},
-    "w_min": {"0": 0.0, "neg": -1.0, "above": 1.5, "nan": np.nan, "inf": np.inf},
-}
-# ... and the edges of each range, which are legal
+# beside temporal_abi_cases.ILLEGAL: the edges of each range, which are legal
 _LEGAL = {"alpha": (0.0, 1.0), "alpha_m": (0.0, 1.0), "tau_n": (-1.0, 1.0), "tau_a": (0.0,), "min_history": (1.0,),
           "w_min": (1.0,)}
-
-
-def _cam(aperture=0.0):
-    cam = np.zeros(24, np.float32)
-    cam[[0, 5, 10, 15]] = 1.0
-    cam[16:20] = (0.5, 0.5, 1.0, aperture)
-    return cam
 
 
 def test_header_and_exports_carry_the_entry_points():
@@ -80,60 +60,6 @@ _T_CASES = [("null_color", b"NULL"), ("null_feat", b"NULL"), ("null_cam", b"NULL
             ("h_huge", b"W and H"), ("device_neg", b"device"), ("aperture", b"aperture"),
             ("prev_aperture", b"aperture"), ("cam_nan", b"camera record"), ("prev_cam_inf", b"camera record")]
 _T_CASES += [(f"{name}:{how}", name.encode()) for name in PARAM_NAMES for how in _ILLEGAL[name]]
-
-
-def _call(L, N, device_form, case):
-    W, H, device = 4, 3, 0
-    color = np.zeros((W, H, 3), np.float32)
-    feat = np.zeros((W, H, 8), np.float32)
-    state = np.ones((W, H, 8), np.float32)
-    pfeat, pstate = feat.copy(), np.zeros((W, H, 8), np.float32)
-    cam, pcam = _cam(), _cam()
-    pcam[3] = 0.5
-    par = np.array(GOOD, np.float32)
-    if device_form:
-        p = dict(color=FAKE, feat=FAKE * 2, state=FAKE * 3, prev_feat=FAKE * 4, prev_state=FAKE * 5)
-    else:
-        p = dict(color=N.ptr(color), feat=N.ptr(feat), state=N.ptr(state), prev_feat=N.ptr(pfeat),
-                 prev_state=N.ptr(pstate))
-    p.update(cam=N.ptr(cam), prev_cam=N.ptr(pcam), params=N.ptr(par))
-    prevs = ("prev_feat", "prev_cam", "prev_state")
-    if case.startswith("null_"):
-        p[{"null_params": "params"}.get(case, case[5:])] = None
-    elif case.startswith("only_"):
-        for k in prevs:
-            if k != case[5:]:
-                p[k] = None
-    elif case.startswith("no_"):
-        p[case[3:]] = None
-    elif case in ("w0", "w_neg", "w_huge"):
-        W = {"w0": 0, "w_neg": -3, "w_huge": 32769}[case]
-    elif case in ("h0", "h_huge"):
-        H = {"h0": 0, "h_huge": 32769}[case]
-    elif case == "device_neg":
-        device = -1
-    elif case == "aperture":
-        cam[19] = 0.1
-    elif case == "prev_aperture":
-        pcam[19] = 0.1
-    elif case == "cam_nan":
-        cam[7] = np.nan
-    elif case == "prev_cam_inf":
-        pcam[16] = np.inf
-    elif ":" in case:
-        name, how = case.split(":")
-        par[PARAM_NAMES.index(name)] = _ILLEGAL[name][how]
-    elif case.startswith("legal="):
-        _, name, value = case.split("=")
-        par[PARAM_NAMES.index(name)] = float(value)
-        device = 1 << 20
-    args = (device, p["color"], p["feat"], p["cam"], p["prev_feat"], p["prev_cam"], p["prev_state"], W, H, p["params"],
-            p["state"], None, None)
-    if device_form:
-        rc, who = L.prt_temporal_accumulate_device(*args, None), b"prt_temporal_accumulate_device:"
-    else:
-        rc, who = L.prt_temporal_accumulate(*args), b"prt_temporal_accumulate:"
-    return rc, L.prt_denoise_last_error(), who, state
 
 
 @pytest.mark.parametrize("device_form", [False, True])

@@ -10,18 +10,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from temporal_abi_cases import FAKE, GOOD, MAX_OBJECTS, call, cam as _cam
 
 NAMES = ("prt_temporal_accumulate_motion", "prt_temporal_accumulate_motion_device")
-GOOD = (0.2, 0.2, 0.9, 0.02, 0.05, 1e-2, 4.0, 0.25)
-FAKE = 4096   # a device "pointer" that is never dereferenced: the checks fail first
-MAX_OBJECTS = 1 << 20
-
-
-def _cam(aperture=0.0):
-    cam = np.zeros(24, np.float32)
-    cam[[0, 5, 10, 15]] = 1.0
-    cam[16:20] = (0.5, 0.5, 1.0, aperture)
-    return cam
 
 
 def test_header_and_exports_carry_the_entry_points():
@@ -46,7 +37,7 @@ def test_the_kernel_lives_in_the_auxiliary_unit_only():
     import json
     from pyrenderer_amd import build as B
     homes = [f for f in B.SOURCES + B.HEADERS + [B.TRACE_INST] + B.AUX_SOURCES + B.AUX_HEADERS
-             if re.search(r"\benqueue_temporal_motion\b|\btemporal_kernel<true>", open(os.path.join(B.CSRC, f)).read())]
+             if re.search(r"\bstruct Motion\b|\btemporal_kernel<true>", open(os.path.join(B.CSRC, f)).read())]
     assert homes and set(homes) <= set(B.AUX_SOURCES + B.AUX_HEADERS), homes
     src = open(os.path.join(B.CSRC, "prt_denoise.hip")).read()
     assert "template <bool kMotion>" in src and "temporal_kernel<false>" in src and "temporal_kernel<true>" in src
@@ -63,71 +54,11 @@ _CASES = [("null_ids", b"NULL"), ("null_color", b"NULL"), ("null_state", b"NULL"
           ("aperture", b"aperture"), ("tau_z", b"tau_z")]
 
 
-def _call(L, N, device_form, case):
-    W, H, device, n_objects = 4, 3, 0, 2
-    color = np.zeros((W, H, 3), np.float32)
-    feat = np.zeros((W, H, 8), np.float32)
-    state = np.ones((W, H, 8), np.float32)
-    pfeat, pstate = feat.copy(), np.zeros((W, H, 8), np.float32)
-    ids, pids = np.zeros((W, H), np.int32), np.zeros((W, H), np.int32)
-    motion = np.zeros((n_objects, 12), np.float32)
-    cam, pcam = _cam(), _cam()
-    pcam[3] = 0.5
-    par = np.array(GOOD, np.float32)
-    if device_form:
-        p = dict(color=FAKE, feat=FAKE * 2, state=FAKE * 3, prev_feat=FAKE * 4, prev_state=FAKE * 5, ids=FAKE * 6,
-                 prev_ids=FAKE * 7, motion=FAKE * 8)
-    else:
-        p = dict(color=N.ptr(color), feat=N.ptr(feat), state=N.ptr(state), prev_feat=N.ptr(pfeat),
-                 prev_state=N.ptr(pstate), ids=N.ptr(ids), prev_ids=N.ptr(pids), motion=N.ptr(motion))
-    p.update(cam=N.ptr(cam), prev_cam=N.ptr(pcam), params=N.ptr(par))
-    prevs = ("prev_feat", "prev_cam", "prev_state", "prev_ids")
-    if case.startswith("null_"):
-        p[{"null_params": "params"}.get(case, case[5:])] = None
-    elif case.startswith("only_"):
-        for k in prevs:
-            if k != case[5:]:
-                p[k] = None
-    elif case.startswith("no_"):
-        p[case[3:]] = None
-    elif case == "n_neg":
-        n_objects = -1
-    elif case == "n_huge":
-        n_objects = MAX_OBJECTS + 1
-    elif case == "w0":
-        W = 0
-    elif case == "h_huge":
-        H = 32769
-    elif case == "device_neg":
-        device = -1
-    elif case == "aperture":
-        pcam[19] = 0.1
-    elif case == "tau_z":
-        par[3] = 0.0
-    elif case == "legal":
-        device = 1 << 20
-    elif case == "legal_empty":   # an empty table needs no pointer
-        device, n_objects, p["motion"] = 1 << 20, 0, None
-    elif case == "legal_first":   # the first frame: every prev pointer NULL
-        device = 1 << 20
-        for k in prevs:
-            p[k] = None
-    elif case == "legal_max":
-        device, n_objects = 1 << 20, MAX_OBJECTS
-    args = (device, p["color"], p["feat"], p["cam"], p["prev_feat"], p["prev_cam"], p["prev_state"], p["ids"],
-            p["prev_ids"], p["motion"], n_objects, W, H, p["params"], p["state"], None, None)
-    if device_form:
-        rc, who = L.prt_temporal_accumulate_motion_device(*args, None), b"prt_temporal_accumulate_motion_device:"
-    else:
-        rc, who = L.prt_temporal_accumulate_motion(*args), b"prt_temporal_accumulate_motion:"
-    return rc, L.prt_denoise_last_error(), who, state
-
-
 @pytest.mark.parametrize("device_form", [False, True])
 @pytest.mark.parametrize("case,word", _CASES)
 def test_bad_arguments_are_rejected_before_any_device(case, word, device_form):
     from pyrenderer_amd import _native as N
-    rc, msg, who, state = _call(N.lib(), N, device_form, case)
+    rc, msg, who, state = call(N.lib(), N, device_form, case, motion=True)
     assert rc == -1, (rc, msg)   # PRT_ERR_ARG
     assert msg.startswith(who) and word in msg, msg
     assert (state == 1).all()
@@ -139,7 +70,7 @@ def test_legal_calls_end_at_the_device_ordinal(case, device_form):
     """A legal call passes every argument check and ends at the device ordinal, which is asked for last: one that
     no machine has is "no such device", or "no HIP device" without a GPU.  Nothing runs either way."""
     from pyrenderer_amd import _native as N
-    rc, msg, who, _ = _call(N.lib(), N, device_form, case)
+    rc, msg, who, _ = call(N.lib(), N, device_form, case, motion=True)
     assert rc in (-1, -2) and msg.startswith(who) and (b"no such device" in msg or b"no HIP device" in msg), (rc, msg)
 
 

@@ -1,6 +1,7 @@
-"""The NumPy restatement of the temporal accumulation with per-object motion (tests/temporal_motion_ref.py)
-against what can be known without it: temporal_ref.accumulate wherever no object moves, bit for bit, and float64
-geometry on the analytic card scene (tests/temporal_motion_cases.py).
+"""The NumPy restatement of the temporal accumulation (tests/temporal_ref.py) with ids and per-object motion
+against what can be known without them: the same function without ids wherever no pixel has a row, bit for bit
+(tests/test_temporal_ref.py anchors that form), and float64 geometry on the analytic card scene
+(tests/temporal_motion_cases.py).
 
 The restatement's figures on the clean card scene at 70 x 130: card pixels that accept history with the card's
 row 0.9762 (static) and 0.7623 (moved), with an identity row in its place 0.0000 and 0.0000; greatest error of
@@ -10,7 +11,6 @@ import pytest
 
 import temporal_cases as TC
 import temporal_motion_cases as MC
-import temporal_motion_ref as MR
 import temporal_ref as T
 from denoise_cases import MARKER, bits
 
@@ -27,7 +27,7 @@ def _same(got, want):
 
 @pytest.fixture(scope="module")
 def plain():
-    """temporal_cases.hostile and temporal_ref's result for every shape and kind, computed once."""
+    """temporal_cases.hostile and the restatement's result without ids for every shape and kind, computed once."""
     out = {}
     for W, H in SHAPES:
         for kind in TC.KINDS:
@@ -43,18 +43,19 @@ def _with_ids(prev, pids):
 @pytest.mark.parametrize("kind", TC.KINDS)
 @pytest.mark.parametrize("W,H", SHAPES)
 def test_without_a_row_it_is_the_static_restatement(plain, W, H, kind):
+    """One id on both frames that has no row, or the identity's, is no id plane at all."""
     C, F, cam, prev, want = plain[(W, H, kind)]
     none = np.full((W, H), -1, np.int32)
     # an empty table and every id -1
-    _same(MR.accumulate(C, F, cam, none, None, _with_ids(prev, none), **P), want)
+    _same(T.accumulate(C, F, cam, _with_ids(prev, none), ids=none, motion=None, **P), want)
     # every id out of range, each kind of it, against a table that holds rows nobody may read
     table = MC.motion_table()
     for v in MC.BAD_IDS:
         out = np.full((W, H), v, np.int32)
-        _same(MR.accumulate(C, F, cam, out, table, _with_ids(prev, out), **P), want)
+        _same(T.accumulate(C, F, cam, _with_ids(prev, out), ids=out, motion=table, **P), want)
     # every id 0 and one bytewise identity row
     zero = np.zeros((W, H), np.int32)
-    _same(MR.accumulate(C, F, cam, zero, MR.IDENTITY[None], _with_ids(prev, zero), **P), want)
+    _same(T.accumulate(C, F, cam, _with_ids(prev, zero), ids=zero, motion=T.IDENTITY[None], **P), want)
 
 
 @pytest.fixture(scope="module")
@@ -62,7 +63,7 @@ def cards():
     out = {}
     for kind in ("static", "moved"):
         C, F, cam, ids, motion, prev = MC.clean(kind, 70, 130)
-        out[kind] = (C, F, cam, ids, motion, prev, MR.accumulate(C, F, cam, ids, motion, prev, diagnostics=True, **P))
+        out[kind] = (C, F, cam, ids, motion, prev, T.accumulate(C, F, cam, prev, ids=ids, motion=motion, diagnostics=True, **P))
     return out
 
 
@@ -73,8 +74,8 @@ def test_the_card_keeps_its_history_only_with_its_row(cards, kind):
     assert card.sum() > 1000
     share = float(d["valid"][card].mean())
     still = motion.copy()
-    still[MC.CARD] = MR.IDENTITY
-    s2 = MR.accumulate(C, F, cam, ids, still, prev, **P)[0]
+    still[MC.CARD] = T.IDENTITY
+    s2 = T.accumulate(C, F, cam, prev, ids=ids, motion=still, **P)[0]
     share_still = float((s2[..., 3][card] > 1).mean())
     # float64 reprojection of the card's pixels through its matrix
     px, py = MC.project64(F, cam, prev[2], MC.card_motion())
@@ -117,7 +118,7 @@ def test_under_equal_cameras_ground_uncovered_by_the_card_starts_afresh(cards):
 def test_the_hostile_scene_exercises_every_branch(kind):
     W, H = 70, 130
     C, F, cam, ids, motion, prev = MC.hostile(kind, W, H)
-    state, color, var, d = MR.accumulate(C, F, cam, ids, motion, prev, diagnostics=True, **P)
+    state, color, var, d = T.accumulate(C, F, cam, prev, ids=ids, motion=motion, diagnostics=True, **P)
     for v in MC.BAD_IDS:
         assert (ids == v).sum() > 50, v
     for oid in range(MC.N_OBJECTS):
@@ -145,12 +146,12 @@ def test_the_librarys_rows_are_the_restatements():
     from pyrenderer_amd import denoise as D
     from pyrenderer_amd import scenes as S
     from pyrenderer_amd.io_utils.read_tungsten import read_file
-    assert D.IDENTITY_ROW.tobytes() == MR.IDENTITY.tobytes()
+    assert D.IDENTITY_ROW.tobytes() == T.IDENTITY.tobytes()
     scene = read_file(S.CORNELL)[0]
     later = S.moved(scene, {5: S.spin(scene.primitives[5], 6.0)})
     rows = D.motion_rows(scene, later)
     rows[6] = np.nan
     ids = np.arange(8, dtype=np.int32).reshape(2, 4)
-    _, has_row, no_pose, identity = MR.rows_of(ids, rows)
+    _, has_row, no_pose, identity = T.rows_of(ids, rows)
     assert has_row.all() and np.array_equal(no_pose.reshape(-1), np.arange(8) == 6)
     assert np.array_equal(identity.reshape(-1), ~np.isin(np.arange(8), (5, 6)))

@@ -10,7 +10,7 @@ features at 512^2, tiled to the larger sizes.  One JSON line per size.
     python tools/denoise_time.py --mode batching                    # render(spp=64) against 8 batches of 8, host wall clock, 512^2
     python tools/denoise_time.py --mode features --sizes 512 4096   # prt_features_device (1 and 8 samples); host wall clock of both compositions at 512^2
     python tools/denoise_time.py --temporal --sizes 512 4096        # prt_temporal_accumulate_device, its motion form, and beside them the filter with and without the spatial fallback
-    python tools/denoise_time.py --temporal --ab-lib abtmp/libprt_parent.so   # ... and the plain entry point of another build of the library, alternating
+    python tools/denoise_time.py --temporal --ab-lib abtmp/libprt_parent.so   # ... and both entry points of another build of the library, alternating
 """
 import argparse
 import json
@@ -39,8 +39,8 @@ def main():
                     help="time the temporal accumulation (a camera turned by 2 degrees) and the variance-guided filter "
                          "that follows it")
     ap.add_argument("--ab-lib", metavar="PATH",
-                    help="--temporal: another build of libprt.so whose prt_temporal_accumulate_device is timed in "
-                         "alternation with this build's, --ab-rounds times each")
+                    help="--temporal: another build of libprt.so whose prt_temporal_accumulate_device and its motion form "
+                         "are timed in alternation with this build's, --ab-rounds times each")
     ap.add_argument("--ab-rounds", type=int, default=3)
     a = ap.parse_args()
     import torch
@@ -276,7 +276,8 @@ def time_temporal(a, scene, cam, world):
                                          d_motion_ptr=d_rows.data_ptr(), n_objects=3)
 
         if a.ab_lib:
-            time_temporal_ab(a, size, temporal, stream, dev, d_c, d_feats, recs, d_states, d_col, d_var)
+            time_temporal_ab(a, size, (temporal, temporal_motion), stream, d_c, d_feats, recs, d_states, d_col, d_var, d_ids,
+                             d_rows)
         legs = (("temporal_motion_time", temporal_motion, n * 164),
                 ("temporal_time", temporal, n * 156),
                 ("denoise_var_time", filt, None),
@@ -306,31 +307,44 @@ def time_temporal(a, scene, cam, world):
         del d_c, d_feats, d_states, d_col, d_var, d_out, d_work, d_ids, d_rows
 
 
-def time_temporal_ab(a, size, this_build, stream, dev, d_c, d_feats, recs, d_states, d_col, d_var):
-    """The plain prt_temporal_accumulate_device of this build and of the build at a.ab_lib on the same buffers,
-    a.ab_rounds times each in alternation: whether a change to the unit left the plain kernel's time alone."""
+def time_temporal_ab(a, size, front_ends, stream, d_c, d_feats, recs, d_states, d_col, d_var, d_ids, d_rows):
+    """prt_temporal_accumulate_device and prt_temporal_accumulate_motion_device of this build and of the build at
+    a.ab_lib on the same buffers, a.ab_rounds times each in alternation: whether a change to the unit left the
+    kernels' times alone.  Three legs a round: this build through the Python front end (front_ends: the two calls
+    of time_temporal), this build straight through ctypes, the other build straight through ctypes (its front end
+    is not at hand).  The HIP events bracket the host's enqueue too, so the first leg against the third carries
+    the front end's Python as well (about 2 us); the second against the third compares the libraries alone."""
     import ctypes
     from pyrenderer_amd import _native as N
     from pyrenderer_amd import denoise as D
-    other = ctypes.CDLL(os.path.abspath(a.ab_lib))
-    fn = other.prt_temporal_accumulate_device
-    fn.restype, fn.argtypes = N.EXPORTS["prt_temporal_accumulate_device"]
+    other, other_name = ctypes.CDLL(os.path.abspath(a.ab_lib)), os.path.basename(a.ab_lib)
     par = np.array([D.TEMPORAL_ALPHA, D.TEMPORAL_ALPHA_M, D.TEMPORAL_TAU_N, D.TEMPORAL_TAU_Z, D.TEMPORAL_TAU_A, D.EPS_A,
                     1.0, D.TEMPORAL_W_MIN], np.float32)
     vp = ctypes.c_void_p
+    for moving, front_end in zip((False, True), front_ends):
+        name = "prt_temporal_accumulate" + ("_motion" if moving else "") + "_device"
+        motion = (vp(d_ids.data_ptr()), vp(d_ids.data_ptr()), vp(d_rows.data_ptr()), d_rows.shape[0]) if moving else ()
 
-    def other_build():
-        rc = fn(0, vp(d_c.data_ptr()), vp(d_feats[1].data_ptr()), N.ptr(recs[1]), vp(d_feats[0].data_ptr()), N.ptr(recs[0]),
-                vp(d_states[0].data_ptr()), size, size, N.ptr(par), vp(d_states[1].data_ptr()), vp(d_col.data_ptr()),
-                vp(d_var.data_ptr()), vp(stream.cuda_stream))
-        assert rc == 0, rc
+        def bare(lib):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = N.EXPORTS[name]
 
-    for r in range(a.ab_rounds):
-        for build, run in (("this", this_build), ("other", other_build)):
-            ms = _median_ms(run, stream, a.warmup, a.reps)
-            print(json.dumps(dict(what="temporal_time_ab", build=build, lib=os.path.basename(a.ab_lib) if build == "other" else "libprt.so",
-                                  round=r, size=size, median_ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4),
-                                  max_ms=round(ms[-1], 4), reps=a.reps)), flush=True)
+            def run():
+                rc = fn(0, vp(d_c.data_ptr()), vp(d_feats[1].data_ptr()), N.ptr(recs[1]), vp(d_feats[0].data_ptr()),
+                        N.ptr(recs[0]), vp(d_states[0].data_ptr()), *motion, size, size, N.ptr(par),
+                        vp(d_states[1].data_ptr()), vp(d_col.data_ptr()), vp(d_var.data_ptr()), vp(stream.cuda_stream))
+                assert rc == 0, rc
+            return run
+
+        legs = (("this", "libprt.so", "front end", front_end), ("this", "libprt.so", "ctypes", bare(N.lib())),
+                ("other", other_name, "ctypes", bare(other)))
+        for r in range(a.ab_rounds):
+            for build, lib_name, how, run in legs:
+                ms = _median_ms(run, stream, a.warmup, a.reps)
+                print(json.dumps(dict(what="temporal_motion_time_ab" if moving else "temporal_time_ab", build=build,
+                                      lib=lib_name, call=how, round=r, size=size,
+                                      median_ms=round(ms[len(ms) // 2], 4), min_ms=round(ms[0], 4),
+                                      max_ms=round(ms[-1], 4), reps=a.reps)), flush=True)
 
 
 def time_features(a, cam, world):

@@ -56,10 +56,10 @@ def soup_scene(flat, n=SOUP_N):
 
 
 def soup_rays(flat, n, seed):
-    """n interior rays of the soup scene's own box, as test_gpu_hits._rays draws them."""
-    from test_gpu_hits import _rays
+    """n interior rays of the soup scene's own box, as kernel_parity.rays draws them."""
+    from kernel_parity import rays
     v = flat.tri_v.reshape(-1, 3)
-    return _rays(n, seed, lo=v.min(0).astype(np.float64), hi=v.max(0).astype(np.float64))
+    return rays(n, seed, lo=v.min(0).astype(np.float64), hi=v.max(0).astype(np.float64))
 
 
 CHAIN_MAX_LEAF = 1   # PRT_MAX_LEAF for chain(): one triangle per leaf

@@ -3,17 +3,14 @@ tests/test_global_invariance.py (CPU: every builder setting does to these scenes
 is for) and tests/test_gpu_global_invariance.py (GPU: schedule thresholds in steady state, and every tree
 shape, against the oracle's brute-force backend).
 
-The scenes are the project's own (test_gpu_parity._soup_scene, hard_scenes, hard_spheres); nothing here
+The scenes are the project's own (kernel_parity.soup_scene, hard_scenes, hard_spheres); nothing here
 knows about the code under test except the names of the environment knobs, which prt_scene_create and
 the BVH builder read once per scene.  Pure NumPy."""
-import os
-from contextlib import contextmanager
-
 import numpy as np
 
 import hard_scenes as HS
 import hard_spheres as SP
-from test_gpu_hits import _rays
+from kernel_parity import env_knobs, rays, soup_scene
 
 # ------------------------------------------------------------------ knobs
 SCHEDULE_KNOBS = ("PRT_RESUME_MIN", "PRT_LEAF_BREAK", "PRT_LEAF_EXIT")
@@ -25,23 +22,16 @@ OTHER_KNOBS = ("PRT_SBVH_ALPHA", "PRT_SAH_CT", "PRT_LEAF_MIN", "PRT_DP_CT", "PRT
 ALL_KNOBS = SCHEDULE_KNOBS + TREE_KNOBS + OTHER_KNOBS
 
 
-@contextmanager
-def knobs(setting):
-    """The environment with exactly the knobs of `setting` (name -> value) set and every other knob of
-    ALL_KNOBS unset; restored on exit.  Scenes and trees read the environment when they are created."""
+def every_knob(setting):
+    """`setting` (name -> value) with every other knob of ALL_KNOBS as None, which env_knobs unsets."""
     assert set(setting) <= set(ALL_KNOBS), setting
-    old = {k: os.environ.get(k) for k in ALL_KNOBS}
-    try:
-        for k in ALL_KNOBS:
-            os.environ.pop(k, None)
-        for k, v in setting.items():
-            os.environ[k] = str(v)
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
+    return {k: setting.get(k) for k in ALL_KNOBS}
+
+
+def knobs(setting):
+    """The environment with exactly the knobs of `setting` set and every other knob of ALL_KNOBS unset;
+    restored on exit.  Scenes and trees read the environment when they are created."""
+    return env_knobs(**every_knob(setting))
 
 
 def _sched(rm=None, lb=None, le=None):
@@ -129,11 +119,10 @@ def stack(cornell_flat, copies=FAT_COPIES, seed=0):
 def scene(cornell, name):
     """The FlatScene of one name, built once per process and not modified by its users."""
     if name not in _scenes:
-        from test_gpu_parity import _soup_scene
         if name == "soup-3000":
-            flat = _soup_scene(cornell, 3000, 9)
+            flat = soup_scene(cornell, 3000, 9)
         elif name == "soup-20000":
-            flat = _soup_scene(cornell, N_LARGE, 9)
+            flat = soup_scene(cornell, N_LARGE, 9)
         elif name == "slivers-1e-5":
             flat = HS.case(cornell, name)[0]
         elif name == "soup-zoo":
@@ -167,7 +156,7 @@ def ray_sets(cornell, name):
             inner = tuple(np.concatenate([sets["interior"][k][:N_RAYS // 2], sets["inside"][k][:N_RAYS // 2]])
                           for k in range(2))
         else:
-            inner = _rays(N_RAYS, 23)
+            inner = rays(N_RAYS, 23)
         _ray_sets[name] = {"interior": inner, "far100": HS.far_rays(flat, N_RAYS, FAR_SEED, FAR_EXTENTS)[:2]}
     return _ray_sets[name]
 

@@ -12,7 +12,8 @@ import numpy as np
 
 from oracle import oracle as O
 from pyrenderer_amd.flatten import FlatScene
-from test_gpu_hits import T_MAX, T_MIN, _axis_rays, _rays
+import kernel_parity as KP
+from kernel_parity import T_MAX, T_MIN, random_bounds  # noqa: F401  (random_bounds: re-exported)
 
 F = np.float32
 _GREY = [0.5, 0.5, 0.5, 0, 0, 0, 1, 0]         # rho.rgb, emit, sided, type, ior, roughness
@@ -65,7 +66,7 @@ def reindexed(flat, perm):
 
 def _with_extras_first(flat, tv):
     """`tv` (m, 9) in front of the scene's own triangles, as one more primitive of material 0
-    (the layout of test_gpu_parity._soup_scene: the light's triangle ids move)."""
+    (the layout of kernel_parity.soup_scene: the light's triangle ids move)."""
     tv = np.asarray(tv, F).reshape(-1, 9)
     m = tv.shape[0]
     lo, hi = _tri_bounds(tv)
@@ -250,7 +251,7 @@ def slivers(cornell_flat, width, n_needles=N_NEEDLES, n_each=8):
     o = rng.uniform((-0.95, 0.05, -0.95), (0.95, 1.95, 0.95), (n_aim, 3)).astype(F)
     d = target - o
     d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(F)
-    ro, rd = _rays(8000, 31)
+    ro, rd = KP.rays(8000, 31)
     return flat, (np.concatenate([o, ro]), np.concatenate([d, rd]))
 
 
@@ -274,12 +275,12 @@ def placed_points(o, scale, translate):
 
 
 def far_rays(flat, n, seed, extents=FAR_EXTENTS[0]):
-    """n rays with unit directions as test_gpu_hits._rays draws them, from origins
+    """n rays with unit directions as kernel_parity.rays draws them, from origins
     centre - d * D + a jitter of a quarter extent, D = min(extents * extent, 0.4 * T_MAX): the hits
     stay below the reference's t_max of 99999.9.  Returns (o, d, D)."""
     centre, extent = scene_box(flat)
     D = min(extents * extent, 0.4 * float(T_MAX))
-    _, d = _rays(n, seed)
+    _, d = KP.rays(n, seed)
     rng = np.random.default_rng(seed + 500)
     o = centre - d.astype(np.float64) * D + rng.uniform(-0.25, 0.25, (n, 3)) * extent
     return o.astype(F), d, D
@@ -288,21 +289,13 @@ def far_rays(flat, n, seed, extents=FAR_EXTENTS[0]):
 def placement_rays(flat, scale, translate, n=6000, seed=0):
     """The ray sets of one placed scene: {name: (o, d)} with interior rays, the axis-aligned set
     (direction components of exactly +-0) and far rays at both distances."""
-    o, d = _rays(n, 40 + seed)
-    ao, ad = _axis_rays(250, 41 + seed)
+    o, d = KP.rays(n, 40 + seed)
+    ao, ad = KP.axis_rays(250, 41 + seed)
     sets = {"interior": (placed_points(o, scale, translate), d), "axis": (placed_points(ao, scale, translate), ad)}
     for e in FAR_EXTENTS:
         fo, fd, _ = far_rays(flat, n, 42 + seed, e)
         sets["far%d" % e] = (fo, fd)
     return sets
-
-
-def random_bounds(osc, o, d, seed):
-    """Shadow-style t_max per ray: around the ray's own closest hit (0.5 .. 1.5 of it), so about half
-    the queries are occluded wherever the scene sits; rays without a hit get T_MAX."""
-    hit, t, _, _ = osc.closest(o, d, T_MIN, T_MAX)
-    k = np.random.default_rng(seed).uniform(0.5, 1.5, o.shape[0])
-    return np.where(hit != 0, t.astype(np.float64) * k, float(T_MAX)).astype(F)
 
 
 # ------------------------------------------------------------------ ties
@@ -332,28 +325,27 @@ def case(cornell, name):
       slivers-W        the 4096 aimed + 8000 random rays
       slivers8-W       the same with 8 needles and 2 of each degenerate kind (51 triangles)
       cornell          the plain box: 20 000 interior rays, 20 000 far rays at each distance
-      soup-pK, box-pK  placement K of _soup_scene(cornell, 300, 9) / of the plain box: interior,
+      soup-pK, box-pK  placement K of soup_scene(cornell, 300, 9) / of the plain box: interior,
                        axis-aligned and far rays at each distance"""
     if name in _cache:
         return _cache[name]
-    from test_gpu_parity import _soup_scene
     kind, _, arg = name.partition("-")
     box = cornell[2]
     if kind == "lattice":
         flat, rays = lattice(AXES.index(arg))
         sets = {"dir%d" % k: (o, d) for k, (o, d, _, _) in enumerate(rays)}
     elif kind == "layers":
-        flat, sets = layers(box, 6, int(arg)), {"interior": _rays(20000, 1)}
+        flat, sets = layers(box, 6, int(arg)), {"interior": KP.rays(20000, 1)}
     elif kind in ("slivers", "slivers8"):
         flat, rays = slivers(box, float(arg)) if kind == "slivers" else slivers(box, float(arg), 8, 2)
         sets = {"aimed+random": rays}
     elif kind == "cornell":
-        flat, sets = box, {"interior": _rays(20000, 1)}
+        flat, sets = box, {"interior": KP.rays(20000, 1)}
         for e in FAR_EXTENTS:
             sets["far%d" % e] = far_rays(box, 20000, 7, e)[:2]
     else:
         scale, translate = PLACEMENTS[int(arg[1:])]
-        flat = placed(_soup_scene(cornell, 300, 9) if kind == "soup" else box, scale, translate)
+        flat = placed(KP.soup_scene(cornell, 300, 9) if kind == "soup" else box, scale, translate)
         sets = placement_rays(flat, scale, translate)
     _cache[name] = (flat, sets)
     return _cache[name]

@@ -14,7 +14,7 @@ import numpy as np
 
 from hard_scenes import F
 from pyrenderer_amd.flatten import FlatScene
-from test_gpu_hits import _axis_rays, _rays
+from kernel_parity import axis_rays, rays, soup_scene
 
 # rho.rgb, emit, sided, type, ior, roughness (hard_scenes._GREY); albedos inside [2^-40, 2^40], so the
 # kernels keep their cheap shading guards (TraceParams::shade_fast) on all of these scenes; the other side,
@@ -80,13 +80,13 @@ def with_spheres(flat, spheres):
 
 def inside_rays(flat, n, seed):
     """n rays whose origins are drawn uniformly inside the scene's spheres, taking the spheres in turn
-    (ray i starts in sphere i % n_sph), with unit directions as _rays draws them: the first hit is the
+    (ray i starts in sphere i % n_sph), with unit directions as rays draws them: the first hit is the
     far root of the sphere itself unless something lies inside it.  Returns (o, d)."""
     rng = np.random.default_rng(seed)
     sph = flat.sph.astype(np.float64)[np.arange(n) % flat.sph.shape[0]]
     v = rng.normal(size=(n, 3))
     v *= (rng.uniform(0, 1, n) ** (1 / 3) / np.linalg.norm(v, axis=1))[:, None]
-    return (sph[:, :3] + 0.999 * sph[:, 3:] * v).astype(F), _rays(n, seed + 1)[1]
+    return (sph[:, :3] + 0.999 * sph[:, 3:] * v).astype(F), rays(n, seed + 1)[1]
 
 
 def many_spheres(seed=5):
@@ -151,15 +151,14 @@ def case(cornell, name):
       zoo            the box + ZOO: 4096 interior rays, 2048 inside-origin rays, the axis-aligned set
       dyadic         the box + DYADIC: the "above" and "centre" grids of dyadic_rays (3468 rays each)
       specks-R-D     the box + one Lambert sphere of radius R: 4096 rays from D away
-      soup-zoo       _soup_scene(cornell, 300, 9) + ZOO (not LDS-resident): interior and inside-origin
+      soup-zoo       soup_scene(cornell, 300, 9) + ZOO (not LDS-resident): interior and inside-origin
       many           the box + 67 random spheres: 4096 interior rays"""
     if name in _cache:
         return _cache[name]
-    from test_gpu_parity import _soup_scene
     box = cornell[2]
     if name == "zoo":
         flat = with_spheres(box, ZOO)
-        sets = {"interior": _rays(4096, 61), "inside": inside_rays(flat, 2048, 62), "axis": _axis_rays(100, 63)}
+        sets = {"interior": rays(4096, 61), "inside": inside_rays(flat, 2048, 62), "axis": axis_rays(100, 63)}
     elif name == "dyadic":
         flat = with_spheres(box, DYADIC)
         sets = {k: v[:2] for k, v in dyadic_rays().items()}
@@ -168,10 +167,10 @@ def case(cornell, name):
         flat = with_spheres(box, [(SPECK_CENTRE, r, "lambert")])
         sets = {"aimed": speck_rays(r, dist)}
     elif name == "soup-zoo":
-        flat = with_spheres(_soup_scene(cornell, 300, 9), ZOO)
-        sets = {"interior": _rays(4096, 64), "inside": inside_rays(flat, 2048, 65)}
+        flat = with_spheres(soup_scene(cornell, 300, 9), ZOO)
+        sets = {"interior": rays(4096, 64), "inside": inside_rays(flat, 2048, 65)}
     elif name == "many":
-        flat, sets = with_spheres(box, many_spheres()), {"interior": _rays(4096, 66)}
+        flat, sets = with_spheres(box, many_spheres()), {"interior": rays(4096, 66)}
     else:
         raise KeyError(name)
     _cache[name] = (flat, sets)

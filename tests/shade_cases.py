@@ -22,10 +22,10 @@ replaced.  Pure NumPy; nothing here knows about the code under test.
 import numpy as np
 
 from pyrenderer_amd.flatten import FlatScene
-from test_gpu_hits import _rays
+import kernel_parity as KP
 
 F = np.float32
-N_RAYS, DEPTH, SEED = 4096, 8, 17          # the first 4096 of _rays(4096, 3), traced at depth 8 with seed 17
+N_RAYS, DEPTH, SEED = 4096, 8, 17          # the first 4096 of rays(4096, 3), traced at depth 8 with seed 17
 
 # material rows of the Cornell box: 0 floor, 1 ceiling, 2 back wall, 3 the green wall, 4 the red wall, 5 and 6
 # the two boxes, 7 the light (test_shade_cases.py checks the ones named here against the geometry)
@@ -110,7 +110,7 @@ _cache = {}
 
 def rays():
     if "rays" not in _cache:
-        o, d = _rays(N_RAYS, 3)
+        o, d = KP.rays(N_RAYS, 3)
         _cache["rays"] = (o[:N_RAYS], d[:N_RAYS])
     return _cache["rays"]
 
@@ -120,14 +120,13 @@ def base(cornell, name):
     if name != SOUP:
         return cornell[2]
     if "soup" not in _cache:
-        from test_gpu_parity import _soup_scene
-        _cache["soup"] = _soup_scene(cornell, 300, 9)
+        _cache["soup"] = KP.soup_scene(cornell, 300, 9)
     return _cache["soup"]
 
 
 def case(cornell, name):
     """The FlatScene of one catalogue entry; `cornell` is the session fixture.  Built once per process and
-    not modified by its users.  soup-black is _soup_scene(cornell, 300, 9) with the `black` and `n3` edits:
+    not modified by its users.  soup-black is soup_scene(cornell, 300, 9) with the `black` and `n3` edits:
     the soup's triangles come first and share the floor's row, so the Cornell rows keep their numbers."""
     if name not in _cache:
         if name == SOUP:

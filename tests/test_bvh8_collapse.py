@@ -163,7 +163,7 @@ def test_stack_need_covers_the_worst_case_traversal(trees, name, width):
 @pytest.mark.parametrize("name", SCENES)
 def test_bvh4_is_unchanged_by_the_width_option(trees, name, cornell):
     from pyrenderer_amd import _native as N
-    from test_bvh_pinned import _fnv1a64
+    from kernel_parity import fnv1a64
     b = trees(name)[0]
     fresh = N.Bvh(np.ascontiguousarray(_tri_v(name, cornell), np.float32).reshape(-1, 9), max_leaf=4)
     first = fresh.collapse(4)            # before this handle was ever asked for the eight-wide tree
@@ -172,7 +172,7 @@ def test_bvh4_is_unchanged_by_the_width_option(trees, name, cornell):
         assert np.array_equal(got[0].view(np.uint32), first[0].view(np.uint32)) and got[1:] == first[1:]
     if name == "cornell":
         pinned = json.load(open(os.path.join(GOLDEN, "bvh_trees.json")))["cornell"]
-        assert _fnv1a64(first[0]) == pinned["nodes4"]
+        assert fnv1a64(first[0]) == pinned["nodes4"]
         assert (len(first[0]), first[1], first[2]) == (pinned["bvh4_nodes"], pinned["bvh4_depth"], pinned["stack_need"])
 
 

@@ -14,6 +14,7 @@ boxes nest: each node's box (in its parent) contains both of its child boxes.  N
 import numpy as np
 import pytest
 
+from kernel_parity import env_knobs
 from pyrenderer_amd import scenes
 from pyrenderer_amd._native import Bvh
 from pyrenderer_amd.flatten import flatten_scene
@@ -24,15 +25,11 @@ KNOBS = ("PRT_SBVH", "PRT_TREELET", "PRT_SAH_BINS", "PRT_ESC_BETA", "PRT_SBVH_AL
 
 @pytest.fixture(scope="module")
 def c4_tree():
-    import os
-    saved = {k: os.environ.pop(k) for k in KNOBS if k in os.environ}
-    try:
+    with env_knobs(**dict.fromkeys(KNOBS)):
         scene, _ = scenes.instanced_cubes()
         tv = flatten_scene(scene).tri_v.reshape(-1, 9)
         b = Bvh(tv)
         nodes, tris, order = b.export()
-    finally:
-        os.environ.update(saved)
     return tv, b, nodes, tris, order
 
 

@@ -109,13 +109,6 @@ def test_tree_is_the_pinned_one(built, golden, case, tmp_path):
 
 # ---------------------------------------------------------------- the library that ships builds the same trees
 
-def _fnv1a64(a):
-    h = 0xcbf29ce484222325
-    for b in np.ascontiguousarray(a).tobytes():
-        h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
-    return f"{h:016x}"
-
-
 def _numpy_soup():
     rng = np.random.default_rng(29)
     n = 3000
@@ -127,6 +120,7 @@ def _numpy_soup():
 @pytest.mark.parametrize("name", ["cornell", "numpy3000"])
 def test_library_exports_the_drivers_tree(built, name, tmp_path, monkeypatch):
     """libprt.so (hipcc -O3) against the pinned g++ build: the same file, the same BVH2 bytes and info."""
+    from kernel_parity import fnv1a64
     from pyrenderer_amd import _native as N
     for k in KNOBS:
         monkeypatch.delenv(k, raising=False)
@@ -136,7 +130,7 @@ def test_library_exports_the_drivers_tree(built, name, tmp_path, monkeypatch):
     rep = _run(built, (str(path), 4), {}, tmp_path)
     b = N.Bvh(tv, max_leaf=4)
     nodes, tris, order = b.export()
-    assert (_fnv1a64(nodes), _fnv1a64(tris), _fnv1a64(order)) == (rep["nodes2"], rep["tris"], rep["order"])
+    assert (fnv1a64(nodes), fnv1a64(tris), fnv1a64(order)) == (rep["nodes2"], rep["tris"], rep["order"])
     assert (b.n_nodes, b.depth, b.n_leaves, b.n_tri) == (rep["bvh2_nodes"], rep["bvh2_depth"], rep["leaves"],
                                                          rep["references"])
     assert f"{np.array([b.pad], np.float32).view(np.uint32)[0]:08x}" == rep["pad_bits"]

@@ -14,7 +14,7 @@ import pytest
 import adaptive_ref as A
 import moments_ref as M
 from denoise_cases import bits
-from test_gpu_moments import BOUND, N_SAMPLES, PAR, _frames
+from moments_cases import BOUND, N_SAMPLES, PAR, frames
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +42,7 @@ def restated():
     after each of the K batches.  Planes start as the sentinel outside the listed tiles and empty inside."""
     out = {}
     for W, H, tw, th in SHAPES:
-        S, F = _frames(W, H, K, 700 + 10 * W + tw)
+        S, F = frames(W, H, K, 700 + 10 * W + tw)
         n = A.n_tiles(tw, th, W, H)
         per_list = {}
         for name, ids in _lists(n, np.random.default_rng(W + tw)).items():

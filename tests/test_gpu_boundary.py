@@ -11,6 +11,8 @@ send/recv self-loop), so the communicator, the group and the root's scatter all 
 import numpy as np
 import pytest
 
+from kernel_parity import packed_camera, scene_json
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,7 +28,7 @@ def _full(ds, cam, W, H, spp, depth, seed):
                                        (99, 69, 1, 1),       # last pixel
                                        (8, 16, 64, 8)])      # tile-aligned strip
 def test_window_is_crop_of_frame_and_oracle(gpu_scene, oracle_scene, cornell, x0, y0, w, h):
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W, H, spp, depth, seed = 100, 70, 3, 8, 11
     full = _full(gpu_scene, cam, W, H, spp, depth, seed)
     win, _ = gpu_scene.render_window(cam, W, H, x0, y0, w, h, spp, depth, seed)
@@ -38,7 +40,7 @@ def test_window_is_crop_of_frame_and_oracle(gpu_scene, oracle_scene, cornell, x0
 
 def test_window_stats_and_errors(gpu_scene, cornell):
     from pyrenderer_amd._native import PRT_FLAG_STATS, PrtError
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     _, st = gpu_scene.render_window(cam, 64, 64, 0, 0, 64, 64, 2, 8, 3, PRT_FLAG_STATS)
     assert st[2] >= 64 * 64 * 2 and st[0] > 0
     z, _ = gpu_scene.render_window(cam, 64, 64, 4, 4, 9, 9, 0, 8)
@@ -53,7 +55,7 @@ def test_window_stats_and_errors(gpu_scene, cornell):
                                                 (512, 512, 64, 2, 8)])  # config 2 frame
 def test_render_multi_one_device_through_rccl(gpu_scene, oracle_scene, cornell, W, H, tile, spp, depth):
     from pyrenderer_amd.device_scene import render_multi
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     m = render_multi([gpu_scene], cam, W, H, tile, spp, depth, seed=5)
     np.testing.assert_array_equal(m, _full(gpu_scene, cam, W, H, spp, depth, 5))
     if W * H <= 128 * 128:
@@ -64,7 +66,7 @@ def test_render_multi_rejects_shared_device(gpu_scene, cornell):
     from pyrenderer_amd._native import PrtError
     from pyrenderer_amd.device_scene import DeviceScene, render_multi
     other = DeviceScene(cornell[2], 0)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     with pytest.raises(PrtError, match="distinct devices"):
         render_multi([gpu_scene, other], cam, 64, 64, 64, 1, 1)
     other.close()
@@ -134,8 +136,7 @@ def test_cli_resume_state_path_and_mismatches(tmp_path, cornell):
     moved.iview[0, 3] += 0.25
     with pytest.raises(ValueError, match="camera"):
         Accumulator.load(state, scene, moved)
-    from test_multi_light import _scene_json
     from pyrenderer_amd.io_utils.read_tungsten import read_file
-    other, ocam = read_file(_scene_json(tmp_path))
+    other, ocam = read_file(scene_json(tmp_path))
     with pytest.raises(ValueError, match="scene"):
         Accumulator.load(state, other, camera)

@@ -25,6 +25,7 @@ import os
 import numpy as np
 import pytest
 
+from kernel_parity import T_MAX, T_MIN, axis_rays, hit_ids, hits_wrong, packed_camera, specular_scene
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -126,23 +127,21 @@ def test_config4_hits_match_oracle(cubes, quantized):
     """prt_closest_hits (World.hit_all, intersection_taichi.py:238-291) on the 1 M-triangle
     scene: 20 k random rays + axis-parallel rays (+-0 components) against the oracle's BVH
     backend, and a brute-force subset (all 1 M triangles per ray) that pins the tree."""
-    from test_gpu_hits import T_MAX, T_MIN, _axis_rays
     ds, osc, _, _ = cubes
 
     def check(o, d, tmax=T_MAX, backend=O.BACKEND_BVH):
-        gid, gt = ds.closest_hits(o, d, T_MIN, tmax, quantized=quantized)
         hit, t, tri, _ = osc.closest(o, d, T_MIN, tmax, backend=backend)
-        oid = np.where(hit != 0, tri, -1).astype(np.int64)
-        bad = np.nonzero((gid != oid) | ((gid >= 0) & (gt != t)))[0]
-        assert bad.size == 0, (bad.size, [(o[i], d[i], gid[i], oid[i], gt[i], t[i]) for i in bad[:3]])
-        return (gid >= 0).mean()
+        want = (hit_ids(hit, tri), t)
+        n, first, ohit = hits_wrong(ds, osc, o, d, T_MIN, tmax, quantized, any_hit=False, want=want)
+        assert n == 0, (n, first)
+        return ohit.mean()
 
     o, d = _cube_rays(20000, 11)
     assert check(o, d) > 0.9
     # hits on instanced cubes (not the walls) dominate
     gid, _ = ds.closest_hits(o, d, T_MIN, T_MAX, quantized=quantized)
     assert (gid[gid >= 0] < 1_000_008).mean() > 0.5
-    o, d = _axis_rays(600, 12, lo=(-0.99, 0.01, -0.99), hi=(0.99, 1.97, 0.99))
+    o, d = axis_rays(600, 12, lo=(-0.99, 0.01, -0.99), hi=(0.99, 1.97, 0.99))
     check(o, d)
     # VERDICT r05 item 3: the frame test's oracle walks the library-built BVH, so the tree is pinned here
     # by brute force over all 1 M triangles (OpenMP in the oracle)
@@ -151,10 +150,10 @@ def test_config4_hits_match_oracle(cubes, quantized):
     # bounded (shadow-style) any-hit queries
     o, d = _cube_rays(20000, 14)
     tmax = np.random.default_rng(15).uniform(0.001, 0.3, o.shape[0]).astype(np.float32)
-    gid, _ = ds.closest_hits(o, d, T_MIN, tmax, any_hit=True, quantized=quantized)
-    hit, _, _, _ = osc.closest(o, d, T_MIN, tmax, backend=O.BACKEND_BVH)
-    assert np.array_equal(gid >= 0, hit != 0)
-    assert 0.05 < (hit != 0).mean() < 0.95
+    hit = osc.closest(o, d, T_MIN, tmax, backend=O.BACKEND_BVH)[0] != 0
+    n, first, _ = hits_wrong(ds, osc, o, d, T_MIN, tmax, quantized, any_hit=True, want=hit)
+    assert n == 0, (n, first)
+    assert 0.05 < hit.mean() < 0.95
 
 
 # ----------------------------------------------------------------------------- config 3
@@ -164,9 +163,8 @@ def test_config3_full_frame_matches_oracle(monkeypatch):
     two trace launches of 128 spp (PRT_CHUNK_BYTES = 4 GiB, read at scene creation); 96 random
     8x8 tiles (1.6 M samples) bit-identical to the oracle."""
     monkeypatch.setenv("PRT_CHUNK_BYTES", str(4 << 30))
-    from test_gpu_parity import _specular_scene
     from pyrenderer_amd.device_scene import DeviceScene
-    _, camera, flat = _specular_scene(0.0)
+    _, camera, flat = specular_scene(0.0)
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
     cam = camera.convert_to_taichi_camera().packed()
@@ -182,7 +180,7 @@ def test_config3_full_frame_matches_oracle(monkeypatch):
 
 @pytest.fixture(scope="module")
 def config5_frame(gpu_scene, cornell):
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     return _full_frame(gpu_scene, cam, 4096, 4096, 256, 8, seed=0)
 
 
@@ -194,7 +192,7 @@ def test_config5_frame_matches_oracle(gpu_scene, oracle_scene, cornell, config5_
     assert np.isfinite(frame).all() and (frame >= 0).all()
     m = frame.mean(axis=(0, 1)) / 256
     assert np.all((m > 0.05) & (m < 2.0)), m
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     _sampled_tiles_equal(frame, oracle_scene, cam, 4096, 4096, 256, 8, 0, 64, rng_seed=6)
     # every 64x64 tile got samples (no chunk or tile left out)
     assert (frame.reshape(64, 64, 64, 64, 3).sum(axis=(1, 3, 4)) > 0).all()
@@ -205,6 +203,6 @@ def test_config5_render_multi_gather(gpu_scene, cornell, config5_frame):
     sums go through an RCCL send/recv self-loop and the device scatter; the frame equals
     the tile render bit for bit."""
     from pyrenderer_amd.device_scene import render_multi
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     m = render_multi([gpu_scene], cam, 4096, 4096, 64, 256, 8, seed=0)
     assert np.array_equal(m, config5_frame)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from denoise_cases import bits, gap_soup, load_scene
+from kernel_parity import packed_camera
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +31,7 @@ def _host(ds, cam, W, H, samples, seed, first_sample=0):
 
 @pytest.fixture(scope="module")
 def packed(cornell):
-    return cornell[1].convert_to_taichi_camera().packed()
+    return packed_camera(cornell)
 
 
 # ------------------------------------------------------------ bit equality ----

@@ -44,8 +44,8 @@ import numpy as np
 import pytest
 
 import global_cases as G
-import hard_scenes as HS
-from hard_scenes import T_MAX, T_MIN
+from kernel_parity import (T_MAX, T_MIN, OracleRefs, all_tiles, check_trace, hits_wrong, is_mis, nee_mode, open_scenes,
+                           packed_camera, random_bounds, render_twice, variant_flags)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -56,41 +56,18 @@ GLOBAL_VARIANTS = (3, 5)       # reference estimator, MIS estimator
 LDS_VARIANTS = (1, 2, 6, 7, 8)
 DEPTH = 4
 TILE = 64
+REFS = OracleRefs()
 
 
 @pytest.fixture(scope="module")
 def scenes(cornell):
     """make(name, setting) -> DeviceScene of G.scene(name) created under G.knobs(setting) (cached)."""
-    from pyrenderer_amd.device_scene import DeviceScene
-    made = {}
-
-    def make(name, setting):
-        key = (name, tuple(sorted(setting.items())))
-        if key not in made:
-            with G.knobs(setting):
-                made[key] = DeviceScene(G.scene(cornell, name), 0)
-        return made[key]
-    yield make
-    for ds in made.values():
-        ds.close()
-
-
-def _flags(v):
-    from pyrenderer_amd import _native as N
-    return (v << 8) | (N.PRT_FLAG_MIS_NEE if v in N.VAR_MIS else 0)
-
-
-def _cam(cornell):
-    return cornell[1].convert_to_taichi_camera().packed()
+    with open_scenes() as make:
+        yield lambda name, setting: make(name, G.scene(cornell, name), **G.every_knob(setting))
 
 
 def _tiles(W, H):
-    return np.arange(((W + TILE - 1) // TILE) * ((H + TILE - 1) // TILE), dtype=np.int32)
-
-
-def _mis(v):
-    from pyrenderer_amd import _native as N
-    return v in N.VAR_MIS
+    return all_tiles(W, H, TILE)
 
 
 # ================================================================== Part A: steady-state schedule
@@ -103,43 +80,36 @@ def _spp(ds, n_slots, at_least=1):
     return max(at_least, -(-FACTOR * _resident_lanes(ds) // n_slots))
 
 
-_frame_refs = {}
-
-
 def _frame_ref(cornell, name, mis, W, H, spp, depth, seed):
     """(slot sums, (extension, shadow) query counts) of the whole frame by the oracle's BVH2 backend on the
     library's default tree, computed once; that backend first has to equal BACKEND_BRUTE on sixteen 16 x 16
     tiles which include the frame's four corners (the oracle keys its draws by the global pixel, so the
     tile size does not matter)."""
-    key = (name, mis, W, H, spp, depth, seed)
-    if key not in _frame_refs:
+    def compute():
         from pyrenderer_amd._native import Bvh
         flat = G.scene(cornell, name)
         osc = O.OracleScene.from_flat(flat)
         with G.knobs({}):
             nodes, _, order = Bvh(flat.tri_v).export()
         osc.set_bvh(nodes, order)
-        cam = _cam(cornell)
-        O.set_nee_mode(mis)
-        try:
-            ref, cnt = osc.render_tiles(cam, W, H, TILE, TILE, _tiles(W, H), spp, depth, seed=seed,
-                                        backend=O.BACKEND_BVH, nthreads=NTHREADS, counters=True)
-            tx, ty = (W + 15) // 16, (H + 15) // 16
-            sub = np.unique(np.r_[0, tx - 1, tx * (ty - 1), tx * ty - 1,
-                                  np.random.default_rng(seed).choice(tx * ty, 12, replace=False)]).astype(np.int32)
-            assert sub.size >= 8
-            kw = dict(seed=seed, nthreads=NTHREADS)
+        cam = packed_camera(cornell)
+        tx, ty = (W + 15) // 16, (H + 15) // 16
+        sub = np.unique(np.r_[0, tx - 1, tx * (ty - 1), tx * ty - 1,
+                              np.random.default_rng(seed).choice(tx * ty, 12, replace=False)]).astype(np.int32)
+        assert sub.size >= 8
+        kw = dict(seed=seed, nthreads=NTHREADS)
+        with nee_mode(mis):
+            ref, cnt = osc.render_tiles(cam, W, H, TILE, TILE, _tiles(W, H), spp, depth, backend=O.BACKEND_BVH,
+                                        counters=True, **kw)
             brute = osc.render_tiles(cam, W, H, 16, 16, sub, spp, depth, backend=O.BACKEND_BRUTE, **kw)
             walked = osc.render_tiles(cam, W, H, 16, 16, sub, spp, depth, backend=O.BACKEND_BVH, **kw)
-        finally:
-            O.set_nee_mode(False)
         assert np.array_equal(walked, brute), (name, mis)
         # ... and those tiles of the whole frame are the same pixels
         full = O.unpack_tiles(ref, W, H, TILE, TILE, _tiles(W, H))
         assert np.array_equal(O.unpack_tiles(brute, W, H, 16, 16, sub)[_mask(W, H, sub)], full[_mask(W, H, sub)])
         assert np.isfinite(ref).all() and ref.mean() > 0
-        _frame_refs[key] = (ref, (int(cnt[2]), int(cnt[3])))
-    return _frame_refs[key]
+        return ref, (int(cnt[2]), int(cnt[3]))
+    return REFS.get(("frame", name, mis, W, H, spp, depth, seed), compute)
 
 
 def _mask(W, H, sub):
@@ -158,21 +128,16 @@ def _render(ds, cam, W, H, spp, depth, seed, v):
     """One launch through forced variant `v` in the production and in the STATS build: dict(img, queries,
     iters, trips).  Asserts what every launch of this file has to satisfy: the launch takes the global
     kernel asked for and stays un-exhausted (FACTOR), no watchdog trip, no non-finite sample, and the
-    STATS image equals the production one."""
+    STATS image equals the production one (render_twice asserts the last three)."""
     from pyrenderer_amd import _native as N
     ids = _tiles(W, H)
     n_items = len(ids) * TILE * TILE * spp
-    info = ds.kernel_info(n_items, _flags(v))
+    info = ds.kernel_info(n_items, variant_flags(v))
     assert info["variant"] == v and not info["lds_scene"] and info["quantized"] and info["bvh_arity"] == 4, info
     assert n_items >= FACTOR * _resident_lanes(ds), (n_items, _resident_lanes(ds))
-    img, _ = ds.render_tiles(cam, W, H, TILE, TILE, ids, spp, depth, seed, _flags(v))
-    ds.check_faults()
-    simg, st = ds.render_tiles(cam, W, H, TILE, TILE, ids, spp, depth, seed, _flags(v) | N.PRT_FLAG_STATS)
-    ds.check_faults()
-    w = ds.diag_words(N.PRT_DIAG_WORDS)
-    assert int(w[N.PRT_DIAG_NONFINITE]) == 0
-    assert np.array_equal(simg, img)
-    return dict(img=img, queries=(int(st[2]), int(st[3])), iters=int(w[N.PRT_DIAG_WAVE_ITERS]),
+    r = render_twice(ds, cam, W, H, TILE, ids, spp, depth, seed, variant_flags(v))
+    w = r["words"]
+    return dict(img=r["img"], queries=r["queries"], iters=int(w[N.PRT_DIAG_WAVE_ITERS]),
                 trips=tuple(int(w[getattr(N, k)]) for k in TRIP_WORDS), items_per_lane=n_items / _resident_lanes(ds))
 
 
@@ -187,7 +152,7 @@ def _run(scenes, cornell, name, v, sched, W, H, depth, seed):
     spp = _spp(base_ds, len(_tiles(W, H)) * TILE * TILE, at_least=8)
     key = (name, v, sched, W, H, depth, seed)
     if key not in _runs:
-        _runs[key] = _render(scenes(name, G.SCHEDULES[sched]), _cam(cornell), W, H, spp, depth, seed, v)
+        _runs[key] = _render(scenes(name, G.SCHEDULES[sched]), packed_camera(cornell), W, H, spp, depth, seed, v)
         r = _runs[key]
         print(f"{name} variant {v} {sched} {W}x{H}x{spp} depth {depth}: {r['items_per_lane']:.2f} items per resident "
               f"lane, {r['queries'][0]} ext / {r['queries'][1]} shadow queries, wave iterations {r['iters']}, "
@@ -197,7 +162,7 @@ def _run(scenes, cornell, name, v, sched, W, H, depth, seed):
 
 def _check_schedule(scenes, cornell, name, v, sched, W, H, depth, seed):
     base, spp = _run(scenes, cornell, name, v, G.BASELINE, W, H, depth, seed)
-    ref, counted = _frame_ref(cornell, name, _mis(v), W, H, spp, depth, seed)
+    ref, counted = _frame_ref(cornell, name, is_mis(v), W, H, spp, depth, seed)
     differ = int((base["img"] != ref).any(axis=-1).sum())
     assert differ == 0, (name, v, "baseline against the oracle", differ)
     assert base["queries"] == counted, (base["queries"], counted)
@@ -250,14 +215,14 @@ def test_corner_multi_frame_launch(scenes, cornell, v):
     """Three progressive frames (frame_stride = spp) through one persistent launch at (64, 64, 64): each
     frame equals the baseline scene's accumulate call for its samples, frame 0 the oracle's frame."""
     import torch
-    cam = _cam(cornell)
+    cam = packed_camera(cornell)
     W = H = 256
     n, seed, name = 3, 7, "soup-3000"
     ids = _tiles(W, H)
     n_slots = len(ids) * TILE * TILE
     base_ds = scenes(name, G.SCHEDULES[G.BASELINE])
     spp = _spp(base_ds, n * n_slots)
-    info = base_ds.kernel_info(n * n_slots * spp, _flags(v))
+    info = base_ds.kernel_info(n * n_slots * spp, variant_flags(v))
     assert info["variant"] == v and not info["lds_scene"], info
     assert n * n_slots * spp >= FACTOR * _resident_lanes(base_ds)
     frames = {}
@@ -265,79 +230,56 @@ def test_corner_multi_frame_launch(scenes, cornell, v):
         ds = scenes(name, G.SCHEDULES[sched])
         out = torch.full((n, n_slots * 3), float("nan"), dtype=torch.float32, device="cuda:0")
         ds.render_frames_device(cam, W, H, TILE, TILE, ids, spp, DEPTH, n, out.data_ptr(), None, seed=seed,
-                                frame_stride=spp, flags=_flags(v))
+                                frame_stride=spp, flags=variant_flags(v))
         ds.check_faults()
         frames[sched] = out.cpu().numpy().reshape(n, n_slots, 3)
-    ref, _ = _frame_ref(cornell, name, _mis(v), W, H, spp, DEPTH, seed)
+    ref, _ = _frame_ref(cornell, name, is_mis(v), W, H, spp, DEPTH, seed)
     assert np.array_equal(frames[G.BASELINE][0], ref)
     for f in range(n):
         acc = np.zeros((n_slots, 3), np.float32)
         base_ds.render_tiles_accumulate(cam, W, H, TILE, TILE, ids, f * spp, spp, DEPTH, acc, seed=seed,
-                                        flags=_flags(v))
+                                        flags=variant_flags(v))
         for sched in frames:
             assert np.array_equal(frames[sched][f], acc), (sched, f)
 
 
 # ================================================================== Part B: tree shapes
 TREE_CASES = [(name, tree) for name in G.SCENES for tree in G.TREES if (name, tree) not in G.DROPPED]
-_hit_refs, _trace_refs, _oscs = {}, {}, {}
 
 
 def _osc(cornell, name):
-    if name not in _oscs:
-        _oscs[name] = O.OracleScene.from_flat(G.scene(cornell, name))
-    return _oscs[name]
+    return REFS.get(("scene", name), lambda: O.OracleScene.from_flat(G.scene(cornell, name)))
 
 
 def _oracle_hits(cornell, name, key):
     """Brute-force (id, t), shadow-style bounds and the bounded any-hit booleans of one ray set, once."""
-    if (name, key) not in _hit_refs:
+    def compute():
         osc = _osc(cornell, name)
         o, d = G.ray_sets(cornell, name)[key]
-        hit, t, tri, _ = osc.closest(o, d, T_MIN, T_MAX)
-        tmax = HS.random_bounds(osc, o, d, 3)
-        _hit_refs[name, key] = (np.where(hit != 0, tri, -1).astype(np.int64), t, tmax,
-                                osc.closest(o, d, T_MIN, tmax)[0] != 0)
-    return _hit_refs[name, key]
-
-
-def _oracle_trace(cornell, name, key, mis):
-    if (name, key, mis) not in _trace_refs:
-        o, d = G.ray_sets(cornell, name)[key]
-        O.set_nee_mode(mis)
-        try:
-            ref = _osc(cornell, name).trace_rays(o, d, DEPTH, seed=17, nthreads=NTHREADS)
-        finally:
-            O.set_nee_mode(False)
-        assert np.isfinite(ref).all() and ref.mean() > 0
-        _trace_refs[name, key, mis] = ref
-    return _trace_refs[name, key, mis]
+        tmax = random_bounds(osc, o, d, 3)
+        return REFS.closest((name, key), osc, o, d), tmax, osc.closest(o, d, T_MIN, tmax)[0] != 0
+    return REFS.get(("hits", name, key), compute)
 
 
 def _check_hits(ds, cornell, name, quantized):
     wrong = []
     for key, (o, d) in G.ray_sets(cornell, name).items():
-        oid, ot, tmax, ohit = _oracle_hits(cornell, name, key)
-        gid, gt = ds.closest_hits(o, d, T_MIN, T_MAX, quantized=quantized)
-        bad = np.nonzero((gid != oid) | ((gid >= 0) & (gt != ot)))[0]
-        if bad.size:
-            wrong.append((key, "closest", bad.size, [(o[i], d[i], gid[i], oid[i], gt[i], ot[i]) for i in bad[:3]]))
-        aid, _ = ds.closest_hits(o, d, T_MIN, tmax, any_hit=True, quantized=quantized)
-        bad = np.nonzero((aid >= 0) != ohit)[0]
-        if bad.size:
-            wrong.append((key, "any-hit", bad.size, [(o[i], d[i], tmax[i], aid[i], ot[i]) for i in bad[:3]]))
+        closest, tmax, ohit = _oracle_hits(cornell, name, key)
+        n, first, _ = hits_wrong(ds, None, o, d, T_MIN, T_MAX, quantized, any_hit=False, want=closest)
+        if n:
+            wrong.append((key, "closest", n, first))
+        n, first, _ = hits_wrong(ds, None, o, d, T_MIN, tmax, quantized, any_hit=True, want=ohit)
+        if n:
+            wrong.append((key, "any-hit", n, first))
         assert 0.2 < ohit.mean() < 0.8, (key, ohit.mean())               # the bounds do separate the rays
     ds.check_faults()
     assert not wrong, (name, [w[:3] for w in wrong], wrong)
 
 
-def _check_trace(ds, cornell, name, v, flags=None):
+def _check_trace(ds, cornell, name, v):
     for key, (o, d) in G.ray_sets(cornell, name).items():
-        ref = _oracle_trace(cornell, name, key, _mis(v))
-        L = ds.trace_rays(o, d, DEPTH, seed=17, flags=_flags(v) if flags is None else flags)
-        ds.check_faults()
-        bad = np.nonzero(np.any(L.view(np.uint32) != ref.view(np.uint32), axis=1))[0]
-        assert bad.size == 0, (name, key, v, bad.size, [(i, o[i], d[i], L[i], ref[i]) for i in bad[:3]])
+        ref = REFS.trace((name, key), _osc(cornell, name), o, d, DEPTH, 17, is_mis(v), nthreads=NTHREADS)
+        check_trace(ds, ref, o, d, DEPTH, 17, v, label="%s %s" % (name, key))
 
 
 def _tree_scene(scenes, cornell, name, setting):
@@ -363,7 +305,7 @@ def test_hits_over_every_tree(scenes, cornell, name, tree, quantized):
 def test_paths_over_every_tree(scenes, cornell, name, tree, v):
     """prt_trace_rays, 4096 + 4096 caller rays at depth 4 through the global-scene kernels."""
     ds = _tree_scene(scenes, cornell, name, G.tree_setting(name, tree))
-    info = ds.kernel_info(G.N_RAYS, _flags(v))
+    info = ds.kernel_info(G.N_RAYS, variant_flags(v))
     assert info["variant"] == v and not info["lds_scene"] and info["bvh_arity"] == 4, info
     _check_trace(ds, cornell, name, v)
 
@@ -373,10 +315,10 @@ def test_large_scene_spills_its_stack(scenes, cornell):
     at the default PRT_SPILL_LDS, and a render's deepest entry does go past it (STATS, word 13)."""
     from pyrenderer_amd import _native as N
     ds = scenes("soup-20000", {})
-    info = ds.kernel_info(256 * 256 * 8, _flags(N.VAR_GLOBAL))
+    info = ds.kernel_info(256 * 256 * 8, variant_flags(N.VAR_GLOBAL))
     assert info["variant"] == N.VAR_GLOBAL and info["stack"] == 16, info
-    ds.render_tiles(_cam(cornell), 256, 256, TILE, TILE, _tiles(256, 256), 8, 8, 1,
-                    _flags(N.VAR_GLOBAL) | N.PRT_FLAG_STATS)
+    ds.render_tiles(packed_camera(cornell), 256, 256, TILE, TILE, _tiles(256, 256), 8, 8, 1,
+                    variant_flags(N.VAR_GLOBAL) | N.PRT_FLAG_STATS)
     ds.check_faults()
     deepest = int(ds.diag_words(N.PRT_DIAG_WORDS)[N.PRT_DIAG_MAX_STACK])
     need = G.tree_report(G.scene(cornell, "soup-20000"), {})["stack_need"]
@@ -396,7 +338,7 @@ def test_fat_leaves_through_the_global_kernels(scenes, cornell, v):
     """Leaves of 6, 7 and 8 coincident triangles (ties on every hit of a stack: the lowest id wins, and the
     copies differ in material) through variants 3 and 5, forced: the scene is LDS-resident."""
     ds = _tree_scene(scenes, cornell, G.FAT, G.FAT_SETTING)
-    info = ds.kernel_info(G.N_RAYS, _flags(v))
+    info = ds.kernel_info(G.N_RAYS, variant_flags(v))
     assert info["variant"] == v and info["bvh_arity"] == 4, info
     _check_trace(ds, cornell, G.FAT, v)
 
@@ -407,6 +349,6 @@ def test_fat_leaves_through_the_lds_kernels(scenes, cornell, width, v):
     """The same leaves through the OCT triangle loop of the phase-aligned kernels (1, 2, 6) and the pooled
     kernels (7, 8: their shadow traversal too), over the BVH4 and the BVH8 in LDS."""
     ds = _tree_scene(scenes, cornell, G.FAT, dict(G.FAT_SETTING, PRT_LDS_WIDTH=width))
-    info = ds.kernel_info(G.N_RAYS, _flags(v))
+    info = ds.kernel_info(G.N_RAYS, variant_flags(v))
     assert info["variant"] == v and info["bvh_arity"] == width and info["lds_scene"], (width, v, info)
     _check_trace(ds, cornell, G.FAT, v)

@@ -16,43 +16,20 @@ import numpy as np
 import pytest
 
 import hard_scenes as HS
-from hard_scenes import T_MAX, T_MIN
+from kernel_parity import (ALL_VARIANTS, T_MAX, T_MIN, OracleRefs, check_trace, hits_wrong, is_mis, packed_camera,
+                           random_bounds, world_cache)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 UP, DOWN = np.float32(np.inf), np.float32(0)
+REFS = OracleRefs()
 
 
 @pytest.fixture(scope="module")
 def world(cornell):
     """name -> (DeviceScene, OracleScene, ray sets); each scene is created once for the module."""
-    from pyrenderer_amd.device_scene import DeviceScene
-    made = {}
-
-    def get(name):
-        if name not in made:
-            flat, sets = HS.case(cornell, name)
-            made[name] = (DeviceScene(flat, 0), O.OracleScene.from_flat(flat), sets)
-        return made[name]
-    yield get
-    for ds, _, _ in made.values():
-        ds.close()
-
-
-_brute = {}
-
-
-def _oracle_closest(name, key, osc, o, d):
-    """Brute-force (id, t) and the shadow-style bounds of one ray set, computed once."""
-    if (name, key) not in _brute:
-        hit, t, tri, _ = osc.closest(o, d, T_MIN, T_MAX)
-        _brute[name, key] = (np.where(hit != 0, tri, -1).astype(np.int64), t, HS.random_bounds(osc, o, d, 3))
-    return _brute[name, key]
-
-
-def _differing(gid, gt, oid, ot):
-    return np.nonzero((gid != oid) | ((gid >= 0) & (gt != ot)))[0]
+    yield from world_cache(lambda name: HS.case(cornell, name))
 
 
 @pytest.mark.parametrize("quantized", [False, True])
@@ -63,16 +40,14 @@ def test_hits_match_brute_force(world, name, quantized):
     ds, osc, sets = world(name)
     wrong = []
     for key, (o, d) in sets.items():
-        oid, ot, tmax = _oracle_closest(name, key, osc, o, d)
-        gid, gt = ds.closest_hits(o, d, T_MIN, T_MAX, quantized=quantized)
-        bad = _differing(gid, gt, oid, ot)
-        if bad.size:
-            wrong.append((key, "closest", bad.size, [(o[i], d[i], gid[i], oid[i], gt[i], ot[i]) for i in bad[:3]]))
-        aid, _ = ds.closest_hits(o, d, T_MIN, tmax, any_hit=True, quantized=quantized)
-        ohit = osc.closest(o, d, T_MIN, tmax)[0] != 0
-        bad = np.nonzero((aid >= 0) != ohit)[0]
-        if bad.size:
-            wrong.append((key, "any-hit", bad.size, [(o[i], d[i], tmax[i], aid[i], ot[i]) for i in bad[:3]]))
+        want = REFS.closest((name, key), osc, o, d)
+        n, first, _ = hits_wrong(ds, osc, o, d, T_MIN, T_MAX, quantized, any_hit=False, want=want)
+        if n:
+            wrong.append((key, "closest", n, first))
+        tmax = REFS.get(("bounds", name, key), lambda: random_bounds(osc, o, d, 3))
+        n, first, ohit = hits_wrong(ds, osc, o, d, T_MIN, tmax, quantized, any_hit=True)
+        if n:
+            wrong.append((key, "any-hit", n, first))
         assert 0.2 < ohit.mean() < 0.8                           # the bounds do separate the rays
     assert not wrong, (name, [w[:3] for w in wrong], wrong)
 
@@ -108,17 +83,6 @@ N_TRACE, DEPTH = 4096, 4
 TRACE_CASES = {"layers": ("layers-0", "interior"), "slivers": ("slivers8-1e-5", "aimed+random"),
                "far100": ("cornell", "far100"), "far1000": ("cornell", "far1000"),
                "translated": ("box-p2", "interior"), "scaled-down": ("box-p0", "interior")}
-_traced = {}
-
-
-def _oracle_trace(case, osc, o, d, mis):
-    if (case, mis) not in _traced:
-        O.set_nee_mode(mis)
-        try:
-            _traced[case, mis] = osc.trace_rays(o, d, DEPTH, seed=17)
-        finally:
-            O.set_nee_mode(False)
-    return _traced[case, mis]
 
 
 def _variant_ids():
@@ -127,20 +91,11 @@ def _variant_ids():
 
 
 def _check_trace(ds, osc, case, o, d, v, lds_scene=True):
-    from pyrenderer_amd import _native as N
-    mis = v in N.VAR_MIS
-    flags = (v << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
-    assert ds.kernel_info()["lds_scene"] == lds_scene, ds.kernel_info()
-    assert ds.kernel_info(n_items=N_TRACE, flags=flags)["variant"] == v
-    print(f"{case}: variant {v} ran at bvh_arity {ds.kernel_info(n_items=N_TRACE, flags=flags)['bvh_arity']}")
-    ref = _oracle_trace(case, osc, o, d, mis)
-    assert np.isfinite(ref).all() and ref.mean() > 0
-    L = ds.trace_rays(o, d, DEPTH, seed=17, flags=flags)
-    bad = np.nonzero(np.any(L.view(np.uint32) != ref.view(np.uint32), axis=1))[0]
-    assert bad.size == 0, (case, v, bad.size, [(o[i], d[i], L[i], ref[i]) for i in bad[:3]])
+    ref = REFS.trace(case, osc, o, d, DEPTH, 17, is_mis(v))
+    check_trace(ds, ref, o, d, DEPTH, 17, v, label=case, lds_scene=lds_scene)
 
 
-@pytest.mark.parametrize("v", [1, 2, 3, 6, 7, 8, 4, 5])
+@pytest.mark.parametrize("v", ALL_VARIANTS)
 @pytest.mark.parametrize("case", list(TRACE_CASES))
 def test_every_kernel_variant_traces_the_oracles_paths(world, case, v):
     """4096 caller rays, depth 4, through each forced trace-kernel variant (the reference
@@ -190,7 +145,7 @@ def test_stack_depth_within_the_collapse_bound(world, cornell, name):
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import interleaved_tiles
     ds, _, _ = world(name)
-    packed = cornell[1].convert_to_taichi_camera().packed()
+    packed = packed_camera(cornell)
     W = H = 64
     tiles = interleaved_tiles(W, H, 64)
     for var in N.VAR_POOL + (N.VAR_LDS,):

@@ -18,51 +18,29 @@ import numpy as np
 import pytest
 
 import hard_spheres as S
-from hard_scenes import T_MAX, T_MIN, random_bounds
-from oracle import oracle as O
+from kernel_parity import (ALL_VARIANTS, T_MAX, T_MIN, OracleRefs, check_trace, hits_wrong, is_mis, packed_camera,
+                           random_bounds, variant_flags, world_cache, wrong_rows)
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 UP, DOWN, NAN = F(np.inf), F(0), F(np.nan)
 SPECK0 = S.speck_name(*S.SPECKS[0])
+REFS = OracleRefs()
 
 
 @pytest.fixture(scope="module")
 def world(cornell):
     """name -> (DeviceScene, OracleScene, ray sets); each scene is created once for the module."""
-    from pyrenderer_amd.device_scene import DeviceScene
-    made = {}
-
-    def get(name):
-        if name not in made:
-            flat, sets = S.case(cornell, name)
-            made[name] = (DeviceScene(flat, 0), O.OracleScene.from_flat(flat), sets)
-        return made[name]
-    yield get
-    for ds, _, _ in made.values():
-        ds.close()
-
-
-def _ids(hit, tri):
-    return np.where(hit != 0, tri, -1).astype(np.int64)
+    yield from world_cache(lambda name: S.case(cornell, name))
 
 
 def _closest_wrong(ds, osc, o, d, tmin, tmax, quantized):
-    """The rays on which prt_closest_hits' (id, t) differs from brute force, with both answers."""
-    hit, ot, tri, _ = osc.closest(o, d, tmin, tmax)
-    oid = _ids(hit, tri)
-    gid, gt = ds.closest_hits(o, d, tmin, tmax, quantized=quantized)
-    bad = np.nonzero((gid != oid) | ((gid >= 0) & (gt != ot)))[0]
-    return bad.size, [(i, o[i], d[i], gid[i], oid[i], gt[i], ot[i]) for i in bad[:3]]
+    return hits_wrong(ds, osc, o, d, tmin, tmax, quantized, any_hit=False)[:2]
 
 
 def _any_wrong(ds, osc, o, d, tmin, tmax, quantized):
-    ohit = osc.closest(o, d, tmin, tmax)[0] != 0
-    aid, _ = ds.closest_hits(o, d, tmin, tmax, any_hit=True, quantized=quantized)
-    bad = np.nonzero((aid >= 0) != ohit)[0]
-    tm = np.broadcast_to(tmax, ohit.shape)
-    return bad.size, [(i, o[i], d[i], tm[i], aid[i], ohit[i]) for i in bad[:3]], ohit
+    return hits_wrong(ds, osc, o, d, tmin, tmax, quantized, any_hit=True)
 
 
 @pytest.mark.parametrize("quantized", [False, True])
@@ -154,7 +132,7 @@ def test_hit_all_records_match_the_oracle(world, name, quantized):
     for key, (o, d) in sets.items():
         want = osc.hit_all(o, d, T_MIN, T_MAX, seed=11)
         got = ds.hit_all(o, d, T_MIN, T_MAX, seed=11, quantized=quantized)
-        bad = np.nonzero(np.any(got.view(np.uint32) != want.view(np.uint32), axis=1))[0]
+        bad = wrong_rows(got, want)
         assert bad.size == 0, (name, key, bad.size, [(i, o[i], d[i], got[i], want[i]) for i in bad[:3]])
         assert (want[:, 0] != 0).mean() > 0.8
     if name == "dyadic":
@@ -170,32 +148,11 @@ N_TRACE, DEPTH = 4096, 8
 TRACE_CASES = {"zoo": ("zoo", "interior"), "zoo-inside": ("zoo", "inside"), "dyadic-above": ("dyadic", "above"),
                "dyadic-centre": ("dyadic", "centre"), "many": ("many", "interior")}
 TRACE_CASES.update({S.speck_name(r, dist): (S.speck_name(r, dist), "aimed") for r, dist in S.SPECKS})
-ALL_VARIANTS = [1, 2, 3, 6, 7, 8, 4, 5]
-_traced = {}
-
-
-def _oracle_trace(case, osc, o, d, mis):
-    if (case, mis) not in _traced:
-        O.set_nee_mode(mis)
-        try:
-            _traced[case, mis] = osc.trace_rays(o, d, DEPTH, seed=17)
-        finally:
-            O.set_nee_mode(False)
-    return _traced[case, mis]
 
 
 def _check_trace(ds, osc, case, o, d, v, lds_scene=True):
-    from pyrenderer_amd import _native as N
-    mis = v in N.VAR_MIS
-    flags = (v << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
-    assert ds.kernel_info()["lds_scene"] == lds_scene, ds.kernel_info()
-    assert ds.kernel_info(n_items=N_TRACE, flags=flags)["variant"] == v
-    print(f"{case}: variant {v} ran at bvh_arity {ds.kernel_info(n_items=N_TRACE, flags=flags)['bvh_arity']}")
-    ref = _oracle_trace(case, osc, o, d, mis)
-    assert np.isfinite(ref).all() and ref.mean() > 0
-    L = ds.trace_rays(o, d, DEPTH, seed=17, flags=flags)
-    bad = np.nonzero(np.any(L.view(np.uint32) != ref.view(np.uint32), axis=1))[0]
-    assert bad.size == 0, (case, v, bad.size, [(i, o[i], d[i], L[i], ref[i]) for i in bad[:3]])
+    ref = REFS.trace(case, osc, o, d, DEPTH, 17, is_mis(v))
+    check_trace(ds, ref, o, d, DEPTH, 17, v, label=case, lds_scene=lds_scene)
 
 
 @pytest.mark.parametrize("v", ALL_VARIANTS)
@@ -216,8 +173,7 @@ def test_an_lds_resident_sphere_scene_takes_all_eight_variants(world):
     from pyrenderer_amd import _native as N
     ds, _, _ = world("zoo")
     assert sorted(ALL_VARIANTS) == sorted(list(N.VAR_REFERENCE) + list(N.VAR_MIS)) == list(range(1, N.VAR_LAST + 1))
-    ran = {ds.kernel_info(n_items=N_TRACE, flags=(v << 8) | (N.PRT_FLAG_MIS_NEE if v in N.VAR_MIS else 0))["variant"]
-           for v in ALL_VARIANTS}
+    ran = {ds.kernel_info(n_items=N_TRACE, flags=variant_flags(v))["variant"] for v in ALL_VARIANTS}
     assert ran == set(range(1, 9)) and ds.kernel_info()["lds_scene"]
 
 
@@ -239,18 +195,18 @@ def test_zoo_render_and_counters_match_the_oracle(world, cornell, kernel):
     bit; the extension and shadow query counts equal the oracle's and no sample is non-finite."""
     from pyrenderer_amd import _native as N
     ds, osc, _ = world("zoo")
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(1, dtype=np.int32)
     flags = N.PRT_FLAG_STATS | ((N.VAR_LDS << 8) if kernel == "lds" else 0)
     want_var = N.VAR_LDS if kernel == "lds" else N.VAR_LDS_POOL
     assert ds.kernel_info(n_items=32 * 32 * 4, flags=flags)["variant"] == want_var
-    ref, oc = osc.render_tiles(cam, 32, 32, 32, 32, ids, 4, 8, seed=9, counters=True)
+    ref, oc = REFS.render_tiles("zoo", osc, cam, 32, 32, 32, ids, 4, 8, 9)
     assert np.isfinite(ref).all() and ref.mean() > 0
     for fl in (flags, flags & ~N.PRT_FLAG_STATS):
         got, st = ds.render_tiles(cam, 32, 32, 32, 32, ids, 4, 8, 9, fl)
         np.testing.assert_array_equal(got, ref)
         if fl & N.PRT_FLAG_STATS:
-            assert st[2] == oc[2] and st[3] == oc[3] and st[0] > 0 and st[1] > 0, (st, oc)
+            assert (st[2], st[3]) == oc and st[0] > 0 and st[1] > 0, (st, oc)
             assert ds.diag_stats()[N.PRT_DIAG_NONFINITE] == 0
 
 
@@ -261,7 +217,7 @@ def test_zoo_features_on_sphere_pixels(world, cornell):
     from pyrenderer_amd.denoise import features_packed_host
     ds, osc, _ = world("zoo")
     flat = ds.flat
-    pc = cornell[1].convert_to_taichi_camera().packed()
+    pc = packed_camera(cornell)
     W = H = 48
     o, d, _ = ds.camera_rays(pc, W, H, 16, 16, np.arange(9, dtype=np.int32), 0, 2, 7)
     hit, _, tri, _ = osc.closest(o, d, T_MIN, T_MAX)

@@ -3,12 +3,12 @@ scene creation forces the width).  The closest (t, id) and every 
 depend on the visiting order, so a width-8 render equals the width-4 render of the same build and the C
 oracle bit for bit, asks the same number of extension and shadow queries, trips no watchdog and produces
 no non-finite sample."""
-import os
-
 import numpy as np
 import pytest
 
 import bvh8_scenes as S8
+from kernel_parity import all_tiles, packed_camera, render_twice, specular_scene
+from kernel_parity import scenes_by_width as scenes  # noqa: F401  (the module-scoped fixture)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -16,62 +16,13 @@ pytestmark = pytest.mark.gpu
 DEFAULT_WIDTH = 8   # of a scene that can take either (prt_plan.cpp lds_width)
 
 
-@pytest.fixture(scope="module")
-def scenes():
-    """make(name, flat, width, **env) -> DeviceScene created with PRT_LDS_WIDTH = width (None: unset) and
-    the other knobs given (cached)."""
-    from pyrenderer_amd.device_scene import DeviceScene
-    made = {}
-
-    def make(name, flat, width, **env):
-        key = (name, width, tuple(sorted(env.items())))
-        if key not in made:
-            knobs = dict(env, PRT_LDS_WIDTH=width)
-            old = {k: os.environ.get(k) for k in knobs}
-            for k, v in knobs.items():
-                os.environ.pop(k, None)
-                if v is not None:
-                    os.environ[k] = str(v)
-            try:
-                made[key] = DeviceScene(flat, 0)
-            finally:
-                for k, v in old.items():
-                    os.environ.pop(k, None)
-                    if v is not None:
-                        os.environ[k] = v
-        return made[key]
-    yield make
-    for ds in made.values():
-        ds.close()
-
-
-def _tiles(W, H, tile):
-    return np.arange(((W + tile - 1) // tile) * ((H + tile - 1) // tile), dtype=np.int32)
-
-
-def _render(ds, cam, W, H, tile, ids, spp, depth, seed, variant, width):
-    """(production image, (ext, shadow) query counts, suspensions) of one scene; the STATS image must equal
-    the production one."""
-    from pyrenderer_amd import _native as N
-    info = ds.kernel_info(len(ids) * tile * tile * spp, variant << 8)
-    assert info["bvh_arity"] == width and info["lds_scene"] and (not variant or info["variant"] == variant), info
-    img, _ = ds.render_tiles(cam, W, H, tile, tile, ids, spp, depth, seed, variant << 8)
-    ds.check_faults()
-    simg, st = ds.render_tiles(cam, W, H, tile, tile, ids, spp, depth, seed, N.PRT_FLAG_STATS | (variant << 8))
-    ds.check_faults()
-    w = ds.diag_words(N.PRT_DIAG_WORDS)
-    assert int(w[N.PRT_DIAG_NONFINITE]) == 0
-    assert 1 <= int(w[N.PRT_DIAG_MAX_STACK]) <= info["stack"], (int(w[N.PRT_DIAG_MAX_STACK]), info)
-    assert np.array_equal(simg, img)
-    return img, (int(st[2]), int(st[3])), int(w[N.PRT_DIAG_SUSPENDED])
-
-
 def _check(make, name, flat, cam, W, H, spp, depth, seed, variant=0, ids=None, tile=64):
-    ids = _tiles(W, H, tile) if ids is None else np.asarray(ids, np.int32)
+    ids = all_tiles(W, H, tile) if ids is None else np.asarray(ids, np.int32)
     ref, cnt = O.OracleScene.from_flat(flat).render_tiles(cam, W, H, tile, tile, ids, spp, depth, seed=seed,
                                                           counters=True)
-    img4, q4, _ = _render(make(name, flat, 4), cam, W, H, tile, ids, spp, depth, seed, variant, 4)
-    img8, q8, _ = _render(make(name, flat, 8), cam, W, H, tile, ids, spp, depth, seed, variant, 8)
+    r4, r8 = (render_twice(make(name, flat, w), cam, W, H, tile, ids, spp, depth, seed, variant << 8, width=w)
+              for w in (4, 8))
+    (img4, q4), (img8, q8) = (r4["img"], r4["queries"]), (r8["img"], r8["queries"])
     print(f"{name} {W}x{H}x{spp} depth {depth} variant {variant}: {q8[0]} ext / {q8[1]} shadow queries, "
           f"{int((img8 != img4).any(axis=-1).sum())} pixels differ from width 4, "
           f"{int((img8 != ref).any(axis=-1).sum())} from the oracle")
@@ -79,18 +30,13 @@ def _check(make, name, flat, cam, W, H, spp, depth, seed, variant=0, ids=None, t
     assert q8 == q4 == (int(cnt[2]), int(cnt[3]))
 
 
-def _cam(cornell):
-    return cornell[1].convert_to_taichi_camera().packed()
-
-
 def test_cornell(scenes, cornell):
-    _check(scenes, "cornell", cornell[2], _cam(cornell), 64, 64, 4, 8, 3)
+    _check(scenes, "cornell", cornell[2], packed_camera(cornell), 64, 64, 4, 8, 3)
 
 
 def test_specular_scene(scenes):
     """The pooled kernel's full build: a sphere, metal and dielectric paths."""
-    from test_gpu_parity import _specular_scene
-    _, cam, flat = _specular_scene(0.35)
+    _, cam, flat = specular_scene(0.35)
     assert flat.sph.shape[0] == 1
     _check(scenes, "specular", flat, cam.convert_to_taichi_camera().packed(), 32, 32, 4, 8, 4)
 
@@ -99,27 +45,27 @@ def test_specular_scene(scenes):
 def test_small_trees(scenes, cornell, name):
     """A root whose children are all leaves (five of its eight slots empty), and a root with one inner child."""
     flat = S8.five_triangles(cornell[2]) if name == "five" else S8.nine_leaves(cornell[2])
-    _check(scenes, name, flat, _cam(cornell), 32, 32, 2, 8, 5)
+    _check(scenes, name, flat, packed_camera(cornell), 32, 32, 2, 8, 5)
 
 
 def test_ragged_tile_set(scenes, cornell):
     """A frame that is no multiple of the tile, and three of its four tiles."""
-    _check(scenes, "cornell", cornell[2], _cam(cornell), 100, 72, 4, 8, 6, ids=[0, 1, 3])
+    _check(scenes, "cornell", cornell[2], packed_camera(cornell), 100, 72, 4, 8, 6, ids=[0, 1, 3])
 
 
 def test_phase_aligned_kernel(scenes, cornell):
     """trace_kernel's LDS instantiation over the eight-wide tree (variant forced)."""
     from pyrenderer_amd import _native as N
-    _check(scenes, "cornell", cornell[2], _cam(cornell), 64, 64, 4, 8, 3, variant=N.VAR_LDS)
+    _check(scenes, "cornell", cornell[2], packed_camera(cornell), 64, 64, 4, 8, 3, variant=N.VAR_LDS)
 
 
 def test_multi_frame_launch(scenes, cornell, oracle_scene):
     """Three progressive frames through one persistent launch."""
     import torch
-    cam = _cam(cornell)
+    cam = packed_camera(cornell)
     W = H = 64
     tile, spp, depth, n, seed = 64, 4, 8, 3, 7
-    ids = _tiles(W, H, tile)
+    ids = all_tiles(W, H, tile)
     n_slots = len(ids) * tile * tile
     frames = {}
     for width in (4, 8):
@@ -137,17 +83,20 @@ def test_multi_frame_launch(scenes, cornell, oracle_scene):
 def test_suspended_tails(scenes, cornell):
     """PRT_POOL_RESUME_MIN at width 8: the parked state (node, leaf, stack pointer, best hit) is the same
     words for either tree.  1 M items, two per resident lane, so that the thresholds apply."""
-    cam = _cam(cornell)
+    from pyrenderer_amd import _native as N
+    cam = packed_camera(cornell)
     W = H = 256
-    ids = _tiles(W, H, 64)
-    got = {thr: _render(scenes("cornell", cornell[2], 8, PRT_POOL_RESUME_MIN=thr), cam, W, H, 64, ids, 16, 8, 2, 0, 8)
-           for thr in (0, 1, 64)}
-    base4 = _render(scenes("cornell", cornell[2], 4, PRT_POOL_RESUME_MIN=0), cam, W, H, 64, ids, 16, 8, 2, 0, 4)
-    print({thr: g[2] for thr, g in got.items()})
-    assert got[0][2] == 0 and got[64][2] > 0
+    ids = all_tiles(W, H, 64)
+    got = {thr: render_twice(scenes("cornell", cornell[2], 8, PRT_POOL_RESUME_MIN=thr), cam, W, H, 64, ids, 16, 8, 2, 0,
+                             width=8) for thr in (0, 1, 64)}
+    base4 = render_twice(scenes("cornell", cornell[2], 4, PRT_POOL_RESUME_MIN=0), cam, W, H, 64, ids, 16, 8, 2, 0,
+                         width=4)
+    suspended = {thr: int(g["words"][N.PRT_DIAG_SUSPENDED]) for thr, g in got.items()}
+    print(suspended)
+    assert suspended[0] == 0 and suspended[64] > 0
     for thr in (1, 64):
-        assert np.array_equal(got[thr][0], got[0][0]) and got[thr][1] == got[0][1], thr
-    assert np.array_equal(got[0][0], base4[0]) and got[0][1] == base4[1]
+        assert np.array_equal(got[thr]["img"], got[0]["img"]) and got[thr]["queries"] == got[0]["queries"], thr
+    assert np.array_equal(got[0]["img"], base4["img"]) and got[0]["queries"] == base4["queries"]
 
 
 def test_info_call_reports_the_width(scenes, cornell):

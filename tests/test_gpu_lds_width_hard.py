@@ -17,13 +17,15 @@ import pytest
 import bvh8_scenes as S8
 import hard_scenes as HS
 import hard_spheres as SP
+from kernel_parity import OracleRefs, all_tiles, check_trace, packed_camera, render_twice
+from kernel_parity import scenes_by_width as scenes  # noqa: F401  (the module-scoped fixture)
 from oracle import oracle as O
-from test_gpu_hard_hits import DEPTH, N_TRACE, _oracle_trace
-from test_gpu_lds_bvh8 import _render, _tiles, scenes  # noqa: F401  (scenes: the module-scoped fixture)
 
 pytestmark = pytest.mark.gpu
 
+N_TRACE, DEPTH = 4096, 4                # as tests/test_gpu_hard_hits.py traces the same scenes
 WIDTHS = (4, 8)
+REFS = OracleRefs()
 LDS_VARIANTS = (1, 2, 6, 7, 8)          # the variants that take the width (prt_plan.h variant_takes_width)
 CORNELL_NEED8 = 15                      # the Cornell BVH8's stack bound: the deepest a benign scene asks for
 SPECK0 = SP.speck_name(*SP.SPECKS[0])
@@ -96,27 +98,6 @@ def _case(cornell, case):
     return _built[case]
 
 
-def _assert_kernel(ds, n_items, flags, width, v):
-    """The launch does take the kernel under test: tree width, variant, scene in LDS."""
-    assert ds.kernel_info()["lds_scene"], ds.kernel_info()
-    info = ds.kernel_info(n_items, flags)
-    assert info["bvh_arity"] == width and info["variant"] == v and info["lds_scene"], (width, v, info)
-    return info
-
-
-def _check_trace(ds, osc, case, width, v, o, d, ties=None):
-    info = _assert_kernel(ds, o.shape[0], v << 8, width, v)
-    ref = _oracle_trace("width:" + case, osc, o, d, False)
-    assert np.isfinite(ref).all() and ref.mean() > 0
-    L = ds.trace_rays(o, d, DEPTH, seed=17, flags=v << 8)
-    ds.check_faults()
-    bad = np.nonzero(np.any(L.view(np.uint32) != ref.view(np.uint32), axis=1))[0]
-    print(f"{case}: width {info['bvh_arity']} variant {info['variant']} stack {info['stack']}, {o.shape[0]} rays, "
-          f"{bad.size} differ from the oracle")
-    on_ties = None if ties is None else "%d of the differing rays are tie rays" % int(ties[bad].sum())
-    assert bad.size == 0, (case, width, v, bad.size, on_ties, [(i, o[i], d[i], L[i], ref[i]) for i in bad[:3]])
-
-
 # ------------------------------------------------------------------ 4a: path level
 def test_the_cases_are_the_ones_the_width_rule_moved(scenes, cornell):
     """With PRT_LDS_WIDTH unset the two-level hostile scenes run at width 4 and the Cornell-sized cases at
@@ -138,24 +119,24 @@ def test_hostile_paths_at_both_widths(scenes, cornell, case, width, v):
     """Up to 4096 caller rays, depth 4, seed 17 through prt_trace_rays: every path's radiance bits equal the
     oracle's, at either tree width, in each LDS reference variant."""
     name, flat, o, d, osc = _case(cornell, case)
-    _check_trace(scenes(name, flat, width), osc, case, width, v, o, d, _tie_rays.get(case))
+    check_trace(scenes(name, flat, width), REFS.trace(case, osc, o, d, DEPTH, 17, False), o, d, DEPTH, 17, v,
+                label="%s at width %d" % (case, width), lds_scene=True, width=width, ties=_tie_rays.get(case))
 
 
 # ------------------------------------------------------------------ 4b: render level
 RENDER_KERNELS = {"default": 0, "lds": 1, "pool": 7}     # name -> forced variant id (0: the scene's default)
-_rendered = {}
 
 
 def _render_case(cornell, name):
     """(flat, camera, oracle image, oracle counters) of one 64 x 64 render, computed once."""
-    if name not in _rendered:
+    def compute():
         flat = S8.soup_scene(cornell[2], S8.SOUP_N) if name == "soup" else HS.case(cornell, name)[0]
-        cam = cornell[1].convert_to_taichi_camera().packed()
-        ref, cnt = O.OracleScene.from_flat(flat).render_tiles(cam, 64, 64, 64, 64, _tiles(64, 64, 64), 4, 8, seed=11,
-                                                              counters=True)
+        cam = packed_camera(cornell)
+        osc = O.OracleScene.from_flat(flat)
+        ref, counted = REFS.render_tiles(name, osc, cam, 64, 64, 64, all_tiles(64, 64, 64), 4, 8, 11)
         assert np.isfinite(ref).all() and ref.mean() > 0
-        _rendered[name] = (flat, cam, ref, (int(cnt[2]), int(cnt[3])))
-    return _rendered[name]
+        return flat, cam, ref, counted
+    return REFS.get(("case", name), compute)
 
 
 @pytest.mark.parametrize("kernel", list(RENDER_KERNELS))
@@ -166,7 +147,7 @@ def test_hostile_renders_at_both_widths(scenes, cornell, name, kernel):
     CU, so their default is the phase-aligned kernel without an occupancy target and the pooled one has to be
     asked for): the width-8 image equals the width-4 image and the oracle's, the STATS image the production
     one, the extension and shadow query counts the oracle's counters; no non-finite sample, no watchdog
-    trip, and the deepest stack entry touched stays within the bound the stack was sized to (_render asserts
+    trip, and the deepest stack entry touched stays within the bound the stack was sized to (render_twice asserts
     the last four).
 
     The deepest stack at width 8 is printed.  It is not deeper than the Cornell BVH8's bound of 15 entries:
@@ -179,21 +160,21 @@ def test_hostile_renders_at_both_widths(scenes, cornell, name, kernel):
     from pyrenderer_amd import _native as N
     flat, cam, ref, counted = _render_case(cornell, name)
     variant = RENDER_KERNELS[kernel]
-    ids = _tiles(64, 64, 64)
+    ids = all_tiles(64, 64, 64)
     got = {}
     for width in WIDTHS:
         ds = scenes(name, flat, width)
         assert ds.kernel_info()["lds_scene"]
-        got[width] = _render(ds, cam, 64, 64, 64, ids, 4, 8, 11, variant, width)
-        info = ds.kernel_info(len(ids) * 64 * 64 * 4, variant << 8)
+        got[width] = render_twice(ds, cam, 64, 64, 64, ids, 4, 8, 11, variant << 8, width=width)
+        info = got[width]["info"]
         assert info["variant"] in LDS_VARIANTS
-        deepest = int(ds.diag_words(N.PRT_DIAG_WORDS)[N.PRT_DIAG_MAX_STACK])
+        deepest = int(got[width]["words"][N.PRT_DIAG_MAX_STACK])
         print(f"{name} {kernel}: width {info['bvh_arity']} variant {info['variant']}, deepest stack {deepest} of "
-              f"{info['stack']}, {int((got[width][0] != ref).any(axis=-1).sum())} pixels differ from the oracle")
+              f"{info['stack']}, {int((got[width]['img'] != ref).any(axis=-1).sum())} pixels differ from the oracle")
         if width == 8 and name != "soup":
             assert info["stack"] > CORNELL_NEED8, info      # sized for more than the Cornell tree ever needs
-    assert np.array_equal(got[8][0], got[4][0]) and np.array_equal(got[8][0], ref), name
-    assert got[8][1] == got[4][1] == counted, (got[8][1], got[4][1], counted)
+    assert np.array_equal(got[8]["img"], got[4]["img"]) and np.array_equal(got[8]["img"], ref), name
+    assert got[8]["queries"] == got[4]["queries"] == counted, (got[8]["queries"], got[4]["queries"], counted)
 
 
 # ------------------------------------------------------------------ 4c: suspended tails, two-level BVH8
@@ -204,18 +185,20 @@ def test_suspended_tails_on_a_two_level_bvh8(scenes, cornell):
     default.  No oracle render at this size; the 64 x 64 render above ties the scene to the oracle."""
     from pyrenderer_amd import _native as N
     flat = HS.case(cornell, "layers-0")[0]
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W = H = 256
-    ids = _tiles(W, H, 64)
+    ids = all_tiles(W, H, 64)
     pool = N.VAR_LDS_POOL
-    got = {thr: _render(scenes("layers-0", flat, 8, PRT_POOL_RESUME_MIN=thr), cam, W, H, 64, ids, 16, 8, 2, pool, 8)
-           for thr in (0, 1, 64)}
-    base4 = _render(scenes("layers-0", flat, 4, PRT_POOL_RESUME_MIN=0), cam, W, H, 64, ids, 16, 8, 2, pool, 4)
-    print("layers-0 width 8 variant %d, suspensions per threshold:" % pool, {thr: g[2] for thr, g in got.items()})
-    assert got[0][2] == 0 and got[64][2] > 0
+    got = {thr: render_twice(scenes("layers-0", flat, 8, PRT_POOL_RESUME_MIN=thr), cam, W, H, 64, ids, 16, 8, 2,
+                             pool << 8, width=8) for thr in (0, 1, 64)}
+    base4 = render_twice(scenes("layers-0", flat, 4, PRT_POOL_RESUME_MIN=0), cam, W, H, 64, ids, 16, 8, 2, pool << 8,
+                         width=4)
+    suspended = {thr: int(g["words"][N.PRT_DIAG_SUSPENDED]) for thr, g in got.items()}
+    print("layers-0 width 8 variant %d, suspensions per threshold:" % pool, suspended)
+    assert suspended[0] == 0 and suspended[64] > 0
     for thr in (1, 64):
-        assert np.array_equal(got[thr][0], got[0][0]) and got[thr][1] == got[0][1], thr
-    assert np.array_equal(got[0][0], base4[0]) and got[0][1] == base4[1]
+        assert np.array_equal(got[thr]["img"], got[0]["img"]) and got[thr]["queries"] == got[0]["queries"], thr
+    assert np.array_equal(got[0]["img"], base4["img"]) and got[0]["queries"] == base4["queries"]
 
 
 # ------------------------------------------------------------------ the soup at the LDS limit

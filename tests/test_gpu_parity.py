@@ -8,9 +8,12 @@ asserted too: >= 99.9% of pixels identical to the last bit (measured: 100%).
 import numpy as np
 import pytest
 
+from kernel_parity import nee_mode, packed_camera, soup_scene, specular_scene
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
+
+_soup_scene = soup_scene   # tools/ab_variants.py (--scene soup:N) imports the scene under this name
 
 TOL_RMSE = 1e-3
 
@@ -34,7 +37,7 @@ def _compare(gpu_sum, ora_sum, spp):
                                            (64, 64, 8, 8),       # config 2's estimator at small size
                                            (100, 70, 3, 16)])    # ragged tiles, reference default depth
 def test_cornell_matches_oracle(gpu_scene, oracle_scene, cornell, W, H, spp, depth):
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     g = _gpu_frame(gpu_scene, cam, W, H, spp, depth, seed=7)
     o = oracle_scene.render(cam, W, H, spp, depth, seed=7)
     assert np.isfinite(g).all()
@@ -46,7 +49,7 @@ def test_cornell_matches_oracle(gpu_scene, oracle_scene, cornell, W, H, spp, dep
 def test_counters_match_oracle(gpu_scene, oracle_scene, cornell):
     """Extension / shadow query counts are a deterministic function of the paths."""
     from pyrenderer_amd._native import PRT_FLAG_STATS
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(4, dtype=np.int32)
     _, st = gpu_scene.render_tiles(cam, 64, 64, 32, 32, ids, 4, 8, 3, PRT_FLAG_STATS)
     _, oc = oracle_scene.render_tiles(cam, 64, 64, 32, 32, ids, 4, 8, seed=3, counters=True)
@@ -57,7 +60,7 @@ def test_counters_match_oracle(gpu_scene, oracle_scene, cornell):
 def test_tiling_and_sharding_invariance(gpu_scene, cornell):
     """RNG keyed by global pixel: tile size and tile order do not change a bit."""
     from pyrenderer_amd.device_scene import interleaved_tiles, unpack_tiles
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     a = _gpu_frame(gpu_scene, cam, 96, 80, 4, 8, seed=5, tile=64)
     b = _gpu_frame(gpu_scene, cam, 96, 80, 4, 8, seed=5, tile=16)
     np.testing.assert_array_equal(a, b)
@@ -75,7 +78,7 @@ def test_tiling_and_sharding_invariance(gpu_scene, cornell):
 
 
 def test_edge_cases(gpu_scene, oracle_scene, cornell):
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     z, _ = gpu_scene.render_tiles(cam, 8, 8, 8, 8, np.array([0], np.int32), 0, 8)
     assert not z.any()
     z, _ = gpu_scene.render_tiles(cam, 8, 8, 8, 8, np.array([0], np.int32), 4, 0)
@@ -94,31 +97,10 @@ def test_edge_cases(gpu_scene, oracle_scene, cornell):
 
 
 def test_depth1_is_direct_light_only(gpu_scene, oracle_scene, cornell):
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     g = _gpu_frame(gpu_scene, cam, 48, 48, 4, 1, seed=1)
     o = oracle_scene.render(cam, 48, 48, 4, 1, seed=1)
     np.testing.assert_array_equal(g, o)
-
-
-def _soup_scene(cornell, n_extra, seed):
-    """Cornell + a random triangle soup inside the box (config 4's shape, small)."""
-    from pyrenderer_amd.flatten import FlatScene
-    f = cornell[2]
-    rng = np.random.default_rng(seed)
-    c = np.stack([rng.uniform(-0.9, 0.9, n_extra), rng.uniform(0.05, 1.8, n_extra), rng.uniform(-0.9, 0.9, n_extra)], 1)
-    tv = (c[:, None, :] + rng.normal(0, 0.03, (n_extra, 3, 3))).astype(np.float32).reshape(-1, 9)
-    e1 = tv[:, 3:6] - tv[:, 0:3]
-    e2 = tv[:, 6:9] - tv[:, 0:3]
-    nn = np.cross(e1.astype(np.float64), e2.astype(np.float64))
-    nn = (nn / np.linalg.norm(nn, axis=1, keepdims=True)).astype(np.float32)
-    # extra triangles first so the light's triangle ids move
-    tri_v = np.concatenate([tv, f.tri_v])
-    tri_n = np.concatenate([nn, f.tri_n])
-    tri_mat = np.concatenate([np.full(n_extra, 0, np.int32), f.tri_mat])
-    tri_prim = np.concatenate([np.zeros(n_extra, np.int32), f.tri_prim + 1])
-    lo = np.concatenate([tv.reshape(-1, 3, 3).min(1).min(0)[None], f.prim_lo])
-    hi = np.concatenate([tv.reshape(-1, 3, 3).max(1).max(0)[None], f.prim_hi])
-    return FlatScene(tri_v, tri_n, tri_mat, tri_prim, lo, hi, f.mat, f.light_tri + n_extra, f.light_off, f.direct_rgb)
 
 
 @pytest.mark.parametrize("n_extra", [0, 6, 12, 20, 28, 40])
@@ -130,7 +112,7 @@ def test_default_variant_reaches_its_occupancy(cornell, n_extra):
     Each scene also renders bit-identically to the oracle with that variant."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    flat = _soup_scene(cornell, n_extra, 11) if n_extra else cornell[2]
+    flat = soup_scene(cornell, n_extra, 11) if n_extra else cornell[2]
     ds = DeviceScene(flat, 0)
     var = ds.kernel_info()["variant"]
     want = {N.VAR_LDS_POOL: (7,), N.VAR_LDS: (7,), N.VAR_LDS6: (6,), N.VAR_GLOBAL: (6,),
@@ -138,7 +120,7 @@ def test_default_variant_reaches_its_occupancy(cornell, n_extra):
     assert var in want, var
     assert ds.blocks_per_cu in want[var], (n_extra, var, ds.blocks_per_cu)
     osc = O.OracleScene.from_flat(flat)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     g = _gpu_frame(ds, cam, 32, 32, 2, 6, seed=5)
     o = osc.render(cam, 32, 32, 2, 6, seed=5)
     np.testing.assert_array_equal(g, o)
@@ -152,7 +134,7 @@ def test_default_variants_cover_the_lds_builds(cornell):
     from pyrenderer_amd.device_scene import DeviceScene
     seen = set()
     for n_extra in (0, 6, 12, 20, 28, 40):
-        ds = DeviceScene(_soup_scene(cornell, n_extra, 11) if n_extra else cornell[2], 0)
+        ds = DeviceScene(soup_scene(cornell, n_extra, 11) if n_extra else cornell[2], 0)
         seen.add(ds.kernel_info()["variant"])
         ds.close()
     assert N.VAR_LDS_POOL in seen and ({N.VAR_LDS, N.VAR_LDS6} & seen), seen
@@ -160,11 +142,11 @@ def test_default_variants_cover_the_lds_builds(cornell):
 
 def test_triangle_soup_matches_oracle(cornell):
     from pyrenderer_amd.device_scene import DeviceScene
-    flat = _soup_scene(cornell, 3000, 9)
+    flat = soup_scene(cornell, 3000, 9)
     ds = DeviceScene(flat, 0)
     assert ds.bvh_depth > 5
     osc = O.OracleScene.from_flat(flat)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     g = _gpu_frame(ds, cam, 48, 48, 2, 6, seed=2)
     o = osc.render(cam, 48, 48, 2, 6, seed=2)
     rmse, same = _compare(g, o, 2)
@@ -178,12 +160,12 @@ def test_lds_soup_deep_stack_matches_oracle(cornell):
     oracle and against the global-scene kernel on the same scene."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    flat = _soup_scene(cornell, 12, 11)
+    flat = soup_scene(cornell, 12, 11)
     ds = DeviceScene(flat, 0)
     k = ds.kernel_info()
     assert k["lds_scene"] and k["stack"] >= 16 and ds.bvh_depth > 4, (k, ds.bvh_depth)
     osc = O.OracleScene.from_flat(flat)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     g = _gpu_frame(ds, cam, 64, 64, 4, 8, seed=4)
     o = osc.render(cam, 64, 64, 4, 8, seed=4)
     np.testing.assert_array_equal(g, o)
@@ -204,7 +186,7 @@ def test_largest_lds_scene_matches_oracle_in_every_lds_variant(cornell):
     from pyrenderer_amd.device_scene import DeviceScene
 
     def resident(n):
-        ds = DeviceScene(_soup_scene(cornell, n, 11), 0)
+        ds = DeviceScene(soup_scene(cornell, n, 11), 0)
         try:
             return ds.kernel_info()["lds_scene"]
         finally:
@@ -216,18 +198,15 @@ def test_largest_lds_scene_matches_oracle_in_every_lds_variant(cornell):
         mid = (lo + hi) // 2
         lo, hi = (mid, hi) if resident(mid) else (lo, mid)
     assert lo >= 1 and resident(lo) and not resident(lo + 1), lo
-    flat = _soup_scene(cornell, lo, 11)
+    flat = soup_scene(cornell, lo, 11)
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(1, dtype=np.int32)
     want = {}
     for mis in (False, True):
-        O.set_nee_mode(mis)
-        try:
+        with nee_mode(mis):
             want[mis] = osc.render_tiles(cam, 64, 64, 64, 64, ids, 4, 4, seed=3)
-        finally:
-            O.set_nee_mode(False)
     for var in (N.VAR_LDS, N.VAR_LDS_ANY_OCC, N.VAR_LDS6, N.VAR_LDS_POOL, N.VAR_LDS_POOL6, N.VAR_MIS[0]):
         mis = var == N.VAR_MIS[0]
         flags = (var << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
@@ -247,7 +226,7 @@ def test_full_size_config2_matches_oracle(gpu_scene, oracle_scene, cornell):
     rare events (e.g. a direction component of exactly 0, ~2^-24 per draw) occur a
     few times, so a sampled check is not enough."""
     import os
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W = H = 512
     full = _gpu_frame(gpu_scene, cam, W, H, 64, 8, seed=0)
     assert np.isfinite(full).all() and full.mean() > 0
@@ -257,29 +236,13 @@ def test_full_size_config2_matches_oracle(gpu_scene, oracle_scene, cornell):
     assert not diff.any(), (int(diff.sum()), np.argwhere(diff)[:5])
 
 
-def _specular_scene(rough=0.0, spheres=True):
-    import json
-    import os
-    from conftest import ROOT
-    from pyrenderer_amd.flatten import flatten_scene
-    from pyrenderer_amd.io_utils.read_tungsten import process_primitives
-    d = json.load(open(os.path.join(ROOT, "pyrenderer_amd", "media", "cornell-box", "scene_specular.json")))
-    for b in d["bsdfs"]:
-        if b["type"] == "metal":
-            b["roughness"] = rough
-    if not spheres:
-        d["primitives"] = [p for p in d["primitives"] if p["type"] != "sphere"]
-    scene, cam = process_primitives(d)
-    return scene, cam, flatten_scene(scene)
-
-
 @pytest.mark.parametrize("rough,kernel", [(0.0, "default"), (0.35, "default"), (0.35, "phase")])
 def test_specular_scene_matches_oracle(rough, kernel):
     """Config 3's materials (metal, dielectric, sphere) through the C-ABI vs the oracle: the default
     (the pooled kernel's full build) and, forced, the phase-aligned LDS kernel."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    scene, cam, flat = _specular_scene(rough)
+    scene, cam, flat = specular_scene(rough)
     assert flat.sph.shape[0] == 1 and (flat.mat[:, 5] == 2).any() and (flat.mat[:, 5] == 3).any()
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
@@ -299,7 +262,7 @@ def test_pool_variants_identical_on_the_specular_scene():
     test_specular_scene_matches_oracle requires."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    scene, cam, flat = _specular_scene(0.35)
+    scene, cam, flat = specular_scene(0.35)
     ds = DeviceScene(flat, 0)
     c = cam.convert_to_taichi_camera().packed()
     imgs = {v: _gpu_frame(ds, c, 64, 64, 4, 8, seed=6, flags=v << 8) for v in N.VAR_POOL}
@@ -317,7 +280,7 @@ def test_specular_boxes_without_spheres_take_the_full_pooled_build():
     must not be chosen — it has no specular code — so the image still matches the oracle."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    scene, cam, flat = _specular_scene(0.35, spheres=False)
+    scene, cam, flat = specular_scene(0.35, spheres=False)
     assert flat.sph.shape[0] == 0 and (flat.mat[:, 5] == 2).any() and (flat.mat[:, 5] == 3).any()
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
@@ -334,7 +297,7 @@ def test_all_kernel_variants_bit_identical(gpu_scene, oracle_scene, cornell):
     occupancy target, global scene: quantised nodes, spill stack, suspended tails) renders
     the same bits as the oracle."""
     from pyrenderer_amd.device_scene import interleaved_tiles
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = interleaved_tiles(64, 64, 32)
     o = oracle_scene.render_tiles(cam, 64, 64, 32, 32, ids, 4, 8, seed=2)
     from pyrenderer_amd import _native as N
@@ -349,7 +312,7 @@ def test_frames_in_flight_on_two_streams(gpu_scene, oracle_scene, cornell):
     import torch
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import interleaved_tiles, unpack_tiles
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W, spp, tile = 128, 8, 64
     ids = interleaved_tiles(W, W, tile)
     o = oracle_scene.render_tiles(cam, W, W, tile, tile, ids, spp, 8, seed=7)
@@ -392,7 +355,7 @@ def test_tile_set_changes_on_one_stream(gpu_scene, oracle_scene, cornell):
     alternating tile sets (and sizes) on one stream must each match the oracle."""
     import torch
     from pyrenderer_amd.device_scene import interleaved_tiles
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W, spp = 128, 4
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
@@ -413,7 +376,7 @@ def test_tile_set_changes_on_one_stream(gpu_scene, oracle_scene, cornell):
 def test_general_camera_matches_oracle(gpu_scene, oracle_scene, cornell, mod):
     """The kernel's pinhole/affine camera shortcut must not change a bit, and the
     general gen_ray (thin-lens draws, non-affine matrix) must match too."""
-    cam = cornell[1].convert_to_taichi_camera().packed().copy()
+    cam = packed_camera(cornell).copy()
     if mod == "aperture":
         cam[19] = 1.0          # sensor_dim.w > 0: lens sample (camera_taichi.py:57-60)
     else:
@@ -429,7 +392,7 @@ def test_spill_stack_matches_oracle(cornell, oracle_scene, monkeypatch):
     from pyrenderer_amd.device_scene import DeviceScene, interleaved_tiles
     monkeypatch.setenv("PRT_SPILL_LDS", "4")
     ds = DeviceScene(cornell[2], 0)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = interleaved_tiles(64, 64, 32)
     o = oracle_scene.render_tiles(cam, 64, 64, 32, 32, ids, 4, 8, seed=2)
     from pyrenderer_amd import _native as N
@@ -443,7 +406,7 @@ def test_bvh4_collapse_choice_keeps_the_image(cornell, oracle_scene, monkeypatch
     oracle's image bit for bit, and the optimal one visits no more nodes."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene, interleaved_tiles
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = interleaved_tiles(64, 64, 32)
     o = oracle_scene.render_tiles(cam, 64, 64, 32, 32, ids, 4, 8, seed=5)
     flags = N.PRT_FLAG_STATS | ((N.VAR_GLOBAL << 8) if variant == "global" else 0)
@@ -463,7 +426,7 @@ def test_large_frame_matches_oracle(gpu_scene, oracle_scene, cornell):
     (p2.x == p.x), which once made BVH4 empty slots (then ref = root) 'hit' and the
     traversal loop forever.  Whole frame against the oracle."""
     import os
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W = H = 1024
     g = _gpu_frame(gpu_scene, cam, W, H, 32, 8, seed=0)
     o = oracle_scene.render(cam, W, H, 32, 8, seed=0, nthreads=min(16, len(os.sched_getaffinity(0))))
@@ -476,15 +439,12 @@ def test_mis_direct_lighting_variant_matches_oracle(gpu_scene, oracle_scene, cor
     as the optional NEE variant: LDS-scene kernel (variant 32) bit-identical to the oracle's
     MIS mode, and different from the default estimator's image."""
     from pyrenderer_amd import _native as N
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     W, H, spp, depth = 64, 48, 4, 8
     ids = np.arange(((W + 31) // 32) * ((H + 31) // 32), dtype=np.int32)
-    O.set_nee_mode(True)
-    try:
+    with nee_mode(True):
         o = oracle_scene.render_tiles(cam, W, H, 32, 32, ids, spp, depth, seed=4)
         oc = oracle_scene.render_tiles(cam, W, H, 32, 32, ids, 2, depth, seed=4, counters=True)[1]
-    finally:
-        O.set_nee_mode(False)
     g, _ = gpu_scene.render_tiles(cam, W, H, 32, 32, ids, spp, depth, 4, N.PRT_FLAG_MIS_NEE)
     assert np.isfinite(g).all() and g.any()
     np.testing.assert_array_equal(g, o)
@@ -508,16 +468,13 @@ def test_mis_variant_on_a_global_scene_matches_oracle(cornell):
     """MIS estimator on a scene too large for LDS (default global MIS kernel, variant 33)."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    flat = _soup_scene(cornell, 3000, 11)
+    flat = soup_scene(cornell, 3000, 11)
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(4, dtype=np.int32)
-    O.set_nee_mode(True)
-    try:
+    with nee_mode(True):
         o = osc.render_tiles(cam, 64, 64, 32, 32, ids, 2, 8, seed=6)
-    finally:
-        O.set_nee_mode(False)
     g, _ = ds.render_tiles(cam, 64, 64, 32, 32, ids, 2, 8, 6, N.PRT_FLAG_MIS_NEE)
     np.testing.assert_array_equal(g, o)
     ds.close()
@@ -530,7 +487,7 @@ def test_nonfinite_sample_counter(gpu_scene, cornell):
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
     from pyrenderer_amd.flatten import FlatScene
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(4, dtype=np.int32)
     gpu_scene.render_tiles(cam, 64, 64, 32, 32, ids, 2, 8, 1, N.PRT_FLAG_STATS)
     assert gpu_scene.diag_stats()[N.PRT_DIAG_NONFINITE] == 0
@@ -552,16 +509,13 @@ def test_mis_variant_on_the_specular_scene():
     on the analytic sphere (hit ids >= n_tri, sphere material lookup) and on specular boxes."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    scene, cam, flat = _specular_scene(0.35)
+    scene, cam, flat = specular_scene(0.35)
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
     c = cam.convert_to_taichi_camera().packed()
     ids = np.arange(4, dtype=np.int32)
-    O.set_nee_mode(True)
-    try:
+    with nee_mode(True):
         o = osc.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, seed=12)
-    finally:
-        O.set_nee_mode(False)
     g, _ = ds.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, 12, N.PRT_FLAG_MIS_NEE)
     assert np.isfinite(g).all() and g.sum() > 0
     rmse, same = _compare(g, o, 4)
@@ -578,17 +532,14 @@ def test_kernels_bit_identical_on_the_specular_scene(variant):
     the oracle's image (64 x 64, 4 spp, depth 8)."""
     from pyrenderer_amd import _native as N
     from pyrenderer_amd.device_scene import DeviceScene
-    scene, cam, flat = _specular_scene(0.35)
+    scene, cam, flat = specular_scene(0.35)
     ds = DeviceScene(flat, 0)
     osc = O.OracleScene.from_flat(flat)
     c = cam.convert_to_taichi_camera().packed()
     ids = np.arange(4, dtype=np.int32)
     mis = variant in N.VAR_MIS
-    O.set_nee_mode(mis)
-    try:
+    with nee_mode(mis):
         o = osc.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, seed=13)
-    finally:
-        O.set_nee_mode(False)
     flags = (variant << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
     assert ds.kernel_info(n_items=64 * 64 * 4, flags=flags)["variant"] == variant
     g, _ = ds.render_tiles(c, 64, 64, 32, 32, ids, 4, 8, 13, flags)

@@ -26,53 +26,32 @@ import numpy as np
 import pytest
 
 import shade_cases as C
-from hard_scenes import T_MAX, T_MIN
-from oracle import oracle as O
+from kernel_parity import (ALL_VARIANTS, T_MAX, T_MIN, OracleRefs, check_trace, is_mis, packed_camera, variant_flags,
+                           world_cache, wrong_rows)
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-ALL_VARIANTS = [1, 2, 3, 6, 7, 8, 4, 5]
-_traced = {}
+REFS = OracleRefs()
 
 
 @pytest.fixture(scope="module")
 def world(cornell):
     """name -> (DeviceScene, OracleScene); each scene is created once for the module."""
-    from pyrenderer_amd.device_scene import DeviceScene
-    made = {}
-
-    def get(name):
-        if name not in made:
-            flat = C.case(cornell, name)
-            made[name] = (DeviceScene(flat, 0), O.OracleScene.from_flat(flat))
-        return made[name]
-    yield get
-    for ds, _ in made.values():
-        ds.close()
-
-
-def _wrong(got, want, nan_aware):
-    """Row indices on which `got` differs from `want`: as uint32 bits, or NaN-aware: a NaN wherever the
-    other has one, and the same bits everywhere else."""
-    same = got.view(np.uint32) == want.view(np.uint32)
-    if nan_aware:
-        same |= np.isnan(got) & np.isnan(want)
-    return np.nonzero(~same.reshape(same.shape[0], -1).all(axis=1))[0]
+    yield from world_cache(lambda name: (C.case(cornell, name),))
 
 
 @pytest.mark.parametrize("name", C.CASES)
 def test_the_live_scene_reports_the_tables_flags(world, name):
     """kernel_info()'s shade_fast and plain are the uploaded scene's own: what the table says, for a large
     launch and for every forced variant alike, so the tests below run the side they claim."""
-    from pyrenderer_amd import _native as N
     ds, _ = world(name)
     _, plain, shade_fast, _ = C.TABLE[name]
     info = ds.kernel_info()
     assert (info["plain"], info["shade_fast"]) == (plain, shade_fast), (name, info)
     assert info["lds_scene"] == (name != C.SOUP), (name, info)
     for v in ALL_VARIANTS:
-        i = ds.kernel_info(n_items=C.N_RAYS, flags=(v << 8) | (N.PRT_FLAG_MIS_NEE if v in N.VAR_MIS else 0))
+        i = ds.kernel_info(n_items=C.N_RAYS, flags=variant_flags(v))
         assert (i["plain"], i["shade_fast"]) == (plain, shade_fast), (name, v, i)
 
 
@@ -82,36 +61,11 @@ def test_the_unedited_box_reports_both_flags_set(gpu_scene):
 
 
 # ------------------------------------------------------------------ kernel level
-def _oracle_trace(name, osc, mis):
-    if (name, mis) not in _traced:
-        O.set_nee_mode(mis)
-        try:
-            _traced[name, mis] = osc.trace_rays(*C.rays(), C.DEPTH, seed=C.SEED)
-        finally:
-            O.set_nee_mode(False)
-    return _traced[name, mis]
-
-
 def _check_trace(ds, osc, name, v, lds_scene=True):
-    from pyrenderer_amd import _native as N
-    mis = v in N.VAR_MIS
-    flags = (v << 8) | (N.PRT_FLAG_MIS_NEE if mis else 0)
     o, d = C.rays()
-    info = ds.kernel_info(n_items=C.N_RAYS, flags=flags)
-    assert ds.kernel_info()["lds_scene"] == lds_scene, ds.kernel_info()
-    assert info["variant"] == v and info["shade_fast"] == C.TABLE[name][2], info
-    print(f"{name}: variant {v} ran at bvh_arity {info['bvh_arity']}, shade_fast {info['shade_fast']}")
-    ref = _oracle_trace(name, osc, mis)
-    finite = C.TABLE[name][3]
-    bad_ref = int((~np.isfinite(ref)).any(axis=1).sum())
-    if finite:
-        assert bad_ref == 0 and ref.mean() > 0
-    else:
-        assert 1 <= bad_ref <= C.N_RAYS // 2, bad_ref
-    L = ds.trace_rays(o, d, C.DEPTH, seed=C.SEED, flags=flags)
-    ds.check_faults()
-    bad = _wrong(L, ref, nan_aware=not finite)
-    assert bad.size == 0, (name, v, bad.size, [(i, o[i], d[i], L[i], ref[i]) for i in bad[:3]])
+    ref = REFS.trace(name, osc, o, d, C.DEPTH, C.SEED, is_mis(v))
+    check_trace(ds, ref, o, d, C.DEPTH, C.SEED, v, label=name, lds_scene=lds_scene,
+                expect={"shade_fast": C.TABLE[name][2]}, finite=C.TABLE[name][3])
 
 
 @pytest.mark.parametrize("v", ALL_VARIANTS)
@@ -129,8 +83,7 @@ def test_an_lds_case_takes_all_eight_variants(world):
     from pyrenderer_amd import _native as N
     ds, _ = world("black")
     assert sorted(ALL_VARIANTS) == sorted(list(N.VAR_REFERENCE) + list(N.VAR_MIS)) == list(range(1, N.VAR_LAST + 1))
-    ran = {ds.kernel_info(n_items=C.N_RAYS, flags=(v << 8) | (N.PRT_FLAG_MIS_NEE if v in N.VAR_MIS else 0))["variant"]
-           for v in ALL_VARIANTS}
+    ran = {ds.kernel_info(n_items=C.N_RAYS, flags=variant_flags(v))["variant"] for v in ALL_VARIANTS}
     assert ran == set(range(1, 9))
 
 
@@ -156,22 +109,22 @@ def test_render_and_counters_match_the_oracle(world, cornell, name, kernel):
     non-finite oracle pixels."""
     from pyrenderer_amd import _native as N
     ds, osc = world(name)
-    cam = cornell[1].convert_to_taichi_camera().packed()
+    cam = packed_camera(cornell)
     ids = np.arange(1, dtype=np.int32)
     spp, seed = (4, 9) if name == "black" else (1, SEED_ABOVE)
     flags = N.PRT_FLAG_STATS | ((N.VAR_LDS << 8) if kernel == "lds" else 0)
     want_var = N.VAR_LDS if kernel == "lds" else N.VAR_LDS_POOL
     info = ds.kernel_info(n_items=32 * 32 * spp, flags=flags)
     assert info["variant"] == want_var and not info["shade_fast"], info
-    ref, oc = osc.render_tiles(cam, 32, 32, 32, 32, ids, spp, 8, seed=seed, counters=True)
+    ref, oc = REFS.render_tiles(name, osc, cam, 32, 32, 32, ids, spp, 8, seed)
     bad_ref = int((~np.isfinite(ref)).any(axis=1).sum())
     assert (bad_ref == 0 and ref.mean() > 0) if name == "black" else bad_ref >= 1, bad_ref
     for fl in (flags, flags & ~N.PRT_FLAG_STATS):
         got, st = ds.render_tiles(cam, 32, 32, 32, 32, ids, spp, 8, seed, fl)
-        bad = _wrong(got, ref, nan_aware=name == "above")
+        bad = wrong_rows(got, ref, nan_aware=name == "above")
         assert bad.size == 0, (name, kernel, fl, bad.size, [(i, got[i], ref[i]) for i in bad[:3]])
         if fl & N.PRT_FLAG_STATS:
-            assert st[2] == oc[2] and st[3] == oc[3] and st[0] > 0 and st[1] > 0, (st, oc)
+            assert (st[2], st[3]) == oc and st[0] > 0 and st[1] > 0, (st, oc)
             assert ds.diag_stats()[N.PRT_DIAG_NONFINITE] == bad_ref, (ds.diag_stats()[N.PRT_DIAG_NONFINITE], bad_ref)
 
 
@@ -185,7 +138,7 @@ def test_hit_all_records_carry_the_non_unit_normal(world, name, quantized):
     o, d = C.rays()
     want = osc.hit_all(o, d, T_MIN, T_MAX, seed=11)
     got = ds.hit_all(o, d, T_MIN, T_MAX, seed=11, quantized=quantized)
-    bad = _wrong(got, want, nan_aware=False)
+    bad = wrong_rows(got, want)
     assert bad.size == 0, (name, quantized, bad.size, [(i, o[i], d[i], got[i], want[i]) for i in bad[:3]])
     ln = np.linalg.norm(want[:, 5:8].astype(np.float64), axis=1)
     scale = 3 if name == "n3" else 0.25
@@ -203,14 +156,13 @@ def test_black_wall_features_and_denoised_frame(world, cornell):
     """prt_features on `black` at 48 x 48, 2 samples, against the host composition bit for bit; the albedo
     is exactly 0 on the pixels whose samples all end on the black wall, and the filter, which divides the
     colour by the albedo, leaves a 4-spp render of the scene finite everywhere."""
-    from pyrenderer_amd.denoise import denoise
+    from pyrenderer_amd.denoise import denoise, features_packed_host
     from pyrenderer_amd.device_scene import unpack_tiles
-    from test_gpu_features import _host
     ds, _ = world("black")
-    pc = cornell[1].convert_to_taichi_camera().packed()
+    pc = packed_camera(cornell)
     W = H = 48
     got = ds.features(pc, W, H, samples=2, seed=7)
-    want = _host(ds, pc, W, H, 2, 7)
+    want = features_packed_host(ds, pc, W, H, samples=2, seed=7, tile=16)
     diff = np.argwhere(np.any(got.view(np.uint32) != want.view(np.uint32), axis=-1))
     assert len(diff) == 0, (len(diff), diff[:5])
     black = (want[..., 7] == 1) & ~want[..., 0:3].any(axis=-1)          # every sample hit, albedo sum exactly 0

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import hard_spheres as S
-from hard_scenes import T_MAX, T_MIN, random_bounds
+from kernel_parity import T_MAX, T_MIN, nee_mode, random_bounds
 from oracle import oracle as O
 
 F = np.float32
@@ -46,11 +46,8 @@ def test_scene_is_valid_and_its_radiance_finite(cornell, name):
     for key, (o, d) in sets.items():
         assert o.shape == d.shape and o.shape[0] <= 4096 and np.isfinite(o).all() and np.isfinite(d).all()
         for mis in (False, True):
-            O.set_nee_mode(mis)
-            try:
+            with nee_mode(mis):
                 L = osc.trace_rays(o, d, 8, seed=17)
-            finally:
-                O.set_nee_mode(False)
             assert np.isfinite(L).all() and L.mean() > 0, (name, key, mis)
 
 

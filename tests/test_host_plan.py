@@ -3,36 +3,15 @@ packing, environment knobs, tile / window / ownership arithmetic, the launch-chu
 run in its AddressSanitizer + UndefinedBehaviorSanitizer build through the stand-alone driver
 tools/sanitize/host_check.cpp and compared with numpy restatements.  A subprocess per call: exit code 0,
 no sanitizer text on stderr, one JSON line on stdout."""
-import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
-from scene_cases import ARRAYS, REJECTED, base_scene, scene
+from host_plan_driver import _flat_args, _run, _scene, built  # noqa: F401  (built: the driver's fixture)
+from scene_cases import REJECTED, base_scene, scene
 
-SAN = os.path.join(ROOT, "tools", "sanitize")
-OUT = os.path.join(ROOT, "build", "sanitize")
 F = np.float32
-
-
-@pytest.fixture(scope="module")
-def built():
-    subprocess.run(["make", "-s", "-C", SAN, os.path.join(OUT, "host_check")], check=True, capture_output=True,
-                   timeout=600)
-    return os.path.join(OUT, "host_check")
-
-
-def _run(built, *args, **env):
-    e = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1", **env)
-    r = subprocess.run([built] + [str(a) for a in args], env=e, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    lines = r.stdout.strip().splitlines()
-    assert len(lines) == 1, r.stdout[-2000:]
-    return json.loads(lines[0])
 
 
 # ---------------------------------------------------------------- tiles, windows, ownership
@@ -471,14 +450,6 @@ def test_camera_terms_in_f32_order(built, cornell, tmp_path):
 
 # ---------------------------------------------------------------- scene validation and packing
 
-def _scene(built, d, s):
-    os.makedirs(d, exist_ok=True)
-    for name in ARRAYS:
-        if s[name] is not None:
-            np.ascontiguousarray(s[name]).tofile(os.path.join(d, name + (".f32" if s[name].dtype == F else ".i32")))
-    return _run(built, "scene", d, s["n_tri"], s["n_sph"], s["n_mat"], s["n_light"])
-
-
 def _packed(d, name, width):
     return np.fromfile(os.path.join(d, name + ".f32"), F).reshape(-1, width)
 
@@ -522,14 +493,6 @@ def _check_packing(d, s, rep):
     for k in range(3):
         assert np.array_equal(lv[:, 4 * k:4 * k + 3], tri_v[t, 3 * k:3 * k + 3]) and not lv[:, 4 * k + 3].any()
     assert np.array_equal(lv[:, 12:15], tri_n[t]) and np.array_equal(lv[:, 15].view(np.int32), tri_mat[t])
-
-
-def _flat_args(flat):
-    has_sph = flat.sph.shape[0] > 0
-    return dict(tri_v=flat.tri_v, tri_n=flat.tri_n, tri_mat=flat.tri_mat, n_tri=flat.n_tri,
-                sph=flat.sph if has_sph else None, sph_mat=flat.sph_mat if has_sph else None, n_sph=flat.sph.shape[0],
-                mat=flat.mat, n_mat=flat.mat.shape[0], light_tri=flat.light_tri, light_off=flat.light_off,
-                n_light=flat.n_light)
 
 
 def test_cornell_packs_as_the_kernels_read_it(built, cornell, tmp_path):

@@ -1,7 +1,7 @@
 """The scenes of tests/shade_cases.py against the host's classification and the oracle alone (no GPU):
 the inputs contain what they are built for, so tests/test_gpu_shade_cases.py cannot pass vacuously.
 
-The host side goes through the stand-alone driver of tests/test_host_plan.py (pack_scene in its
+The host side goes through the stand-alone driver of tests/host_plan_driver.py (pack_scene in its
 sanitizer build): each case's (plain, shade_fast) is what the table says.  The oracle side traces the
 4096 rays at depth 8 with seed 17 under both direct-lighting estimators: the finite cases stay finite and
 carry light, the overflow cases overflow on a few paths, and on every case at least 1000 paths differ in
@@ -17,29 +17,26 @@ import numpy as np
 import pytest
 
 import shade_cases as C
+from host_plan_driver import _flat_args, _scene, built  # noqa: F401  (built: the driver's fixture)
+from kernel_parity import OracleRefs, nee_mode, wrong_rows
 from oracle import oracle as O
-from test_host_plan import _flat_args, _scene, built  # noqa: F401  (built: the driver's fixture)
 
 F = np.float32
-_traced = {}
+REFS = OracleRefs()
 
 
 def _trace(cornell, name, mis, edited=True):
     """The oracle's radiance of the case's rays, (4096, 3); of the unedited scene with edited=False."""
-    key = (name if edited else "base-" + ("soup" if name == C.SOUP else "box"), mis)
-    if key not in _traced:
+    key = name if edited else "base-" + ("soup" if name == C.SOUP else "box")
+    def compute():
         flat = C.case(cornell, name) if edited else C.base(cornell, name)
-        O.set_nee_mode(mis)
-        try:
-            _traced[key] = O.OracleScene.from_flat(flat).trace_rays(*C.rays(), C.DEPTH, seed=C.SEED)
-        finally:
-            O.set_nee_mode(False)
-    return _traced[key]
+        with nee_mode(mis):
+            return O.OracleScene.from_flat(flat).trace_rays(*C.rays(), C.DEPTH, seed=C.SEED)
+    return REFS.get((key, mis), compute)
 
 
 def _differ(cornell, name, mis):
-    return int(np.any(_trace(cornell, name, mis).view(np.uint32) != _trace(cornell, name, mis, False).view(np.uint32),
-                      axis=1).sum())
+    return wrong_rows(_trace(cornell, name, mis), _trace(cornell, name, mis, False)).size
 
 
 def test_rows_are_the_walls_they_are_named_for(cornell):
@@ -138,15 +135,14 @@ def test_the_table_covers_both_sides():
 
 def test_nan_aware_comparison_forgives_payloads_only():
     """The comparison tests/test_gpu_shade_cases.py uses on the overflow cases."""
-    from test_gpu_shade_cases import _wrong
     a = np.array([[1, np.inf, np.nan], [0, 2, 3]], F)
     b = a.copy()
     b.view(np.uint32)[0, 2] ^= 1                                        # another payload of the same NaN
-    assert _wrong(a, b, True).size == 0 and _wrong(a, b, False).tolist() == [0]
+    assert wrong_rows(a, b, True).size == 0 and wrong_rows(a, b, False).tolist() == [0]
     for edit in ((0, 1, -np.inf), (0, 2, np.inf), (1, 0, -0.0), (1, 1, np.nan)):
         c = b.copy()
         c[edit[:2]] = edit[2]
-        assert _wrong(a, c, True).tolist() == [edit[0]], edit
+        assert wrong_rows(a, c, True).tolist() == [edit[0]], edit
 
 
 @pytest.mark.parametrize("mis", [False, True], ids=["reference", "mis"])

@@ -48,7 +48,8 @@ extern "C" {
  * sample-moments variance (prt_moments_add*, prt_denoise_var_given*), then the four of the temporal
  * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*), then the two of adaptive sampling
  * (prt_adaptive_update*), then the two of temporal accumulation across moving objects
- * (prt_temporal_accumulate_motion*). */
+ * (prt_temporal_accumulate_motion*), then the refit of a resident scene (prt_scene_update) and the read-back
+ * of a scene's device buffers (prt_scene_download). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -143,6 +144,47 @@ int prt_scene_create(int device,
  * bytes, blocks/CU of the default variant, CUs */
 int prt_scene_info(void* scene, int64_t* info8);
 void prt_scene_destroy(void* scene);
+/* Added under ABI 4, purely additive: new geometry for a resident scene whose primitives moved (DESIGN.md
+ * §13).  tri_v, tri_n and sph are the full arrays with the counts of creation (sph may be NULL when the scene
+ * has no spheres); tri_mat, the materials, the light lists and direct_rgb stay those of creation.  The
+ * topology of the trees, their leaf references and the triangle order stay too: the device rewrites the
+ * BVH-order triangle records, refits the boxes of the four- and eight-wide trees bottom-up (a leaf's box is the
+ * bound of its triangles' vertices, padded by the builder's rule taken on the new vertices) and re-quantises
+ * the four-wide nodes; the shading data (normals, frames, light vertices, the shade_fast flag) is re-packed on
+ * the host and uploaded into the existing buffers.  Every buffer, the handle, its streams and render contexts
+ * survive.  Results do not depend on the tree, so every query and render equals that of a scene created from
+ * the same arrays, bit for bit; a tree built without reference splits is also word for word the created one.
+ * References split at creation get the whole triangle's box, so the tree loosens as objects move far from the
+ * pose it was built at (DeviceScene.tree_cost tells).  The first update allocates the device copies it needs
+ * (triangle order, level lists, slot bounds, vertices: prt_scene_info's device bytes grow by them).
+ * Synchronises the device before it touches the scene and its own stream before it returns.  A NULL scene or
+ * array, a vertex, normal or sphere that is not finite, or a radius <= 0 return PRT_ERR_ARG before the device
+ * is touched: the scene then renders what it rendered before.  That promise covers argument errors only.  After
+ * PRT_ERR_HIP or PRT_ERR_OOM (an allocation of the first update, an upload or a launch failed part-way) some
+ * buffers may hold the new geometry and others the old, and the device bytes may count a copy that a later,
+ * successful update allocates again: the scene is then good for prt_scene_destroy and for another
+ * prt_scene_update that succeeds, which rewrites every buffer, and for nothing else. */
+int prt_scene_update(void* scene, const float* tri_v, const float* tri_n, const float* sph);
+/* Test and inspection hook, added with prt_scene_update: the scene's device buffer `which` copied to out
+ * (host), `bytes` its exact size, else PRT_ERR_ARG.  Layouts: prt_bvh_collapse's nodes for the two trees
+ * (NODES8: 0 bytes when the scene has no eight-wide tree), 16 f32 per quantised node, prt_bvh_export's tris,
+ * 4 f32 per triangle (normal, material bits), 24 f32 per triangle (frames), 16 f32 per emitter triangle, 4 f32
+ * per sphere.  PRT_BUF_UPDATE_MS: 5 f64, the last update's host checks and packing, uploads, triangle records,
+ * tree levels and quantiser in ms.  which | PRT_BUF_BYTES: out receives the buffer's size as one int64
+ * (bytes = 8).  PRT_BUF_UPDATE_MS and the size queries go beyond the device buffers: they answer from the
+ * handle's host state, make no device call and synchronise nothing; every other download synchronises the
+ * device first, so it sees the scene as the last render or update left it. */
+#define PRT_BUF_NODES4 0
+#define PRT_BUF_NODES4Q 1
+#define PRT_BUF_NODES8 2
+#define PRT_BUF_TRIS 3
+#define PRT_BUF_TRI_NM 4
+#define PRT_BUF_TRI_FRAME 5
+#define PRT_BUF_LIGHT_V 6
+#define PRT_BUF_SPH 7
+#define PRT_BUF_UPDATE_MS 8
+#define PRT_BUF_BYTES 0x100
+int prt_scene_download(void* scene, int which, void* out, int64_t bytes);
 
 /* ------------------------------------------------------------- render ----
  * Replaces the render() kernel of main_taichi.py:80-99 run `spp` times

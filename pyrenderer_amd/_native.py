@@ -68,6 +68,18 @@ PRT_DIAG_LANE_TABLE_WORDS = 16
 PRT_DIAG_SUSPENDED = 176
 PRT_DIAG_RESUMED = 177
 PRT_DIAG_WORDS = 192
+# prt_scene_download's buffers (include/prt.h PRT_BUF_*), and their numpy row shapes
+PRT_BUF_NODES4 = 0
+PRT_BUF_NODES4Q = 1
+PRT_BUF_NODES8 = 2
+PRT_BUF_TRIS = 3
+PRT_BUF_TRI_NM = 4
+PRT_BUF_TRI_FRAME = 5
+PRT_BUF_LIGHT_V = 6
+PRT_BUF_SPH = 7
+PRT_BUF_UPDATE_MS = 8
+PRT_BUF_BYTES = 0x100
+PRT_ERR_ARG = -1
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -96,6 +108,8 @@ EXPORTS = {
     "prt_bvh_destroy": (None, [_vp]),
     "prt_scene_create": (_i, [_i, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i32, _vp, _vp]),
     "prt_scene_info": (_i, [_vp, _vp]),
+    "prt_scene_update": (_i, [_vp, _vp, _vp, _vp]),
+    "prt_scene_download": (_i, [_vp, _i, _vp, _i64]),
     "prt_scene_kernel": (_i, [_vp, _vp]),
     "prt_launch_kernel": (_i, [_vp, _i64, _u32, _vp]),
     "prt_closest_hits": (_i, [_vp, _vp, ctypes.c_int64, _u32, _vp, _vp]),

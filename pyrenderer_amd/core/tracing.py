@@ -405,11 +405,17 @@ class TemporalAccumulator:
     reprojection.  One device, no save / load.  Geometry is static unless add() is given the frame's scene:
     the history then follows rigidly moving primitives (DESIGN.md §11 "Moving objects").  Moving lights, and
     the shading changes a moving object casts on static surfaces (its shadow, its reflection), keep their
-    history and lag behind by about 1 / alpha frames: SVGF's known limit."""
+    history and lag behind by about 1 / alpha frames: SVGF's known limit.
+
+    refit=True: a frame whose scene differs from the last one's only in its geometry updates the world this
+    accumulator built in place (World.update: the trees are refit on the device, the device scene and its
+    render contexts stay) instead of building a new world and closing the old one; the images are the same
+    bit for bit.  A scene that differs in more, and a world the caller passed in, take the rebuild."""
 
     def __init__(self, scene, *, depth, spp, seed=0, resolution=None, device=0, tile=64, world=None, nee="reference",
-                 **temporal_params):
+                 refit=False, **temporal_params):
         from .. import denoise as D
+        self.refit = bool(refit)
         unknown = sorted(set(temporal_params) - set(D.TEMPORAL_PARAMS))
         if unknown:
             raise TypeError(f"unknown temporal parameter(s) {unknown}: expected some of {D.TEMPORAL_PARAMS}")
@@ -450,9 +456,14 @@ class TemporalAccumulator:
             scene = self.scene if scene is None else scene
             # raises before anything is built or rendered
             motion = D.motion_rows(scene if self.scene is None else self.scene, scene)
+        if self._prev is not None and motion is not None:
+            # the last frame's id plane, due now after a static frame: composed while the device scene still
+            # holds that frame's pose (a refit below moves it in place)
+            self.object_ids()
         stale = None
         if scene is not None and scene is not self.scene:
-            stale, self.world, self._own_world = (self.world if self._own_world else None), None, True
+            if not self._refit_world(scene):
+                stale, self.world, self._own_world = (self.world if self._own_world else None), None, True
             self.scene = scene
         if self.world is None:
             self.world = build_world(self.scene, (self.device,))
@@ -475,6 +486,17 @@ class TemporalAccumulator:
                 ds.close()
         self.frames += 1
         return self
+
+    def _refit_world(self, scene):
+        """refit=True and a world of this accumulator's own: update it in place to `scene`; False when that is
+        not possible (the caller then rebuilds)."""
+        if not (self.refit and self._own_world and self.world is not None):
+            return False
+        try:
+            self.world.update(scene.primitives)
+        except ValueError:   # more than the geometry differs
+            return False
+        return True
 
     def object_ids(self):
         """The last frame's object-id plane, (W, H) int32 (pyrenderer_amd.denoise.object_ids): the plane the
@@ -529,12 +551,13 @@ class TemporalAccumulator:
 
 
 def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, device=0, tile=64, world=None,
-                    nee="reference", denoise="variance", scenes=None, **temporal_params):
+                    nee="reference", denoise="variance", scenes=None, refit=False, **temporal_params):
     """The frames of a camera path with temporal accumulation, (n, W, H, 3) float32: frame t is
     TemporalAccumulator.add(cameras[t]) followed by denoised() (denoise="variance", the default) or
     accumulated() (denoise=False).  Anything else is a ValueError.  scenes: None (default) is the static
     `scene`; one scene per camera makes frame t add(cameras[t], scenes[t]), the history following the
-    primitives that move between them."""
+    primitives that move between them; refit=True then refits the resident scene between frames instead of
+    rebuilding it (TemporalAccumulator's refit), same images."""
     if not ((isinstance(denoise, str) and denoise == "variance") or denoise is False):
         raise ValueError(f"denoise must be 'variance' or False, not {denoise!r}")
     cameras = list(cameras)
@@ -545,7 +568,7 @@ def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, devi
         if len(scenes) != len(cameras):
             raise ValueError(f"scenes must hold one scene per camera: {len(scenes)} for {len(cameras)} cameras")
     acc = TemporalAccumulator(scene, depth=depth, spp=spp, seed=seed, resolution=resolution, device=device, tile=tile,
-                              world=world, nee=nee, **temporal_params)
+                              world=world, nee=nee, refit=refit, **temporal_params)
     out = []
     for t, cam in enumerate(cameras):
         acc.add(cam, None if scenes is None else scenes[t])

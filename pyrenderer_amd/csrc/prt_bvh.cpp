@@ -558,19 +558,16 @@ int32_t tree_depth(const std::vector<TNode>& nodes, int32_t root) {
 
 // The build's references (B->tb / ref_tri / cen): one per triangle, several (early split clipping) for
 // triangles whose box area exceeds esc_beta x the mean (0 = off; at most 2 n_tri + 4096 in all).  Also
-// the scene's box and largest coordinate magnitude, which size the padding.
-bool make_references(const float* tri_v, int64_t n_tri, double esc_beta, Builder* B, Box* scene, float* max_abs,
-                     std::string* err) {
+// the scene's box.
+bool make_references(const float* tri_v, int64_t n_tri, double esc_beta, Builder* B, Box* scene, std::string* err) {
     std::vector<Box> tri_box((size_t)n_tri);
     double mean_area = 0.0;
     for (int64_t i = 0; i < n_tri; ++i) {
         const float* t = tri_v + 9 * i;
         Box b;
         b.grow(t); b.grow(t + 3); b.grow(t + 6);
-        for (int k = 0; k < 9; ++k) {
+        for (int k = 0; k < 9; ++k)
             if (!std::isfinite(t[k])) { *err = "non-finite vertex in triangle " + std::to_string(i); return false; }
-            *max_abs = std::max(*max_abs, std::fabs(t[k]));
-        }
         tri_box[(size_t)i] = b;
         mean_area += b.area();
         scene->grow(b);
@@ -682,6 +679,20 @@ void statistics(const Builder& B, int32_t root, BvhHost* out) {
 
 }  // namespace
 
+// Padding: ~8 ulps of the largest coordinate magnitude / extent.  Keeps the
+// slab test conservative against Moller-Trumbore accepting hit points that
+// lie a rounding error outside the triangle (axis-aligned Cornell edges).
+float bvh_pad(const float* tri_v, int64_t n_tri) {
+    Box scene;
+    float max_abs = 0.0f;
+    for (int64_t i = 0; i < 3 * n_tri; ++i) {
+        scene.grow(tri_v + 3 * i);
+        for (int k = 0; k < 3; ++k) max_abs = std::max(max_abs, std::fabs(tri_v[3 * i + k]));
+    }
+    const float extent = scene.valid() ? std::max({scene.hi[0] - scene.lo[0], scene.hi[1] - scene.lo[1], scene.hi[2] - scene.lo[2]}) : 0.0f;
+    return std::max(max_abs, extent) * 1e-6f + 1e-30f;
+}
+
 bool build_bvh(const float* tri_v, int64_t n_tri, int max_leaf, BvhHost* out, std::string* err) {
     if (max_leaf < 1 || max_leaf > kMaxLeaf) { *err = "max_leaf must be in [1, 8]"; return false; }
     if (n_tri < 0 || n_tri >= ((int64_t)1 << 27)) { *err = "triangle count out of range (< 2^27)"; return false; }
@@ -689,8 +700,7 @@ bool build_bvh(const float* tri_v, int64_t n_tri, int max_leaf, BvhHost* out, st
     B.tv = tri_v; B.max_leaf = max_leaf;
     B.knobs = read_bvh_knobs(n_tri, max_leaf);
     Box scene;
-    float max_abs = 0.0f;
-    if (!make_references(tri_v, n_tri, B.knobs.esc_beta, &B, &scene, &max_abs, err)) return false;
+    if (!make_references(tri_v, n_tri, B.knobs.esc_beta, &B, &scene, err)) return false;
     const int64_t n_ref0 = (int64_t)B.tb.size();
     // spatial splits add references up to the budget, below the 2^27 the leaf encoding addresses
     B.ref_budget = std::min<int64_t>((int64_t)((double)n_ref0 * B.knobs.budget), ((int64_t)1 << 27) - 1);
@@ -709,11 +719,7 @@ bool build_bvh(const float* tri_v, int64_t n_tri, int max_leaf, BvhHost* out, st
     // every reference sits in exactly one leaf: the leaf order is the triangle records' order
     const int64_t n_ref = (int64_t)B.order.size();
     if (n_ref != (int64_t)B.tb.size()) { *err = "internal: BVH references lost in the build"; return false; }
-    // Padding: ~8 ulps of the largest coordinate magnitude / extent.  Keeps the
-    // slab test conservative against Moller-Trumbore accepting hit points that
-    // lie a rounding error outside the triangle (axis-aligned Cornell edges).
-    const float extent = scene.valid() ? std::max({scene.hi[0] - scene.lo[0], scene.hi[1] - scene.lo[1], scene.hi[2] - scene.lo[2]}) : 0.0f;
-    out->pad = std::max(max_abs, extent) * 1e-6f + 1e-30f;
+    out->pad = bvh_pad(tri_v, n_tri);
     flatten(B, root, out->pad, out);
     statistics(B, root, out);
     if (B.knobs.verbose)

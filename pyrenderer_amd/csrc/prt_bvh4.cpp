@@ -18,7 +18,6 @@ constexpr int kNode4 = kNode4F4 * 4;  // floats of one four-wide node
 // eight-wide visit tests two groups of four boxes and pushes up to seven children, 159 (closest-hit) and
 // 129 (any-hit) VALU instructions against 77 and 69 in the pooled kernel's listing
 constexpr double visit_cost(int width) { return width == 4 ? 1.0 : 2.0; }
-constexpr int32_t kEmptyRef = 0x7FFFFFFF;   // ref of an empty slot: the traversal sentinel
 
 // The collapse's knobs, read once per collapse: the env variable through atoi / atof, then the clamp.
 struct CollapseKnobs {
@@ -261,43 +260,8 @@ void collapse_bvh8(const BvhHost& b2, Bvh8Host* out) { collapse_wide<8>(b2, out)
 
 void quantize_bvh4(const Bvh4Host& b4, float pad, std::vector<float>* out) {
     out->assign((size_t)b4.n_nodes * 16, 0.0f);
-    const double margin = 2.0 * (double)pad;
-    for (int64_t n = 0; n < b4.n_nodes; ++n) {
-        const float* f = b4.nodes.data() + (size_t)n * kNode4;
-        float* q = out->data() + (size_t)n * 16;
-        bool ok[4];
-        for (int k = 0; k < 4; ++k) ok[k] = std::isfinite(f[k]);   // empty slots hold +inf
-        uint32_t ql[3] = {0, 0, 0}, qh[3] = {0, 0, 0};
-        for (int a = 0; a < 3; ++a) {
-            double lo = INFINITY, hi = -INFINITY;
-            for (int k = 0; k < 4; ++k)
-                if (ok[k]) {
-                    lo = std::min(lo, (double)f[(2 * a) * 4 + k]);
-                    hi = std::max(hi, (double)f[(2 * a + 1) * 4 + k]);
-                }
-            if (!(lo <= hi)) { lo = 0.0; hi = 0.0; }
-            // origin rounded down to f32; grid step = the f32 at or above range / 254 (and >= 1e-30)
-            const float o = round_down_f32(lo - margin);
-            const double ext = hi + margin - (double)o;
-            const float stf = std::max(round_up_f32(ext / 254.0), (float)1e-30);
-            const double st = (double)stf;
-            q[a] = o;
-            q[3 + a] = stf;
-            for (int k = 0; k < 4; ++k) {
-                if (!ok[k]) continue;
-                double l = (double)f[(2 * a) * 4 + k], h = (double)f[(2 * a + 1) * 4 + k];
-                long ql_k = (long)std::floor((l - margin - (double)o) / st);
-                long qh_k = (long)std::ceil((h + margin - (double)o) / st);
-                ql_k = std::max(0L, std::min(255L, ql_k));
-                qh_k = std::max(0L, std::min(255L, qh_k));
-                ql[a] |= (uint32_t)ql_k << (8 * k);
-                qh[a] |= (uint32_t)qh_k << (8 * k);
-            }
-            q[6 + 2 * a] = bits<float>(ql[a]);
-            q[7 + 2 * a] = bits<float>(qh[a]);
-        }
-        for (int k = 0; k < 4; ++k) q[12 + k] = ok[k] ? f[24 + k] : bits<float>(kEmptyRef);
-    }
+    for (int64_t n = 0; n < b4.n_nodes; ++n)
+        quantize_node4(b4.nodes.data() + (size_t)n * kNode4, pad, out->data() + (size_t)n * 16);
 }
 
 }  // namespace prt

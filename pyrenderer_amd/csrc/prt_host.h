@@ -15,6 +15,7 @@
 #include "../../include/prt.h"
 #include "prt_kernels.h"
 #include "prt_plan.h"
+#include "prt_refit.h"
 
 namespace prt {
 
@@ -75,8 +76,26 @@ constexpr size_t kMaxCtx = 8;
 constexpr size_t kFaultOffset = 32;
 inline int* fault_flag(const DevBuf& work) { return (int*)((char*)work.p + kFaultOffset); }
 
+// What prt_scene_update needs of a scene beyond its device buffers: kept on the host at creation (the tree's
+// triangle order, each wide tree's nodes by level, and the arrays pack_scene reads that an update does not
+// replace), and the device copies and work buffers that the first update allocates — a scene that is never
+// updated holds none of them.
+struct RefitState {
+    std::vector<int32_t> order;               // BVH slot -> triangle
+    std::vector<int32_t> level4, level8;      // node indices by level (prt_plan.h wide_levels)
+    std::vector<int64_t> off4, off8;
+    std::vector<int32_t> tri_mat, sph_mat, light_tri, light_off;
+    std::vector<float> mat;
+    bool resident = false;                    // the device buffers below are allocated and filled
+    DevBuf d_order, d_level4, d_level8, d_bounds, d_tri_v;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    // the last update: host validation + pack, uploads, triangle records, tree levels, quantiser (ms)
+    double ms[5] = {0, 0, 0, 0, 0};
+};
+
 struct Scene {
     int device = 0;
+    RefitState refit;
     int64_t n_tri = 0, n_nodes = 0;
     int32_t depth = 0;
     int n_light = 0, n_mat = 0, cus = 0;

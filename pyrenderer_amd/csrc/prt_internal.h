@@ -16,15 +16,16 @@ namespace prt {
 //   f[3] = (bits(child L), bits(child R), 0, 0)
 // Child reference: >= 0 inner node index; < 0 leaf, v = -ref-1,
 // first = v >> 3 (index into the BVH-ordered triangle array), count = (v&7)+1.
+// (constexpr: the device refit, prt_refit.hip, decodes them too)
 constexpr int kMaxLeaf = 8;
 constexpr int kNodeF4 = 4;
 constexpr int kTriF4 = 3;  // (v0, id bits) (e1, 0) (e2, 0)
 
-inline int32_t leaf_ref(int64_t first, int count) {
+constexpr int32_t leaf_ref(int64_t first, int count) {
     return -(int32_t)(((first << 3) | (int64_t)(count - 1)) + 1);
 }
-inline int64_t leaf_first(int32_t ref) { return (-(int64_t)ref - 1) >> 3; }
-inline int leaf_count(int32_t ref) { return (int)((-(int64_t)ref - 1) & 7) + 1; }
+constexpr int64_t leaf_first(int32_t ref) { return (-(int64_t)ref - 1) >> 3; }
+constexpr int leaf_count(int32_t ref) { return (int)((-(int64_t)ref - 1) & 7) + 1; }
 
 struct BvhHost {
     std::vector<float> nodes;      // n_nodes * 16
@@ -83,5 +84,9 @@ void quantize_bvh4(const Bvh4Host& b4, float pad, std::vector<float>* out);
 // Box padding keeps the slab test conservative w.r.t. Moller-Trumbore's own
 // rounding so traversal returns exactly the brute-force closest hit.
 bool build_bvh(const float* tri_v, int64_t n_tri, int max_leaf, BvhHost* out, std::string* err);
+// The one pad rule: the absolute box padding of a scene with these (finite) vertices,
+// max(largest |coordinate|, largest extent) * 1e-6f + 1e-30f.  The builder and the refit of a resident
+// scene (prt_scene_update) both take it from the geometry they are given.
+float bvh_pad(const float* tri_v, int64_t n_tri);
 
 }  // namespace prt

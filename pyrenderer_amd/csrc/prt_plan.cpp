@@ -106,6 +106,45 @@ void pack_scene(const SceneArgs& a, PackedScene* out) {
     }
 }
 
+bool validate_update(const float* tri_v, const float* tri_n, int64_t n_tri, const float* sph, int64_t n_sph,
+                     std::string* err) {
+    if (n_tri > 0 && (!tri_v || !tri_n)) return bad(err, "bad triangle arrays");
+    if (n_sph > 0 && !sph) return bad(err, "bad sphere array");
+    for (int64_t i = 0; i < 9 * n_tri; ++i)
+        if (!std::isfinite(tri_v[i])) return bad(err, "non-finite vertex in triangle " + std::to_string(i / 9));
+    for (int64_t i = 0; i < 3 * n_tri; ++i)
+        if (!std::isfinite(tri_n[i])) return bad(err, "non-finite normal in triangle " + std::to_string(i / 3));
+    for (int64_t k = 0; k < n_sph; ++k) {
+        for (int c = 0; c < 4; ++c)
+            if (!std::isfinite(sph[4 * k + c])) return bad(err, "non-finite sphere " + std::to_string(k));
+        if (!(sph[4 * k + 3] > 0.0f)) return bad(err, "sphere radius must be > 0");
+    }
+    return true;
+}
+
+bool wide_levels(const float* nodes, int64_t n_nodes, int width, std::vector<int32_t>* list,
+                 std::vector<int64_t>* off) {
+    const int64_t stride = width == 8 ? kNode8F4 * 4 : kNode4F4 * 4;
+    std::vector<int32_t> depth((size_t)std::max<int64_t>(n_nodes, 0), 0);
+    int32_t deepest = 0;
+    for (int64_t i = 0; i < n_nodes; ++i)
+        for (int k = 0; k < width; ++k) {
+            int32_t ref;
+            std::memcpy(&ref, nodes + i * stride + 6 * width + k, 4);
+            if (ref < 0 || ref == 0x7FFFFFFF) continue;   // a leaf, an empty slot
+            if (ref <= i || ref >= n_nodes) return false;
+            depth[(size_t)ref] = depth[(size_t)i] + 1;
+            deepest = std::max(deepest, depth[(size_t)ref]);
+        }
+    off->assign((size_t)(n_nodes > 0 ? deepest + 2 : 1), 0);
+    for (int64_t i = 0; i < n_nodes; ++i) ++(*off)[(size_t)depth[(size_t)i] + 1];
+    for (size_t l = 1; l < off->size(); ++l) (*off)[l] += (*off)[l - 1];
+    list->assign((size_t)std::max<int64_t>(n_nodes, 0), 0);
+    std::vector<int64_t> at(off->begin(), off->end());
+    for (int64_t i = 0; i < n_nodes; ++i) (*list)[(size_t)at[(size_t)depth[(size_t)i]]++] = (int32_t)i;
+    return true;
+}
+
 long long env_int(const char* name, long long lo, long long hi, long long fallback) {
     const char* v = std::getenv(name);
     return v ? std::max(lo, std::min(hi, std::atoll(v))) : fallback;

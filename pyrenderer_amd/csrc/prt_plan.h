@@ -36,6 +36,17 @@ struct PackedScene {
 };
 void pack_scene(const SceneArgs& a, PackedScene* out);   // of validated arguments
 
+// prt_scene_update's argument checks on the new geometry (the counts are those of creation): NULL arrays, a
+// vertex or normal that is not finite, a sphere row that is not finite or whose radius is not > 0
+bool validate_update(const float* tri_v, const float* tri_n, int64_t n_tri, const float* sph, int64_t n_sph,
+                     std::string* err);
+// The nodes of a wide tree (prt_internal.h Bvh4Host / Bvh8Host records, `width` 4 or 8) by level, the root
+// at level 0: list = the node indices level by level, those of level l at off[l] .. off[l + 1].  emit_wide
+// numbers every child above its parent, so one forward sweep finds every depth.  false (never for a tree of
+// the library's own): a child reference that is out of range or not above its parent.
+bool wide_levels(const float* nodes, int64_t n_nodes, int width, std::vector<int32_t>* list,
+                 std::vector<int64_t>* off);
+
 // integer environment knob: `fallback` when unset, else its value clamped to [lo, hi]
 long long env_int(const char* name, long long lo, long long hi, long long fallback);
 // PRT_SPILL_LDS takes 4, 16 or 32 entries; every other value means 16

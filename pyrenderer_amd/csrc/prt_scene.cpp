@@ -1,6 +1,7 @@
 // prt_scene.cpp — the library's identity calls, host BVH handles, and a scene's life: validate, build
 // the BVH, pack, upload, query the device, read the environment knobs; plus the calls of the size-only
 // launch decisions (prt_plan.h: LDS footprints, the trace-kernel variant) for a scene (prt_host.h).
+#include <chrono>
 #include <cstdlib>
 #include <new>
 
@@ -26,6 +27,8 @@ void destroy_scene(Scene* s) {
     DeviceGuard g(s->device);
     if (!s->ctx.empty()) (void)hipDeviceSynchronize();
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->refit.ev)
+        if (e) (void)hipEventDestroy(e);
     if (s->scatter_ev) (void)hipEventDestroy(s->scatter_ev);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -106,6 +109,8 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
         s->stack4 = b4.stack_need <= 32 ? stack_variant(b4.stack_need - 1) : 0;
         s->need4 = b4.stack_need;
         if (int rc = upload(s->nodes4, b4.nodes.data(), sizeof(float) * b4.nodes.size(), total)) return rc;
+        if (!wide_levels(b4.nodes.data(), b4.n_nodes, 4, &s->refit.level4, &s->refit.off4))
+            return fail(PRT_ERR_INTERNAL, "internal: BVH4 child not numbered above its parent");
         std::vector<float> q4;
         quantize_bvh4(b4, bvh.pad, &q4);
         s->n_node4q_f4 = (int64_t)q4.size() / 4;
@@ -121,9 +126,18 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
         s->n_node8_f4 = (int64_t)b8.nodes.size() / 4;
         s->need8 = b8.stack_need;
         s->stack8 = b8.stack_need <= 32 ? stack_variant(b8.stack_need - 1) : 0;
+        if (!wide_levels(b8.nodes.data(), b8.n_nodes, 8, &s->refit.level8, &s->refit.off8))
+            return fail(PRT_ERR_INTERNAL, "internal: BVH8 child not numbered above its parent");
         if (int rc = upload(s->nodes8, b8.nodes.data(), sizeof(float) * b8.nodes.size(), total)) return rc;
         s->lds_width = lds_width(sizes_of(s, 8), s->need8, (int)env_int("PRT_LDS_WIDTH", 0, 8, 0));
     }
+    // what an update re-packs with and refits along (prt_host.h RefitState), host copies only
+    s->refit.order = bvh.order;
+    s->refit.tri_mat.assign(a.tri_mat, a.tri_mat + a.n_tri);
+    s->refit.sph_mat.assign(a.sph_mat, a.sph_mat + a.n_sph);
+    s->refit.mat.assign(a.mat, a.mat + 8 * (size_t)a.n_mat);
+    s->refit.light_off.assign(a.light_off, a.light_off + a.n_light + 1);
+    s->refit.light_tri.assign(a.light_tri, a.light_tri + a.light_off[a.n_light]);
     s->n_sph = a.n_sph;
     s->plain = pk.plain;
     s->shade_fast = pk.shade_fast;
@@ -160,6 +174,72 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
             s->chunk_bytes = std::max<size_t>((size_t)1 << 28, std::min(s->chunk_bytes, free_b / 4));
     }
+    return PRT_OK;
+}
+
+// first update: the device copies of the tree's order and level lists, the slot bounds and the
+// original-order vertices
+int refit_resident(Scene* s) {
+    RefitState& r = s->refit;
+    if (r.resident) return PRT_OK;
+    size_t* total = &s->device_bytes;
+    if (int rc = upload(r.d_order, r.order.data(), sizeof(int32_t) * r.order.size(), total)) return rc;
+    if (int rc = upload(r.d_level4, r.level4.data(), sizeof(int32_t) * r.level4.size(), total)) return rc;
+    if (int rc = upload(r.d_level8, r.level8.data(), sizeof(int32_t) * r.level8.size(), total)) return rc;
+    HIP_TRY(r.d_bounds.ensure(std::max<size_t>(sizeof(float) * 6 * r.order.size(), 16)));
+    HIP_TRY(r.d_tri_v.ensure(std::max<size_t>(sizeof(float) * 9 * (size_t)s->n_tri, 16)));
+    *total += r.d_bounds.bytes + r.d_tri_v.bytes;
+    for (hipEvent_t& e : r.ev) HIP_TRY(hipEventCreate(&e));
+    r.resident = true;
+    return PRT_OK;
+}
+
+int put(DevBuf& b, const void* host, size_t bytes, hipStream_t stream) {
+    if (bytes > b.bytes) return fail(PRT_ERR_INTERNAL, "internal: update larger than the scene's buffer");
+    if (bytes) HIP_TRY(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, stream));
+    return PRT_OK;
+}
+
+// one tree's levels, deepest first, one launch each
+int refit_tree(int width, DevBuf& nodes, const DevBuf& level, const std::vector<int64_t>& off, const DevBuf& bounds,
+               float pad, hipStream_t stream) {
+    for (size_t l = off.size() - 1; l-- > 0;)
+        HIP_TRY(launch_refit_level(width, (float*)nodes.p, (const int32_t*)level.p + off[l], off[l + 1] - off[l],
+                                   (const float*)bounds.p, pad, stream));
+    return PRT_OK;
+}
+
+// device half of prt_scene_update (validated arguments, packed shading data)
+int update_scene(Scene* s, const float* tri_v, const float* sph, const PackedScene& pk, float pad) {
+    RefitState& r = s->refit;
+    // no render of this scene may be in flight on any of its streams while its buffers change
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = refit_resident(s)) return rc;
+    hipStream_t st = s->stream;
+    HIP_TRY(hipEventRecord(r.ev[0], st));
+    if (int rc = put(r.d_tri_v, tri_v, sizeof(float) * 9 * (size_t)s->n_tri, st)) return rc;
+    if (int rc = put(s->tri_nm, pk.tri_nm.data(), sizeof(float) * pk.tri_nm.size(), st)) return rc;
+    if (int rc = put(s->tri_frame, pk.tri_frame.data(), sizeof(float) * pk.tri_frame.size(), st)) return rc;
+    if (int rc = put(s->light_v, pk.light_v.data(), sizeof(float) * pk.light_v.size(), st)) return rc;
+    if (int rc = put(s->sph, sph, sizeof(float) * 4 * (size_t)s->n_sph, st)) return rc;
+    HIP_TRY(hipEventRecord(r.ev[1], st));
+    HIP_TRY(launch_refit_tris((const float*)r.d_tri_v.p, (const int32_t*)r.d_order.p, (int64_t)r.order.size(),
+                              (float4*)s->tris.p, (float*)r.d_bounds.p, st));
+    HIP_TRY(hipEventRecord(r.ev[2], st));
+    if (int rc = refit_tree(4, s->nodes4, r.d_level4, r.off4, r.d_bounds, pad, st)) return rc;
+    if (s->n_node8_f4 > 0)
+        if (int rc = refit_tree(8, s->nodes8, r.d_level8, r.off8, r.d_bounds, pad, st)) return rc;
+    HIP_TRY(hipEventRecord(r.ev[3], st));
+    HIP_TRY(launch_refit_quantize((const float*)s->nodes4.p, s->n_node4_f4 / kNode4F4, pad, (float*)s->nodes4q.p, st));
+    HIP_TRY(hipEventRecord(r.ev[4], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 4; ++k) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
+        r.ms[k + 1] = ms;
+    }
+    s->shade_fast = pk.shade_fast;
+    s->blocks_per_cu = variant_occ(s, launch_variant(s, 0), false);
     return PRT_OK;
 }
 
@@ -285,6 +365,63 @@ int prt_scene_info(void* scene, int64_t* info8) {
 }
 
 void prt_scene_destroy(void* scene) { destroy_scene((Scene*)scene); }
+
+int prt_scene_update(void* scene, const float* tri_v, const float* tri_n, const float* sph) {
+    auto* s = (Scene*)scene;
+    if (!s) return fail(PRT_ERR_ARG, "scene is NULL");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string err;
+    if (!validate_update(tri_v, tri_n, s->n_tri, sph, s->n_sph, &err)) return fail(PRT_ERR_ARG, err);
+    RefitState& r = s->refit;
+    const SceneArgs a{tri_v, tri_n, r.tri_mat.data(), s->n_tri, sph, r.sph_mat.data(), s->n_sph, r.mat.data(), s->n_mat,
+                      r.light_tri.data(), r.light_off.data(), s->n_light};
+    PackedScene pk;
+    float pad = 0.0f;
+    try {
+        pack_scene(a, &pk);
+        pad = bvh_pad(tri_v, s->n_tri);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_ERR_OOM, "host allocation failed during the scene update");
+    }
+    r.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    DeviceGuard g(s->device);
+    return update_scene(s, tri_v, sph, pk, pad);
+}
+
+int prt_scene_download(void* scene, int which, void* out, int64_t bytes) {
+    auto* s = (Scene*)scene;
+    if (!s || !out) return fail(PRT_ERR_ARG, "NULL argument");
+    const bool ask = (which & PRT_BUF_BYTES) != 0;
+    const DevBuf* b = nullptr;
+    int64_t have = 0;
+    switch (which & ~PRT_BUF_BYTES) {
+        case PRT_BUF_NODES4: b = &s->nodes4; have = 16 * s->n_node4_f4; break;
+        case PRT_BUF_NODES4Q: b = &s->nodes4q; have = 16 * s->n_node4q_f4; break;
+        case PRT_BUF_NODES8: b = &s->nodes8; have = 16 * s->n_node8_f4; break;
+        case PRT_BUF_TRIS: b = &s->tris; have = 16 * s->n_tri_f4; break;
+        case PRT_BUF_TRI_NM: b = &s->tri_nm; have = 16 * std::max<int64_t>(s->n_tri, 1); break;
+        case PRT_BUF_TRI_FRAME: b = &s->tri_frame; have = 96 * std::max<int64_t>(s->n_tri, 1); break;
+        case PRT_BUF_LIGHT_V: b = &s->light_v; have = 64 * (int64_t)s->n_lt; break;
+        case PRT_BUF_SPH: b = &s->sph; have = 16 * s->n_sph; break;
+        case PRT_BUF_UPDATE_MS: have = (int64_t)sizeof(s->refit.ms); break;
+        default: return fail(PRT_ERR_ARG, "unknown buffer");
+    }
+    if (ask) {
+        if (bytes != (int64_t)sizeof(int64_t)) return fail(PRT_ERR_ARG, "a size query writes one int64");
+        std::memcpy(out, &have, sizeof(int64_t));
+        return PRT_OK;
+    }
+    if (bytes != have) return fail(PRT_ERR_ARG, "buffer holds " + std::to_string(have) + " bytes, not " + std::to_string(bytes));
+    if (!b) {
+        std::memcpy(out, s->refit.ms, sizeof(s->refit.ms));
+        return PRT_OK;
+    }
+    if ((size_t)have > b->bytes) return fail(PRT_ERR_INTERNAL, "internal: buffer shorter than its contents");
+    DeviceGuard g(s->device);
+    HIP_TRY(hipDeviceSynchronize());
+    if (have) HIP_TRY(hipMemcpy(out, b->p, (size_t)have, hipMemcpyDeviceToHost));
+    return PRT_OK;
+}
 
 int prt_scene_kernel(void* scene, int32_t* out4) { return prt_launch_kernel(scene, INT64_MAX, 0, out4); }
 

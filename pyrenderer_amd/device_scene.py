@@ -96,10 +96,61 @@ class DeviceScene:
                                    flat.sph.shape[0], N.ptr(flat.mat), flat.mat.shape[0], N.ptr(flat.light_tri),
                                    N.ptr(flat.light_off), flat.n_light, N.ptr(flat.direct_rgb), ctypes.byref(h)))
         self.h = h
+        self._read_info()
+
+    def _read_info(self):
         info = np.zeros(8, np.int64)
-        N.check(L.prt_scene_info(self.h, N.ptr(info)))
+        N.check(N.lib().prt_scene_info(self.h, N.ptr(info)))
         (self.device, self.n_tri, self.n_nodes, self.bvh_depth, self.stack, self.device_bytes, self.blocks_per_cu,
          self.cus) = (int(v) for v in info)
+
+    # prt_scene_download's buffers: name -> (PRT_BUF_*, dtype, floats per row)
+    BUFFERS = {"nodes4": (N.PRT_BUF_NODES4, np.float32, 32), "nodes4q": (N.PRT_BUF_NODES4Q, np.float32, 16),
+               "nodes8": (N.PRT_BUF_NODES8, np.float32, 56), "tris": (N.PRT_BUF_TRIS, np.float32, 12),
+               "tri_nm": (N.PRT_BUF_TRI_NM, np.float32, 4), "tri_frame": (N.PRT_BUF_TRI_FRAME, np.float32, 24),
+               "light_v": (N.PRT_BUF_LIGHT_V, np.float32, 16), "sph": (N.PRT_BUF_SPH, np.float32, 4),
+               "update_ms": (N.PRT_BUF_UPDATE_MS, np.float64, 5)}
+
+    def check_compatible(self, flat):
+        """ValueError unless `flat` is this scene's with only its geometry moved: the same triangle and sphere
+        counts, tri_mat, mat, sph_mat, light_tri and light_off (what update() keeps from creation)."""
+        old = self.flat
+        if flat.n_tri != old.n_tri or flat.sph.shape[0] != old.sph.shape[0]:
+            raise ValueError(f"update() keeps the primitive counts: {flat.n_tri} triangles and {flat.sph.shape[0]} "
+                             f"spheres for a scene of {old.n_tri} and {old.sph.shape[0]}")
+        for k in ("tri_mat", "mat", "sph_mat", "light_tri", "light_off"):
+            a, b = getattr(flat, k), getattr(old, k)
+            if a.shape != b.shape or a.tobytes() != b.tobytes():
+                raise ValueError(f"update() moves geometry only: {k} differs from the scene's")
+
+    def update(self, flat):
+        """prt_scene_update: the scene's primitives moved to `flat`'s tri_v, tri_n and sph.  The trees are refit
+        on the device; the handle, its buffers and render contexts stay.  Everything else of
+        `flat` must be the scene's (ValueError)."""
+        self.check_compatible(flat)
+        sph = flat.sph if flat.sph.shape[0] else None
+        N.check(N.lib().prt_scene_update(self.h, N.ptr(flat.tri_v), N.ptr(flat.tri_n), N.ptr(sph)))
+        self.flat = flat
+        self._read_info()     # the first update allocates its device copies: device_bytes grows by them
+        return self
+
+    def download(self, name):
+        """prt_scene_download: the device buffer `name` (one of BUFFERS) as a (rows, n) array in the layout
+        include/prt.h gives; "update_ms" is the last update's five times."""
+        which, dtype, row = self.BUFFERS[name]
+        size = np.zeros(1, np.int64)
+        N.check(N.lib().prt_scene_download(self.h, which | N.PRT_BUF_BYTES, N.ptr(size), 8))
+        out = np.zeros((int(size[0]) // (row * np.dtype(dtype).itemsize), row), dtype)
+        N.check(N.lib().prt_scene_download(self.h, which, N.ptr(out), out.nbytes))
+        return out
+
+    def tree_cost(self):
+        """Sum of the surface areas of the BVH4's child boxes, in float64 from the downloaded nodes.  Its ratio
+        to the value after creation says how far updates have loosened the tree: time to rebuild."""
+        n = self.download("nodes4").astype(np.float64)
+        ext = [np.where(n[:, 8 * a + 4:8 * a + 8] >= n[:, 8 * a:8 * a + 4],
+                        n[:, 8 * a + 4:8 * a + 8] - n[:, 8 * a:8 * a + 4], 0.0) for a in range(3)]
+        return float(2.0 * (ext[0] * ext[1] + ext[1] * ext[2] + ext[2] * ext[0]).sum())
 
     def close(self):
         if getattr(self, "h", None):

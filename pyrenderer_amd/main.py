@@ -85,6 +85,9 @@ def parse(argv=None):
                     help="with --frames: turn primitive PRIM (its index in the scene) by DEG degrees per frame about "
                          "the vertical axis through the centre of its bounding box; with --temporal the history "
                          "follows it (per-object motion and an object-id test); usable with --orbit 0")
+    ap.add_argument("--refit", action="store_true",
+                    help="with --frames and --spin: refit the resident scene's BVH on the GPU between frames instead "
+                         "of building a new scene per frame (same images)")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
                     help="adaptive sampling: render in batches of --batch-spp and stop every 64 x 64 tile once the "
                          "relative standard error of its pixels' demodulated luminance is at most TARGET; needs "
@@ -125,8 +128,11 @@ def parse(argv=None):
             ap.error(f"--spin takes a primitive index and degrees per frame, not {args.spin[0]!r} {args.spin[1]!r}")
         if args.spin[0] < 0 or not np.isfinite(args.spin[1]):
             ap.error(f"--spin needs a primitive index >= 0 and finite degrees, not {args.spin[0]} {args.spin[1]}")
+    if args.refit and args.spin is None:
+        ap.error("--refit refits the scene that --spin moves: it needs --frames N --spin PRIM DEG")
     if not args.frames:
-        for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal), ("--spin", args.spin)):
+        for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal), ("--spin", args.spin),
+                            ("--refit", args.refit)):
             if given:
                 ap.error(f"{flag} needs --frames N")
     else:
@@ -225,12 +231,14 @@ def render_frames(args, scene, camera, W, H):
             scenes = spun(scene, args.spin[0], args.spin[1], args.frames)
         except ValueError as e:
             raise SystemExit(f"--spin: {e}")
-    world = build_world(scene, (args.devices[0],))
+    # --refit: one world of the sequence's own, updated in place (the accumulator builds its own)
+    refit = args.refit and scenes is not None   # parse() refuses --refit without --spin
+    world = None if refit and args.temporal else build_world(scene, (args.devices[0],))
     it = D.ITERATIONS if args.denoise_iterations is None else args.denoise_iterations
     acc = None
     if args.temporal:
         acc = TemporalAccumulator(scene, depth=args.depth, spp=args.samples, seed=args.seed, resolution=(W, H),
-                                  device=args.devices[0], world=world, nee=args.nee)
+                                  device=args.devices[0], world=world, nee=args.nee, refit=refit)
     mean = None
     for t in range(args.frames):
         cam = orbit(camera, t * args.orbit)
@@ -239,7 +247,9 @@ def render_frames(args, scene, camera, W, H):
             acc.add(cam, None if scenes is None else scenes[t])
             mean = acc.denoised(iterations=it) if args.denoise else acc.accumulated()
         else:
-            if scenes is not None and t > 0:   # every frame stands alone, in its own world
+            if refit and t > 0:
+                world.update(scenes[t].primitives)
+            elif scenes is not None and t > 0:   # every frame stands alone, in its own world
                 for ds in world.device_scenes.values():
                     ds.close()
                 world = build_world(scenes[t], (args.devices[0],))

@@ -39,6 +39,23 @@ class World:
                 self.device_scenes[d] = DeviceScene(self.flat, d)
         return self
 
+    def update(self, primitives):
+        """The committed world's primitives moved: `primitives` are the same ones in the same order with new
+        poses (e.g. pyrenderer_amd.scenes.moved(...).primitives).  Re-flattens and refits every device scene in
+        place (DeviceScene.update); a ValueError (raised before any device scene changes) when anything but
+        the geometry differs."""
+        primitives = list(primitives)
+        flat = flatten_scene(_PrimList(primitives))
+        for ds in self.device_scenes.values():
+            ds.check_compatible(flat)
+        for ds in self.device_scenes.values():
+            ds.update(flat)
+        self.primitives, self.lights = [], []
+        for p in primitives:
+            self.add(p)
+        self.flat = flat
+        return self
+
     def device_scene(self, device=0):
         if device not in self.device_scenes:
             self.commit(devices=(device,))

@@ -49,7 +49,8 @@ extern "C" {
  * accumulation (prt_temporal_accumulate*, prt_denoise_var_mixed*), then the two of adaptive sampling
  * (prt_adaptive_update*), then the two of temporal accumulation across moving objects
  * (prt_temporal_accumulate_motion*), then the refit of a resident scene (prt_scene_update) and the read-back
- * of a scene's device buffers (prt_scene_download). */
+ * of a scene's device buffers (prt_scene_download), then the rebuild of a resident scene's trees on the device
+ * (prt_scene_rebuild, prt_scene_rebuild_info). */
 #define PRT_ABI_VERSION 4
 
 #define PRT_OK 0
@@ -185,6 +186,31 @@ int prt_scene_update(void* scene, const float* tri_v, const float* tri_n, const 
 #define PRT_BUF_UPDATE_MS 8
 #define PRT_BUF_BYTES 0x100
 int prt_scene_download(void* scene, int which, void* out, int64_t bytes);
+/* Added under ABI 4, purely additive: the trees of a resident scene built again on the device, for a scene whose
+ * refit tree has loosened.  Arguments, checks and the promise about a refused call are
+ * prt_scene_update's; a scene of 2^28 triangles or more is refused too (PRT_ERR_ARG).  The tree is a linear BVH
+ * (Karras 2012): per triangle the centroid (lo + hi) * 0.5f of its vertex bounds; per axis the 10-bit cell
+ * min((int)((c - cmin) / (cmax - cmin) * 1024.0f), 1023) within the centroids' bounds, all in f32, 0 on an axis
+ * of zero extent; the 30-bit Morton code with x the most significant bit of each triple; a stable sort by code
+ * gives the new slot order, one slot per triangle (no reference is split); the keys code << 32 | slot are
+ * distinct, and the binary radix tree over them splits a range at the highest bit in which its first and last
+ * key differ.  A wide node over a range takes as children the ranges reached after log2(width) binary splits, a
+ * range of at most PRT_MAX_LEAF triangles (as read when the scene was created, default 4) stopping as a leaf;
+ * children stand in slot order, empty slots after them; the nodes are numbered breadth-first, level by level.
+ * Boxes, padding and the quantised records are prt_scene_update's.  Written: the slot order, the triangle
+ * records, the four-wide tree (f32 and quantised) and, for a scene whose new sizes fit LDS, the eight-wide one
+ * with the width rule taken again (else the scene has none); the stack needs, the stack variants and the
+ * default kernel follow the new trees (a four-wide tree needing more than 32 entries takes the spill variants,
+ * as at creation), prt_scene_info's n_nodes and depth become the four-wide tree's node count and levels - 1.
+ * A later prt_scene_update refits the new trees.  Buffers grow only when a tree needs more room than they have;
+ * the first rebuild allocates the build's work arrays (about 64 bytes per triangle), a second rebuild of the
+ * same scene nothing.  Handle, streams and render contexts survive; synchronises as prt_scene_update does. */
+int prt_scene_rebuild(void* scene, const float* tri_v, const float* tri_n, const float* sph);
+/* The last rebuild's report (PRT_ERR_ARG before the first): info8 = four-wide nodes, depth (levels - 1),
+ * worst-case stack entries; eight-wide nodes (0: none), depth, stack entries; the LDS kernels' width; slots.
+ * ms8 = host checks and packing, uploads, codes, sort, binary tree, wide emission (both widths, with one count
+ * read back per level), triangle records and boxes, quantiser.  Either may be NULL. */
+int prt_scene_rebuild_info(void* scene, int64_t* info8, double* ms8);
 
 /* ------------------------------------------------------------- render ----
  * Replaces the render() kernel of main_taichi.py:80-99 run `spp` times

@@ -110,6 +110,8 @@ EXPORTS = {
     "prt_scene_info": (_i, [_vp, _vp]),
     "prt_scene_update": (_i, [_vp, _vp, _vp, _vp]),
     "prt_scene_download": (_i, [_vp, _i, _vp, _i64]),
+    "prt_scene_rebuild": (_i, [_vp, _vp, _vp, _vp]),
+    "prt_scene_rebuild_info": (_i, [_vp, _vp, _vp]),
     "prt_scene_kernel": (_i, [_vp, _vp]),
     "prt_launch_kernel": (_i, [_vp, _i64, _u32, _vp]),
     "prt_closest_hits": (_i, [_vp, _vp, ctypes.c_int64, _u32, _vp, _vp]),

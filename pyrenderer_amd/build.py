@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libprt.so")
 SOURCES = ["prt_kernels.hip", "prt_plan.cpp", "prt_scene.cpp", "prt_capi.cpp", "prt_multi.cpp", "prt_bvh.cpp",
-           "prt_bvh4.cpp", "prt_trace_pool.hip", "prt_refit.hip"]
+           "prt_bvh4.cpp", "prt_trace_pool.hip", "prt_refit.hip", "prt_lbvh.hip"]
 # per-unit extra flags: the pooled-shadow kernel is register-allocated with LLVM's AMDGPU
 # pressure trackers (4 instead of 39 spilled VGPRs at 7 waves/SIMD; prt_trace_pool.hip)
 UNIT_FLAGS = {"prt_trace_pool.hip": ["-mllvm", "--amdgpu-use-amdgpu-trackers"]}
@@ -32,7 +32,7 @@ TRACE_SETS = [(s, t) for s in (4, 10, 16, 32) for t in (0, 1)]
 # the two trace kernels, the variant dispatch); prt_host.h / prt_plan.h are the host units'; prt_lds_layout.h
 # and prt_variant_table.h (no HIP include) are read by both sides
 HEADERS = ["prt_kernels.h", "prt_internal.h", "prt_bvh_util.h", "prt_host.h", "prt_plan.h", "prt_device.h", "prt_math.h", "prt_traverse.h", "prt_shade.h",
-           "prt_trace.h", "prt_pool.h", "prt_variants.h", "prt_lds_layout.h", "prt_variant_table.h", "prt_refit.h"]
+           "prt_trace.h", "prt_pool.h", "prt_variants.h", "prt_lds_layout.h", "prt_variant_table.h", "prt_refit.h", "prt_lbvh.h"]
 # the denoiser: units of their own, compiled with the same FLAGS and linked into
 # libprt.so.  They include none of HEADERS and nothing above includes theirs, so they cannot change
 # the trace kernels' code: they are dependencies of the build (_stale) but NOT part of kernel_sha(),

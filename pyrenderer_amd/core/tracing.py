@@ -410,12 +410,21 @@ class TemporalAccumulator:
     refit=True: a frame whose scene differs from the last one's only in its geometry updates the world this
     accumulator built in place (World.update: the trees are refit on the device, the device scene and its
     render contexts stay) instead of building a new world and closing the old one; the images are the same
-    bit for bit.  A scene that differs in more, and a world the caller passed in, take the rebuild."""
+    bit for bit.  A scene that differs in more, and a world the caller passed in, take the rebuild.
+
+    rebuild_ratio (with refit=True only, else a ValueError): World.update's, a number r that has the resident
+    scene's trees built again on the GPU once refits have raised tree_cost() above r times its value at the
+    last build; None (default) only ever refits."""
 
     def __init__(self, scene, *, depth, spp, seed=0, resolution=None, device=0, tile=64, world=None, nee="reference",
-                 refit=False, **temporal_params):
+                 refit=False, rebuild_ratio=None, **temporal_params):
         from .. import denoise as D
         self.refit = bool(refit)
+        if rebuild_ratio is not None and not self.refit:
+            raise ValueError("rebuild_ratio rebuilds the scene that refit=True keeps resident: it needs refit=True")
+        if rebuild_ratio is not None and not (isinstance(rebuild_ratio, (int, float)) and rebuild_ratio > 0):
+            raise ValueError(f"rebuild_ratio must be a number > 0 or None, not {rebuild_ratio!r}")
+        self.rebuild_ratio = rebuild_ratio
         unknown = sorted(set(temporal_params) - set(D.TEMPORAL_PARAMS))
         if unknown:
             raise TypeError(f"unknown temporal parameter(s) {unknown}: expected some of {D.TEMPORAL_PARAMS}")
@@ -493,7 +502,7 @@ class TemporalAccumulator:
         if not (self.refit and self._own_world and self.world is not None):
             return False
         try:
-            self.world.update(scene.primitives)
+            self.world.update(scene.primitives, rebuild_ratio=self.rebuild_ratio)
         except ValueError:   # more than the geometry differs
             return False
         return True
@@ -551,13 +560,15 @@ class TemporalAccumulator:
 
 
 def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, device=0, tile=64, world=None,
-                    nee="reference", denoise="variance", scenes=None, refit=False, **temporal_params):
+                    nee="reference", denoise="variance", scenes=None, refit=False, rebuild_ratio=None,
+                    **temporal_params):
     """The frames of a camera path with temporal accumulation, (n, W, H, 3) float32: frame t is
     TemporalAccumulator.add(cameras[t]) followed by denoised() (denoise="variance", the default) or
     accumulated() (denoise=False).  Anything else is a ValueError.  scenes: None (default) is the static
     `scene`; one scene per camera makes frame t add(cameras[t], scenes[t]), the history following the
     primitives that move between them; refit=True then refits the resident scene between frames instead of
-    rebuilding it (TemporalAccumulator's refit), same images."""
+    rebuilding it (TemporalAccumulator's refit), same images, and rebuild_ratio= (with refit=True only) has its
+    trees built again on the GPU once the refits have loosened them that far (TemporalAccumulator's)."""
     if not ((isinstance(denoise, str) and denoise == "variance") or denoise is False):
         raise ValueError(f"denoise must be 'variance' or False, not {denoise!r}")
     cameras = list(cameras)
@@ -568,7 +579,7 @@ def render_sequence(scene, cameras, *, spp, depth, seed=0, resolution=None, devi
         if len(scenes) != len(cameras):
             raise ValueError(f"scenes must hold one scene per camera: {len(scenes)} for {len(cameras)} cameras")
     acc = TemporalAccumulator(scene, depth=depth, spp=spp, seed=seed, resolution=resolution, device=device, tile=tile,
-                              world=world, nee=nee, refit=refit, **temporal_params)
+                              world=world, nee=nee, refit=refit, rebuild_ratio=rebuild_ratio, **temporal_params)
     out = []
     for t, cam in enumerate(cameras):
         acc.add(cam, None if scenes is None else scenes[t])

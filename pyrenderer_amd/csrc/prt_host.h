@@ -14,6 +14,7 @@
 
 #include "../../include/prt.h"
 #include "prt_kernels.h"
+#include "prt_lbvh.h"
 #include "prt_plan.h"
 #include "prt_refit.h"
 
@@ -93,9 +94,26 @@ struct RefitState {
     double ms[5] = {0, 0, 0, 0, 0};
 };
 
+// What prt_scene_rebuild keeps between calls: the device build's work arrays (prt_plan.h lbvh_scratch), which
+// the first rebuild allocates and a later one of the same scene finds large enough, and the last build's
+// report (include/prt.h prt_scene_rebuild_info).
+struct RebuildState {
+    DevBuf cen, cbox, codes, ids, codes_sorted, keys, split, items, child0, cnt, off, max_anc, temp;
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // host validation + pack, uploads, codes, sort, binary tree, wide emission (both widths, with the per-level
+    // read-backs), triangle records + boxes, quantiser (ms)
+    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // four-wide nodes, depth, stack need; eight-wide nodes (0: none), depth, stack need; LDS width; slots
+    int64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t count = 0;                        // rebuilds so far
+};
+
 struct Scene {
     int device = 0;
     RefitState refit;
+    RebuildState rebuild;
+    int max_leaf = 4;                // env PRT_MAX_LEAF as read at creation: a rebuild's leaves hold as many
+    int lds_width_knob = 0;          // env PRT_LDS_WIDTH as read at creation (prt_plan.h lds_width)
     int64_t n_tri = 0, n_nodes = 0;
     int32_t depth = 0;
     int n_light = 0, n_mat = 0, cus = 0;

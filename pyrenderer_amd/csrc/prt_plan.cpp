@@ -145,6 +145,29 @@ bool wide_levels(const float* nodes, int64_t n_nodes, int width, std::vector<int
     return true;
 }
 
+LbvhScratch lbvh_scratch(int64_t n) {
+    const size_t m = (size_t)std::max<int64_t>(n, 1), cap = (size_t)lbvh_node_capacity(n);
+    LbvhScratch z;
+    z.cen = std::max<size_t>(sizeof(float) * 3 * m, 16);      // centroids
+    z.word = std::max<size_t>(sizeof(int32_t) * m, 16);       // codes, ids, sorted codes, splits, first children
+    z.key = std::max<size_t>(sizeof(uint64_t) * m, 16);       // sort keys
+    z.item = std::max<size_t>(16 * cap, 16);                  // one LbvhItem per node
+    z.count = sizeof(int32_t) * (m / 2 + 2);                  // a level's counts and their scan, one word over
+    return z;
+}
+
+bool LbvhLevels::push(int64_t count, int64_t capacity, int64_t widest) {
+    if (count < 0 || count > widest || count > capacity - n_nodes()) return false;
+    off.push_back(n_nodes() + count);
+    return true;
+}
+
+std::vector<int32_t> iota_list(int64_t n_nodes) {
+    std::vector<int32_t> v((size_t)std::max<int64_t>(n_nodes, 0));
+    for (size_t i = 0; i < v.size(); ++i) v[i] = (int32_t)i;
+    return v;
+}
+
 long long env_int(const char* name, long long lo, long long hi, long long fallback) {
     const char* v = std::getenv(name);
     return v ? std::max(lo, std::min(hi, std::atoll(v))) : fallback;

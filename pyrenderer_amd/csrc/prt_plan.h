@@ -47,6 +47,31 @@ bool validate_update(const float* tri_v, const float* tri_n, int64_t n_tri, cons
 bool wide_levels(const float* nodes, int64_t n_nodes, int width, std::vector<int32_t>* list,
                  std::vector<int64_t>* off);
 
+// ---- the host bookkeeping of a device build (prt_scene_rebuild; prt_lbvh.h)
+// slots a device build accepts: leaf_ref addresses first < 2^28
+constexpr int64_t kLbvhMaxSlots = (int64_t)1 << 28;
+// Nodes a wide tree over n slots can have at the most, the room its item and node arrays get before the tree
+// is known: every node but a leaf-only root covers a distinct range of two slots or more, and such ranges,
+// nested or disjoint, number at most n - 1.
+inline int64_t lbvh_node_capacity(int64_t n) { return n > 1 ? n - 1 : 1; }
+// bytes of the build's work arrays at n slots (prt_host.h RebuildState), 16 at the least each
+struct LbvhScratch { size_t cen, word, key, item, count; };
+LbvhScratch lbvh_scratch(int64_t n);
+// A tree numbered breadth-first as it is emitted: off[l] .. off[l + 1] are the nodes of level l.
+struct LbvhLevels {
+    std::vector<int64_t> off{0};
+    int64_t n_nodes() const { return off.back(); }
+    int depth() const { return (int)off.size() - 2; }          // levels - 1; -1 before the root's level
+    // the next level holds `count` nodes (the inner children of the level before, one for the root); false: the
+    // count is negative or above `widest`, or the tree would outgrow `capacity` nodes
+    bool push(int64_t count, int64_t capacity, int64_t widest);
+};
+// emit_wide's rule: the sentinel, the ancestors' entries of the deepest node, and the width - 1 slots a visit
+// writes above the top
+inline int wide_stack_need(int max_anc, int width) { return 1 + max_anc + (width - 1); }
+// the level list of such a tree: 0, 1, ..., n_nodes - 1
+std::vector<int32_t> iota_list(int64_t n_nodes);
+
 // integer environment knob: `fallback` when unset, else its value clamped to [lo, hi]
 long long env_int(const char* name, long long lo, long long hi, long long fallback);
 // PRT_SPILL_LDS takes 4, 16 or 32 entries; every other value means 16

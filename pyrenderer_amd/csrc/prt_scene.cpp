@@ -29,6 +29,8 @@ void destroy_scene(Scene* s) {
     for (hipEvent_t e : s->ev) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->refit.ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->rebuild.ev)
+        if (e) (void)hipEventDestroy(e);
     if (s->scatter_ev) (void)hipEventDestroy(s->scatter_ev);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -120,6 +122,7 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
     s->n_tri_f4 = (int64_t)bvh.tris.size() / 4;
     // LDS-resident scenes also get the eight-wide tree; the width rule (prt_plan.h lds_width) says which of
     // the two their LDS reference kernels traverse
+    s->lds_width_knob = (int)env_int("PRT_LDS_WIDTH", 0, 8, 0);
     if (lds_fits(sizes_of(s, 4))) {
         Bvh8Host b8;
         collapse_bvh8(bvh, &b8);
@@ -129,7 +132,7 @@ int fill_scene(Scene* s, const SceneArgs& a, const BvhHost& bvh, const PackedSce
         if (!wide_levels(b8.nodes.data(), b8.n_nodes, 8, &s->refit.level8, &s->refit.off8))
             return fail(PRT_ERR_INTERNAL, "internal: BVH8 child not numbered above its parent");
         if (int rc = upload(s->nodes8, b8.nodes.data(), sizeof(float) * b8.nodes.size(), total)) return rc;
-        s->lds_width = lds_width(sizes_of(s, 8), s->need8, (int)env_int("PRT_LDS_WIDTH", 0, 8, 0));
+        s->lds_width = lds_width(sizes_of(s, 8), s->need8, s->lds_width_knob);
     }
     // what an update re-packs with and refits along (prt_host.h RefitState), host copies only
     s->refit.order = bvh.order;
@@ -243,6 +246,147 @@ int update_scene(Scene* s, const float* tri_v, const float* sph, const PackedSce
     return PRT_OK;
 }
 
+// a buffer that grows only when it holds less than `bytes`; the scene's device bytes follow it
+int grow(DevBuf& b, size_t bytes, size_t* total) {
+    const size_t had = b.bytes;
+    const hipError_t e = b.ensure(std::max<size_t>(bytes, 16));
+    *total = *total - had + b.bytes;
+    if (e != hipSuccess) return fail(PRT_ERR_OOM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    return PRT_OK;
+}
+
+// Stage 4 of a rebuild for one width: the levels top-down (one count read back per level), then the node
+// records into `nodes`, grown to the tree's size first.  The keys' binary tree is in b.split.
+int build_wide(Scene* s, int width, DevBuf& nodes, LbvhLevels* lv, int* need) {
+    RebuildState& b = s->rebuild;
+    hipStream_t st = s->stream;
+    const int64_t n = s->n_tri, cap = lbvh_node_capacity(n), widest = n / 2 + 1;
+    auto* items = (LbvhItem*)b.items.p;
+    HIP_TRY(launch_lbvh_root(items, n, (int32_t*)b.max_anc.p, st));
+    *lv = LbvhLevels();
+    lv->push(1, cap, widest);
+    for (;;) {
+        const int64_t base = lv->off[(size_t)lv->depth()], count = lv->n_nodes() - base;
+        HIP_TRY(launch_lbvh_level(width, items, base, count, lv->n_nodes(), (const int32_t*)b.split.p, s->max_leaf,
+                                  (int32_t*)b.cnt.p, (int32_t*)b.off.p, (int32_t*)b.child0.p, (int32_t*)b.max_anc.p,
+                                  b.temp.p, b.temp.bytes, st));
+        int32_t next = 0;
+        HIP_TRY(hipMemcpyAsync(&next, (const int32_t*)b.off.p + count, sizeof next, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (next == 0) break;
+        if (!lv->push(next, cap, widest)) return fail(PRT_ERR_INTERNAL, "internal: rebuilt tree outgrew its bound");
+    }
+    int32_t max_anc = 0;
+    HIP_TRY(hipMemcpyAsync(&max_anc, b.max_anc.p, sizeof max_anc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *need = wide_stack_need(max_anc, width);
+    const size_t node_bytes = sizeof(float) * 4 * (size_t)(width == 8 ? kNode8F4 : kNode4F4);
+    if (int rc = grow(nodes, node_bytes * (size_t)lv->n_nodes(), &s->device_bytes)) return rc;
+    HIP_TRY(launch_lbvh_emit(width, items, (const int32_t*)b.child0.p, lv->n_nodes(), (const int32_t*)b.split.p,
+                             s->max_leaf, (float*)nodes.p, st));
+    return PRT_OK;
+}
+
+// device half of prt_scene_rebuild (validated arguments, packed shading data): DESIGN.md §14
+int rebuild_scene(Scene* s, const float* tri_v, const float* sph, const PackedScene& pk, float pad) {
+    RefitState& r = s->refit;
+    RebuildState& b = s->rebuild;
+    const int64_t n = s->n_tri;
+    // no render of this scene may be in flight on any of its streams while its buffers change
+    HIP_TRY(hipDeviceSynchronize());
+    if (int rc = refit_resident(s)) return rc;
+    size_t* total = &s->device_bytes;
+    const LbvhScratch z = lbvh_scratch(n);
+    size_t temp_bytes = 0;
+    HIP_TRY(lbvh_temp_bytes(n, &temp_bytes));
+    DevBuf* words[] = {&b.codes, &b.ids, &b.codes_sorted, &b.split, &b.child0};
+    for (DevBuf* w : words)
+        if (int rc = grow(*w, z.word, total)) return rc;
+    if (int rc = grow(b.cen, z.cen, total)) return rc;
+    if (int rc = grow(b.cbox, 32, total)) return rc;
+    if (int rc = grow(b.keys, z.key, total)) return rc;
+    if (int rc = grow(b.items, z.item, total)) return rc;
+    if (int rc = grow(b.cnt, z.count, total)) return rc;
+    if (int rc = grow(b.off, z.count, total)) return rc;
+    if (int rc = grow(b.max_anc, 16, total)) return rc;
+    if (int rc = grow(b.temp, temp_bytes, total)) return rc;
+    for (hipEvent_t& e : b.ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    hipStream_t st = s->stream;
+    HIP_TRY(hipEventRecord(b.ev[0], st));
+    if (int rc = put(r.d_tri_v, tri_v, sizeof(float) * 9 * (size_t)n, st)) return rc;
+    if (int rc = put(s->tri_nm, pk.tri_nm.data(), sizeof(float) * pk.tri_nm.size(), st)) return rc;
+    if (int rc = put(s->tri_frame, pk.tri_frame.data(), sizeof(float) * pk.tri_frame.size(), st)) return rc;
+    if (int rc = put(s->light_v, pk.light_v.data(), sizeof(float) * pk.light_v.size(), st)) return rc;
+    if (int rc = put(s->sph, sph, sizeof(float) * 4 * (size_t)s->n_sph, st)) return rc;
+    HIP_TRY(hipEventRecord(b.ev[1], st));
+    HIP_TRY(launch_lbvh_codes((const float*)r.d_tri_v.p, n, (float*)b.cen.p, (float*)b.cbox.p, (uint32_t*)b.codes.p,
+                              (uint32_t*)b.ids.p, b.temp.p, b.temp.bytes, st));
+    HIP_TRY(hipEventRecord(b.ev[2], st));
+    // one slot per triangle: the order's buffer, sized for creation's slots, holds them
+    HIP_TRY(launch_lbvh_sort((const uint32_t*)b.codes.p, (const uint32_t*)b.ids.p, n, (uint32_t*)b.codes_sorted.p,
+                             (int32_t*)r.d_order.p, (uint64_t*)b.keys.p, b.temp.p, b.temp.bytes, st));
+    HIP_TRY(hipEventRecord(b.ev[3], st));
+    HIP_TRY(launch_lbvh_topology((const uint64_t*)b.keys.p, n, (int32_t*)b.split.p, st));
+    HIP_TRY(hipEventRecord(b.ev[4], st));
+    LbvhLevels lv4, lv8;
+    int need4 = 0, need8 = 0;
+    if (int rc = build_wide(s, 4, s->nodes4, &lv4, &need4)) return rc;
+    s->n_tri_f4 = kTriF4 * n;
+    s->n_node4_f4 = lv4.n_nodes() * kNode4F4;
+    s->n_node4q_f4 = lv4.n_nodes() * kNodeQF4;
+    s->need4 = need4;
+    s->stack4 = need4 <= 32 ? stack_variant(need4 - 1) : 0;
+    s->n_nodes = lv4.n_nodes();
+    s->depth = lv4.depth();
+    s->n_node8_f4 = 0;
+    s->need8 = s->stack8 = 0;
+    s->lds_width = 4;
+    // LDS-resident scenes also get the eight-wide tree, and the width rule again (fill_scene)
+    if (lds_fits(sizes_of(s, 4))) {
+        if (int rc = build_wide(s, 8, s->nodes8, &lv8, &need8)) return rc;
+        s->n_node8_f4 = lv8.n_nodes() * kNode8F4;
+        s->need8 = need8;
+        s->stack8 = need8 <= 32 ? stack_variant(need8 - 1) : 0;
+        s->lds_width = lds_width(sizes_of(s, 8), s->need8, s->lds_width_knob);
+    }
+    if (int rc = grow(s->nodes4q, sizeof(float) * 4 * (size_t)s->n_node4q_f4, total)) return rc;
+    if (int rc = grow(r.d_level4, sizeof(int32_t) * (size_t)lv4.n_nodes(), total)) return rc;
+    if (int rc = grow(r.d_level8, sizeof(int32_t) * (size_t)lv8.n_nodes(), total)) return rc;
+    HIP_TRY(launch_lbvh_iota((int32_t*)r.d_level4.p, lv4.n_nodes(), st));
+    HIP_TRY(launch_lbvh_iota((int32_t*)r.d_level8.p, lv8.n_nodes(), st));
+    HIP_TRY(hipEventRecord(b.ev[5], st));
+    // stage 5: the refit's own launches on the new order and level lists
+    r.off4 = lv4.off;
+    r.off8 = lv8.off;
+    r.level4 = iota_list(lv4.n_nodes());
+    r.level8 = iota_list(lv8.n_nodes());
+    HIP_TRY(launch_refit_tris((const float*)r.d_tri_v.p, (const int32_t*)r.d_order.p, n, (float4*)s->tris.p,
+                              (float*)r.d_bounds.p, st));
+    if (int rc = refit_tree(4, s->nodes4, r.d_level4, r.off4, r.d_bounds, pad, st)) return rc;
+    if (s->n_node8_f4 > 0)
+        if (int rc = refit_tree(8, s->nodes8, r.d_level8, r.off8, r.d_bounds, pad, st)) return rc;
+    HIP_TRY(hipEventRecord(b.ev[6], st));
+    HIP_TRY(launch_refit_quantize((const float*)s->nodes4.p, lv4.n_nodes(), pad, (float*)s->nodes4q.p, st));
+    HIP_TRY(hipEventRecord(b.ev[7], st));
+    r.order.resize((size_t)n);
+    if (n) HIP_TRY(hipMemcpyAsync(r.order.data(), r.d_order.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 7; ++k) {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, b.ev[k], b.ev[k + 1]));
+        b.ms[k + 1] = ms;
+    }
+    const int64_t info[8] = {lv4.n_nodes(), lv4.depth(), need4, s->n_node8_f4 ? lv8.n_nodes() : 0,
+                             s->n_node8_f4 ? lv8.depth() : 0, need8, s->lds_width, n};
+    std::memcpy(b.info, info, sizeof info);
+    ++b.count;
+    s->shade_fast = pk.shade_fast;
+    std::memset(s->occ, 0, sizeof s->occ);   // the blocks per CU were those of the old tree's stacks
+    s->blocks_per_cu = variant_occ(s, launch_variant(s, 0), false);
+    return PRT_OK;
+}
+
 }  // namespace
 }  // namespace prt
 
@@ -334,8 +478,9 @@ int prt_scene_create(int device, const float* tri_v, const float* tri_n, const i
 
     BvhHost bvh;
     PackedScene pk;
+    const int max_leaf = (int)env_int("PRT_MAX_LEAF", INT32_MIN, INT32_MAX, 4);
     try {
-        if (!build_bvh(tri_v, n_tri, (int)env_int("PRT_MAX_LEAF", INT32_MIN, INT32_MAX, 4), &bvh, &err))
+        if (!build_bvh(tri_v, n_tri, max_leaf, &bvh, &err))
             return fail(PRT_ERR_ARG, err);
         pack_scene(a, &pk);
     } catch (const std::bad_alloc&) {
@@ -344,6 +489,7 @@ int prt_scene_create(int device, const float* tri_v, const float* tri_n, const i
     auto* s = new (std::nothrow) Scene();
     if (!s) return fail(PRT_ERR_OOM, "host allocation failed");
     s->device = device;
+    s->max_leaf = max_leaf;
     s->n_tri = n_tri;
     s->n_nodes = bvh.n_nodes;
     s->depth = bvh.depth;
@@ -386,6 +532,42 @@ int prt_scene_update(void* scene, const float* tri_v, const float* tri_n, const 
     r.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     DeviceGuard g(s->device);
     return update_scene(s, tri_v, sph, pk, pad);
+}
+
+int prt_scene_rebuild(void* scene, const float* tri_v, const float* tri_n, const float* sph) {
+    auto* s = (Scene*)scene;
+    if (!s) return fail(PRT_ERR_ARG, "scene is NULL");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string err;
+    if (!validate_update(tri_v, tri_n, s->n_tri, sph, s->n_sph, &err)) return fail(PRT_ERR_ARG, err);
+    if (s->n_tri >= kLbvhMaxSlots) return fail(PRT_ERR_ARG, "a rebuild takes fewer than 2^28 triangles");
+    RefitState& r = s->refit;
+    const SceneArgs a{tri_v, tri_n, r.tri_mat.data(), s->n_tri, sph, r.sph_mat.data(), s->n_sph, r.mat.data(), s->n_mat,
+                      r.light_tri.data(), r.light_off.data(), s->n_light};
+    PackedScene pk;
+    float pad = 0.0f;
+    try {
+        pack_scene(a, &pk);
+        pad = bvh_pad(tri_v, s->n_tri);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_ERR_OOM, "host allocation failed during the scene rebuild");
+    }
+    s->rebuild.ms[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    DeviceGuard g(s->device);
+    try {
+        return rebuild_scene(s, tri_v, sph, pk, pad);
+    } catch (const std::bad_alloc&) {
+        return fail(PRT_ERR_OOM, "host allocation failed during the scene rebuild");
+    }
+}
+
+int prt_scene_rebuild_info(void* scene, int64_t* info8, double* ms8) {
+    auto* s = (Scene*)scene;
+    if (!s) return fail(PRT_ERR_ARG, "scene is NULL");
+    if (s->rebuild.count == 0) return fail(PRT_ERR_ARG, "the scene has not been rebuilt");
+    if (info8) std::memcpy(info8, s->rebuild.info, sizeof s->rebuild.info);
+    if (ms8) std::memcpy(ms8, s->rebuild.ms, sizeof s->rebuild.ms);
+    return PRT_OK;
 }
 
 int prt_scene_download(void* scene, int which, void* out, int64_t bytes) {

@@ -96,6 +96,8 @@ class DeviceScene:
                                    flat.sph.shape[0], N.ptr(flat.mat), flat.mat.shape[0], N.ptr(flat.light_tri),
                                    N.ptr(flat.light_off), flat.n_light, N.ptr(flat.direct_rgb), ctypes.byref(h)))
         self.h = h
+        self.last_update = None      # "refit" or "rebuild": what the last update() / rebuild() did
+        self._built_cost = None      # tree_cost() at the last build, taken when update(rebuild_ratio=) first asks
         self._read_info()
 
     def _read_info(self):
@@ -123,16 +125,54 @@ class DeviceScene:
             if a.shape != b.shape or a.tobytes() != b.tobytes():
                 raise ValueError(f"update() moves geometry only: {k} differs from the scene's")
 
-    def update(self, flat):
+    def update(self, flat, rebuild_ratio=None):
         """prt_scene_update: the scene's primitives moved to `flat`'s tri_v, tri_n and sph.  The trees are refit
         on the device; the handle, its buffers and render contexts stay.  Everything else of
-        `flat` must be the scene's (ValueError)."""
+        `flat` must be the scene's (ValueError).
+
+        rebuild_ratio: None (default) only refits.  A number r refits, then rebuilds the trees on the device
+        (rebuild()) if tree_cost() exceeds r times its value at the last build: creation, or the last rebuild.
+        The baseline is read (one download of the four-wide nodes) when a ratio is first given, before that call
+        moves anything: give the ratio from the first update on, or it is the cost of whatever pose earlier
+        plain update()s left.  `last_update` says which of "refit" and "rebuild" the call ended with.  No default
+        ratio is offered:
+        DESIGN.md §14 has the measured break-even."""
+        if rebuild_ratio is not None and not (isinstance(rebuild_ratio, (int, float)) and rebuild_ratio > 0):
+            raise ValueError(f"rebuild_ratio must be a number > 0 or None, not {rebuild_ratio!r}")
         self.check_compatible(flat)
+        if rebuild_ratio is not None and self._built_cost is None:
+            self._built_cost = self.tree_cost()      # of the pose this tree was built at, before it moves
         sph = flat.sph if flat.sph.shape[0] else None
         N.check(N.lib().prt_scene_update(self.h, N.ptr(flat.tri_v), N.ptr(flat.tri_n), N.ptr(sph)))
         self.flat = flat
         self._read_info()     # the first update allocates its device copies: device_bytes grows by them
+        self.last_update = "refit"
+        if rebuild_ratio is not None and self.tree_cost() > rebuild_ratio * self._built_cost:
+            self.rebuild(flat)
         return self
+
+    def rebuild(self, flat=None):
+        """prt_scene_rebuild: the trees built again on the device, a linear BVH over `flat`'s triangles (default:
+        the scene's current geometry), into this resident scene: for a tree that refits have
+        loosened.  `flat` as for update().  The handle and its render contexts stay; later update()s refit the
+        new tree, and tree_cost()'s baseline for update(rebuild_ratio=) is the new tree's."""
+        flat = self.flat if flat is None else flat
+        self.check_compatible(flat)
+        sph = flat.sph if flat.sph.shape[0] else None
+        N.check(N.lib().prt_scene_rebuild(self.h, N.ptr(flat.tri_v), N.ptr(flat.tri_n), N.ptr(sph)))
+        self.flat = flat
+        self._read_info()
+        self._built_cost = self.tree_cost()
+        self.last_update = "rebuild"
+        return self
+
+    def rebuild_info(self):
+        """prt_scene_rebuild_info: the last rebuild's trees and stage times, dict(nodes4, depth4, need4, nodes8,
+        depth8, need8, lds_width, slots, ms): ms the eight times in milliseconds (include/prt.h)."""
+        info, ms = np.zeros(8, np.int64), np.zeros(8, np.float64)
+        N.check(N.lib().prt_scene_rebuild_info(self.h, N.ptr(info), N.ptr(ms)))
+        keys = ("nodes4", "depth4", "need4", "nodes8", "depth8", "need8", "lds_width", "slots")
+        return dict(zip(keys, (int(v) for v in info)), ms=ms)
 
     def download(self, name):
         """prt_scene_download: the device buffer `name` (one of BUFFERS) as a (rows, n) array in the layout

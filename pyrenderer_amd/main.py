@@ -88,6 +88,10 @@ def parse(argv=None):
     ap.add_argument("--refit", action="store_true",
                     help="with --frames and --spin: refit the resident scene's BVH on the GPU between frames instead "
                          "of building a new scene per frame (same images)")
+    ap.add_argument("--rebuild-ratio", type=float, default=None, metavar="R",
+                    help="with --refit: build the resident scene's BVH again on the GPU once refits have raised "
+                         "its tree cost above R times the value at the last build (same images); no default, "
+                         "DESIGN.md section 14 has the measured break-even")
     ap.add_argument("--adaptive", type=float, default=None, metavar="TARGET",
                     help="adaptive sampling: render in batches of --batch-spp and stop every 64 x 64 tile once the "
                          "relative standard error of its pixels' demodulated luminance is at most TARGET; needs "
@@ -130,6 +134,10 @@ def parse(argv=None):
             ap.error(f"--spin needs a primitive index >= 0 and finite degrees, not {args.spin[0]} {args.spin[1]}")
     if args.refit and args.spin is None:
         ap.error("--refit refits the scene that --spin moves: it needs --frames N --spin PRIM DEG")
+    if args.rebuild_ratio is not None and not args.refit:
+        ap.error("--rebuild-ratio rebuilds the scene that --refit keeps resident: it needs --refit")
+    if args.rebuild_ratio is not None and not (np.isfinite(args.rebuild_ratio) and args.rebuild_ratio > 0):
+        ap.error(f"--rebuild-ratio needs a finite ratio > 0, not {args.rebuild_ratio}")
     if not args.frames:
         for flag, given in (("--orbit", args.orbit != 0.0), ("--temporal", args.temporal), ("--spin", args.spin),
                             ("--refit", args.refit)):
@@ -238,7 +246,8 @@ def render_frames(args, scene, camera, W, H):
     acc = None
     if args.temporal:
         acc = TemporalAccumulator(scene, depth=args.depth, spp=args.samples, seed=args.seed, resolution=(W, H),
-                                  device=args.devices[0], world=world, nee=args.nee, refit=refit)
+                                  device=args.devices[0], world=world, nee=args.nee, refit=refit,
+                                  rebuild_ratio=args.rebuild_ratio if refit else None)
     mean = None
     for t in range(args.frames):
         cam = orbit(camera, t * args.orbit)
@@ -248,7 +257,7 @@ def render_frames(args, scene, camera, W, H):
             mean = acc.denoised(iterations=it) if args.denoise else acc.accumulated()
         else:
             if refit and t > 0:
-                world.update(scenes[t].primitives)
+                world.update(scenes[t].primitives, rebuild_ratio=args.rebuild_ratio)
             elif scenes is not None and t > 0:   # every frame stands alone, in its own world
                 for ds in world.device_scenes.values():
                     ds.close()

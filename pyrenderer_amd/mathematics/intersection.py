@@ -39,17 +39,25 @@ class World:
                 self.device_scenes[d] = DeviceScene(self.flat, d)
         return self
 
-    def update(self, primitives):
+    def update(self, primitives, rebuild_ratio=None):
         """The committed world's primitives moved: `primitives` are the same ones in the same order with new
         poses (e.g. pyrenderer_amd.scenes.moved(...).primitives).  Re-flattens and refits every device scene in
         place (DeviceScene.update); a ValueError (raised before any device scene changes) when anything but
-        the geometry differs."""
+        the geometry differs.  rebuild_ratio: DeviceScene.update's, None (default) only ever refits."""
+        return self._move(primitives, lambda ds, flat: ds.update(flat, rebuild_ratio=rebuild_ratio))
+
+    def rebuild(self, primitives=None):
+        """Builds every device scene's trees again on its GPU (DeviceScene.rebuild), at the poses of `primitives`
+        (as for update(); default: the world's own)."""
+        return self._move(self.primitives if primitives is None else primitives, lambda ds, flat: ds.rebuild(flat))
+
+    def _move(self, primitives, apply):
         primitives = list(primitives)
         flat = flatten_scene(_PrimList(primitives))
         for ds in self.device_scenes.values():
             ds.check_compatible(flat)
         for ds in self.device_scenes.values():
-            ds.update(flat)
+            apply(ds, flat)
         self.primitives, self.lights = [], []
         for p in primitives:
             self.add(p)
